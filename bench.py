@@ -17,7 +17,10 @@ all-to-all turns pair shards into l shards for K2, a second all-to-all hands eve
 factor rows of its own channels; every rank generates the same global normal stream and
 synthesises F/N channels.  Total work is fixed -> "scaling": "strong".
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the line (stage times and
+rooflines come from the timed steps themselves).  --full adds the legs that take runs of their own: the warm path, the
+numpy-seeded and legacy-RNG modes, the host-delivered rate, the drop-in call and the CPU baseline.  --dump-outputs DIR
+writes the maps of the last timed step (a fixed sample of pixels, see dump_outputs) to DIR/maps.npy.
 """
 import argparse
 import json
@@ -50,6 +53,7 @@ MIN_RANKS = {"cfg5": 8}        # workloads that do not fit fewer GPUs: emulate o
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X vendor spec; profiles/mfma_f64_probe_r01.txt measures 77.4
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md
 L2_PEAK_GBS = 34500.0          # MI355X_MICROARCH.md: L2 (per XCD, aggregate) ~34.5 TB/s
+DUMP_VALUES = 1 << 22          # --dump-outputs: at most 4 Mi float64 values (32 MiB) of maps
 
 
 def build_model(name):
@@ -93,6 +97,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs outside the headline: warm path, seeded / legacy-RNG modes, host-delivered rate, "
+                         "drop-in call, CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the maps of the last timed step (fixed sample of pixels, float64) to DIR/maps.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--warm", action="store_true", help="time the warm path only (factors cached)")
     ap.add_argument("--no-host-delivered", action="store_true", help="skip the PCIe-inclusive (numpy-returning) leg")
@@ -289,10 +298,14 @@ def main():
     maps_buf = shard.maps_buf
     cold_factors = shard.factors
 
+    # before any later leg overwrites the maps buffer
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, shard, F, dist, rank)
+
     # warm path (factors cached: draw + synthesis only - what repeated seeds amortise, cora/signal/lss.py:424-478),
     # measured after the timed region and reported next to the headline (cold) number
     warm_ms = None
-    if not args.warm and args.emulate_shard <= 1:
+    if args.full and not args.warm and args.emulate_shard <= 1:
         fac = cold_factors()
         nw = max(1, min(3, args.steps))
         barrier()
@@ -309,10 +322,10 @@ def main():
     # where numpy would leave it) instead of the library's Philox stream; and the legacy mode (rng=None: numpy's global
     # MT19937 + polar method, what Sky3d.getsky() draws from), generated on the device as well
     # Since round 5 the stream is generated range of multipoles by range (no 16 F nalm byte buffer), so the legs run on
-    # every line: multi-component workloads (separate: the components draw one after the other from the one generator),
+    # every --full line: multi-component workloads (separate: the components draw one after the other from the one generator),
     # emulated shards and real ranks (every rank consumes the whole stream for its own rows of the factors).
     seeded_numpy = legacy_rng = None
-    if not (args.no_seeded_modes or args.checksum or args.warm):
+    if args.full and not (args.no_seeded_modes or args.checksum or args.warm):
         seeded_numpy, legacy_rng = seeded_modes(ctx, shard, cold_factors, F, lmax, barrier, args.steps, len(comps)
                                                 if args.sum_mode == "separate" else 1, nnu)
 
@@ -320,7 +333,7 @@ def main():
     # realisation crosses PCIe.  skysim.mkfullsky_stream double-buffers that copy (pinned memory, copy stream) behind the
     # next realisation; measured after the timed region, reported next to the HBM-resident headline, never as `value`.
     host_delivered = None
-    if rank == 0 and world == 1 and args.emulate_shard <= 1 and len(comps) == 1 and not args.no_host_delivered:
+    if args.full and rank == 0 and world == 1 and args.emulate_shard <= 1 and len(comps) == 1 and not args.no_host_delivered:
         try:
             host_delivered = host_delivered_rate(ctx, shard, nside, F, npix)
         except Exception as e:      # (e.g. a box that cannot page-lock 80 GB): the leg is extra, the headline must not die with it
@@ -331,7 +344,7 @@ def main():
     # (cora/core/skysim.py:72-136; the second half of Sky3d.getsky(), cora/core/maps.py:227-237) - H2D of the 1.07 GB
     # C_l, factor + seeded draw + synthesis, D2H of the 25.8 GB of maps into a fresh numpy array.  Outside the timed region.
     drop_in = None
-    if rank == 0 and world == 1 and args.emulate_shard <= 1 and len(comps) == 1 and not (args.no_host_delivered or args.checksum or args.warm):
+    if args.full and rank == 0 and world == 1 and args.emulate_shard <= 1 and len(comps) == 1 and not (args.no_host_delivered or args.checksum or args.warm):
         try:
             drop_in = drop_in_call(build_model(comps[0][0]), freq, nside, lmax, zromb, F, npix)
         except Exception as e:      # (extra leg: the headline must not die with it)
@@ -491,7 +504,7 @@ def main():
                 "frac": alg_bytes / 1e9 / (ms_step * 1e-3) / HBM_PEAK_GBS,
             },
         }
-        if not args.no_cpu_baseline and world == 1 and len(comps) == 1 and not emu:
+        if args.full and not args.no_cpu_baseline and world == 1 and len(comps) == 1 and not emu:
             result["cpu_baseline"] = cpu_baseline(model_name, F, freq, nside, lmax, zromb)
             result["config"]["gpu_over_cpu"] = value / result["cpu_baseline"]["value"]
         os.write(json_fd, (json.dumps(result) + "\n").encode())
@@ -499,6 +512,27 @@ def main():
     if dist is not None:
         dist.destroy_process_group()
     return result
+
+
+def dump_outputs(path, shard, F, dist, rank):
+    """--dump-outputs: the maps of the last timed step - what `realise` hands its caller - as DIR/maps.npy, float64,
+    [channel, pixel] in global channel order (the channels this run made: all F, or the emulated rank's share).  The
+    pixels are a fixed sample, the same in every run at the same nside: all of them when F maps hold at most
+    DUMP_VALUES values, otherwise DUMP_VALUES // F pixels drawn by default_rng(0) without replacement, ascending."""
+    import torch
+
+    n = min(shard.npix, DUMP_VALUES // F)
+    pix = np.arange(n) if n == shard.npix else np.sort(np.random.default_rng(0).choice(shard.npix, n, replace=False))
+    part = shard.maps_buf.index_select(1, torch.as_tensor(pix, device=shard.maps_buf.device)).cpu().numpy()
+    parts = [(np.asarray(shard.channels), part)]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, (np.asarray(shard.channels), part))
+    if rank == 0:
+        chans = np.concatenate([c for c, _ in parts])
+        maps = np.concatenate([p for _, p in parts])[np.argsort(chans, kind="stable")]
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "maps.npy"), maps.astype(np.float64))
 
 
 def exchange_model(comps, F, L, N, sum_mode, critical_ms):

@@ -476,6 +476,45 @@ def test_bench_self_launch_command(monkeypatch):
         assert name in bench.WORKLOADS
 
 
+def test_bench_dump_outputs_sample_and_channel_order(tmp_path):
+    """bench.py --dump-outputs writes the maps of the last step as DIR/maps.npy, float64, in global channel order: whole
+    maps when they are small, otherwise the same default_rng(0) pixel sample on every run, within DUMP_VALUES values; an
+    N-rank job (here a folded 2-rank one, gathered by a stand-in process group) gives the single-rank array."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Shard:
+        def __init__(self, full, chans):
+            self.npix, self.channels, self.maps_buf = full.shape[1], np.array(chans), full[list(chans)].clone()
+
+    small = torch.randn(16, 12 * 64 * 64, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), Shard(small, range(16)), 16, None, 0)
+    m = np.load(str(tmp_path / "a" / "maps.npy"))
+    assert m.dtype == np.float64 and np.array_equal(m, small.numpy())
+
+    big = torch.randn(256, 12 * 256 * 256, dtype=torch.float64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), Shard(big, range(256)), 256, None, 0)
+    m = np.load(str(tmp_path / "b" / "maps.npy"))
+    assert m.shape == (256, bench.DUMP_VALUES // 256) and m.nbytes <= 64 << 20
+    pix = np.sort(np.random.default_rng(0).choice(big.shape[1], m.shape[1], replace=False))
+    assert np.array_equal(m, big.numpy()[:, pix]) and np.array_equal(m, np.load(str(tmp_path / "c" / "maps.npy")))
+
+    r0, r1 = Shard(small, [0, 1, 2, 3, 12, 13, 14, 15]), Shard(small, range(4, 12))
+
+    class Group:
+        def get_world_size(self):
+            return 2
+
+        def all_gather_object(self, parts, obj):
+            parts[:] = [obj, (r1.channels, r1.maps_buf.numpy())]
+
+    bench.dump_outputs(str(tmp_path / "d"), r0, 16, Group(), 0)
+    assert np.array_equal(np.load(str(tmp_path / "d" / "maps.npy")), small.numpy())
+
+
 # ------------------------------------------------------------------ bench line bookkeeping (no GPU)
 @pytest.mark.parametrize("line,workload,nranks,nu0,nnu,mode", [
     ("bench_cfg3_r03_final.json", "cfg3", 1, 0, 256, "joint"),

@@ -3,7 +3,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_lds
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $OUT -o lds -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-host-delivered --no-seeded-modes > /dev/null 2> $OUT/lds.err
+rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES --output-format csv -d $OUT -o lds -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-host-delivered --no-seeded-modes > /dev/null 2> $OUT/lds.err
 python3 - <<PY
 import csv, collections
 f="$OUT/lds_counter_collection.csv"

@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 run() { n=$1; shift
   rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT -o $n -- "$@" > /dev/null 2> $OUT/$n.err
 }
-run bench python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+run bench python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline
 run analysis python3 tools/bench_analysis.py
 run corrfunc python3 tools/bench_corrfunc.py
 run pol python3 tools/bench_pol.py

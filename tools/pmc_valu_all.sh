@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_valu
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT -o mix -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/mix.err
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT -o mix -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/mix.err
 python3 - <<'PY'
 import csv, glob, os, collections
 out = os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/pmc_valu"

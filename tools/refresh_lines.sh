@@ -6,8 +6,8 @@
 TAG=${1:-r05}
 OUT=gpurun_out/lines_$TAG
 mkdir -p $OUT
-B="python3 bench.py --no-cpu-baseline --no-host-delivered"
-python3 bench.py > $OUT/bench_cfg3_${TAG}_with_baselines.json 2> $OUT/default.err || exit 1
+B="python3 bench.py --full --no-cpu-baseline --no-host-delivered"
+python3 bench.py --full > $OUT/bench_cfg3_${TAG}_with_baselines.json 2> $OUT/default.err || exit 1
 for n in 2 4 8; do $B --emulate-shard $n > $OUT/bench_cfg3_emulated_shard${n}_${TAG}.json 2>> $OUT/shard.err || exit 1; done
 $B --emulate-shard 8 --fold > $OUT/bench_cfg3_emulated_shard8_fold_${TAG}.json 2>> $OUT/shard.err || exit 1
 $B --workload cfg4 --sum-mode joint --steps 4 --warmup 1 > $OUT/bench_cfg4_${TAG}_joint.json 2>> $OUT/cfg4.err || exit 1
