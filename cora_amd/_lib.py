@@ -692,10 +692,11 @@ class Context:
         _check(self.lib.corahip_alm2map(self.h, plan, self._f64(alm), nnu, self._f64(maps), self._p(ws), need))
         return maps
 
-    def mkfullsky_fused(self, C, nside, rng, nu0=0, nnu=None, alms=False, workspace_bytes=None):
+    def mkfullsky_fused(self, C, nside, rng, nu0=0, nnu=None, alms=False, workspace_bytes=None, workspace=None):
         """``corahip_mkfullsky``: C [L, F, F] (device) -> maps [nnu, npix] or, with ``alms``, a_lm [nnu, 1, L, L] complex,
         in one library call.  ``rng``: ("pcg64", state, inc) python ints of a numpy bit generator - returns the state
-        after the draws -, ("stream", g) device normals in stream order, or ("philox", seed).  Returns (out, state)."""
+        after the draws -, ("stream", g) device normals in stream order, or ("philox", seed).  ``workspace``: a caller's
+        uint8 device buffer of at least the bytes the call takes (default: a fresh one).  Returns (out, state)."""
         torch = _torch()
         L, F = int(C.shape[0]), int(C.shape[1])
         lmax = L - 1
@@ -733,7 +734,11 @@ class Context:
         b = c_size_t()
         _check(self.lib.corahip_mkfullsky_workspace_bytes(plan, F, nu0, nnu, kind, 1 if alms else 0, ctypes.byref(b)))
         need = int(b.value) if workspace_bytes is None else int(workspace_bytes)
-        ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        if workspace is None:
+            ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        else:
+            ws = workspace
+            assert ws.dtype == torch.uint8 and ws.device == self.device and ws.numel() >= need, (ws.numel(), need)
         out = (torch.empty((nnu, 1, L, L), dtype=torch.complex128, device=self.device) if alms
                else self.empty((nnu, 12 * nside * nside)))
         _check(self.lib.corahip_mkfullsky(self.h, plan, self._f64(C), F, ctypes.byref(r), nu0, nnu, 1 if alms else 0,
@@ -750,11 +755,11 @@ class Context:
         _check(self.lib.corahip_map2alm_workspace_bytes(plan, nnu, ctypes.byref(b)))
         return int(b.value)
 
-    def map2alm(self, maps, nside, lmax, ring_w=None, chunk=None):
+    def map2alm(self, maps, nside, lmax, ring_w=None, chunk=None, out=None):
         """One weighted quadrature pass maps [nnu, npix] -> alm_dev [nalm, ceil(nnu/4), 2, 4] (K5^T + K4^T).
 
         ring_w: device [2 nside] north-ring weights or None.  Channels go through in chunks of `chunk`
-        (a multiple of 8; default: as many as a 96 GB workspace holds)."""
+        (a multiple of 8; default: as many as a 96 GB workspace holds).  out: the alm_dev buffer to write."""
         torch = _torch()
         plan = self.sht_plan(nside, lmax)
         nnu, npix = maps.shape
@@ -765,7 +770,9 @@ class Context:
             per8 = self.map2alm_workspace_bytes(plan, 8)
             chunk = max(8, min((int(96e9 // per8)) * 8, (nnu + 7) // 8 * 8))
         assert chunk % 8 == 0
-        out = self.empty((nalm, G4, 2, 4))
+        if out is None:
+            out = self.empty((nalm, G4, 2, 4))
+        assert tuple(out.shape) == (nalm, G4, 2, 4), out.shape
         for c0 in range(0, nnu, chunk):
             n = min(chunk, nnu - c0)
             G8 = (n + 7) // 8 * 2
@@ -791,9 +798,9 @@ class Context:
         return maps
 
     # -- spin-2 analysis (composition of scalar passes) ---------------------------------------
-    def map2alm_spin2(self, maps_qu, nside, lmax, ring_w=None):
+    def map2alm_spin2(self, maps_qu, nside, lmax, ring_w=None, out=None):
         """One quadrature pass (Q_f, U_f interleaved) [2 nf, npix] -> alm_dev [nalm, G, 2, 4] with (E_f, B_f)
-        interleaved, G = nnu_pad8(2 nf) / 4 (the layout alm2map_spin2 takes)."""
+        interleaved, G = nnu_pad8(2 nf) / 4 (the layout alm2map_spin2 takes); out: the alm_dev buffer to write."""
         plan = self.sht_plan(nside, lmax)
         n2, npix = maps_qu.shape
         assert n2 % 2 == 0 and npix == 12 * nside * nside
@@ -804,7 +811,9 @@ class Context:
         a6 = self.map2alm(maps6, nside, lmax, ring_w)
         del maps6
         gout = (2 * nf + 7) // 8 * 2
-        out = self.empty((nalm, gout, 2, 4))
+        if out is None:
+            out = self.empty((nalm, gout, 2, 4))
+        assert tuple(out.shape) == (nalm, gout, 2, 4), out.shape
         _check(self.lib.corahip_spin2_combine(self.h, plan, self._f64(a6), a6.shape[1], nf, self._f64(out), gout))
         return out
 

@@ -616,7 +616,8 @@ ringfft_blu_ct(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
 //             contiguous bytes; the loads of the NEXT item are issued behind this pass and complete behind the others),
 //   pass B^H, A^H  radix 16 with the conjugate twiddles in front (decimation in time): Z_k in natural order,
 //   split     X_m = 1/2 [(Z_m + conj Z_{N-m}) - i e^{-i pi m / N} (Z_m - conj Z_{N-m})], G_m = w_ring (4 pi / npix)
-//             e^{-i m phi0} X_m for m < mcut(ring) <= N + 1 (no aliasing on a belt ring), stored as whole 64-byte cells.
+//             e^{-i m phi0} X_m for m < mcut(ring) <= N + 1, stored as whole 64-byte cells.  Only launched for
+//             lmax <= N (sht_ringana_ct): above that the belt rings alias and the run-time kernel takes them.
 // Every twiddle and phase is a per-thread constant of the kernel (phi0 of a belt ring is 0 or pi / (2 N)).
 // ------------------------------------------------------------------------------------
 template <int N, int NCH, int T>
@@ -1120,8 +1121,10 @@ int sht_ringana_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sh
     hipStream_t st = ctx->stream;
     int rc;
 #define ANA_ARGS ctx, st, p, c, maps, nvalid, nnu_pad, ring_w, G, inter
-    if (c.P == 0 && c.N == 2048) rc = launch_ana_direct<2048, 4, 512>(ANA_ARGS);
-    else if (c.P == 0 && c.N == 4096) rc = launch_ana_direct<4096, 2, 512>(ANA_ARGS);
+    // (the direct kernels store m <= N only: with lmax > N - the aliased lmax = 3 nside - 1 - the belt's cells
+    //  N < m < mcut hold aliases they do not write, and the class goes to the run-time ringana_kernel, which folds them)
+    if (c.P == 0 && c.N == 2048 && p->lmax <= c.N) rc = launch_ana_direct<2048, 4, 512>(ANA_ARGS);
+    else if (c.P == 0 && c.N == 4096 && p->lmax <= c.N) rc = launch_ana_direct<4096, 2, 512>(ANA_ARGS);
     else if (c.P3 == 2560 && !no3) rc = launch_ana_blu<2560, 2, 512>(ANA_ARGS, true);
     else if (c.P3 == 3584 && !no3) rc = launch_ana_blu<3584, 2, 512>(ANA_ARGS, true);
     else if (c.P3 == 3072 && !no3) rc = launch_ana_blu<3072, 2, 512>(ANA_ARGS, true);

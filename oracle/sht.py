@@ -258,8 +258,8 @@ def ring_analysis(x, nphi, phi0, L):
     return X[m % nphi] * np.exp(-1j * m * phi0)
 
 
-def anal_to_gm(hpmap, nside, lmax, ring_w=None):
-    """Weighted ring spectra (gn, gs) [2 nside][lmax+1] of a RING map."""
+def anal_to_gm(hpmap, nside, lmax, ring_w=None, pairs=None):
+    """Weighted ring spectra (gn, gs) [2 nside][lmax+1] of a RING map (only the rows of ``pairs`` filled when given)."""
     ri = healpix.ring_info(nside)
     nring = 4 * nside - 1
     npair = 2 * nside
@@ -267,7 +267,7 @@ def anal_to_gm(hpmap, nside, lmax, ring_w=None):
     area = 4.0 * np.pi / healpix.nside2npix(nside)
     gn = np.zeros((npair, L), dtype=np.complex128)
     gs = np.zeros((npair, L), dtype=np.complex128)
-    for r in range(npair):
+    for r in range(npair) if pairs is None else pairs:
         wr = area * (1.0 if ring_w is None else ring_w[r])
         n, s, p0 = int(ri["nphi"][r]), int(ri["start"][r]), float(ri["phi0"][r])
         gn[r] = wr * ring_analysis(hpmap[s : s + n], n, p0, L)
@@ -278,16 +278,20 @@ def anal_to_gm(hpmap, nside, lmax, ring_w=None):
     return gn, gs
 
 
-def map2alm_adjoint(hpmap, nside, lmax, ring_w=None):
-    """One quadrature pass: a_lm = sum_pix w_ring(pix) (4 pi / npix) map(pix) conj(Y_lm(pix)), packed order."""
+def map2alm_adjoint(hpmap, nside, lmax, ring_w=None, pairs=None):
+    """One quadrature pass: a_lm = sum_pix w_ring(pix) (4 pi / npix) map(pix) conj(Y_lm(pix)), packed order.
+
+    pairs: north ring indices r < 2 nside (0-based) the sum runs over, each with its south mirror; the map must
+    vanish on every other ring (a map supported on a few rings then costs those rings only)."""
     ri = healpix.ring_info(nside)
     npair = 2 * nside
-    gn, gs = anal_to_gm(np.asarray(hpmap, dtype=np.float64), nside, lmax, ring_w)
+    gn, gs = anal_to_gm(np.asarray(hpmap, dtype=np.float64), nside, lmax, ring_w, pairs)
+    rows = np.arange(npair) if pairs is None else np.asarray(pairs, dtype=np.int64)
     alm = np.zeros((lmax + 1) * (lmax + 2) // 2, dtype=np.complex128)
-    z = np.ascontiguousarray(ri["z"][:npair])
-    sth = np.ascontiguousarray(ri["sth"][:npair])
-    _load().oracle_legendre_anal(lmax, npair, _dp(z), _dp(sth), _dp(np.ascontiguousarray(gn).view(np.float64)),
-                                 _dp(np.ascontiguousarray(gs).view(np.float64)), _dp(alm.view(np.float64)))
+    z = np.ascontiguousarray(ri["z"][rows])
+    sth = np.ascontiguousarray(ri["sth"][rows])
+    _load().oracle_legendre_anal(lmax, len(rows), _dp(z), _dp(sth), _dp(np.ascontiguousarray(gn[rows]).view(np.float64)),
+                                 _dp(np.ascontiguousarray(gs[rows]).view(np.float64)), _dp(alm.view(np.float64)))
     return alm
 
 
@@ -396,8 +400,9 @@ def _wx_from_lambda(lmax, m, z):
     return W, X
 
 
-def map2alm_spin2_adjoint(q, u, nside, lmax, ring_w=None):
-    """One quadrature pass (Q, U) RING maps -> packed (E, B)."""
+def map2alm_spin2_adjoint(q, u, nside, lmax, ring_w=None, ms=None):
+    """One quadrature pass (Q, U) RING maps -> packed (E, B); with ``ms`` only the coefficients of those m are
+    formed (the others stay zero: the m loop is host numpy, minutes at full size)."""
     ri = healpix.ring_info(nside)
     npair = 2 * nside
     nring = 4 * nside - 1
@@ -406,7 +411,7 @@ def map2alm_spin2_adjoint(q, u, nside, lmax, ring_w=None):
     nalm = (lmax + 1) * (lmax + 2) // 2
     e = np.zeros(nalm, dtype=np.complex128)
     b = np.zeros(nalm, dtype=np.complex128)
-    for m in range(lmax + 1):
+    for m in range(lmax + 1) if ms is None else sorted(set(int(x) for x in ms)):
         i0 = alm_index(m, m, lmax)
         for r in range(npair):
             z = float(ri["z"][r])

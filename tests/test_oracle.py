@@ -504,6 +504,37 @@ def test_spin2_analysis_oracle_definition_and_round_trip():
     assert np.abs(e4 + b).max() < 1e-6 and np.abs(b4 - e).max() < 1e-6
 
 
+def test_restricted_analysis_oracles_equal_the_full_ones():
+    """The restrictions the full-size analysis tests use to keep the host oracle short: map2alm_spin2_adjoint(ms=)
+    forms exactly the coefficients of the listed m (the others zero), and map2alm_adjoint(pairs=) of a map that vanishes
+    off those ring pairs equals the full quadrature."""
+    from oracle import sht
+
+    nside, lmax = 8, 20
+    npix = 12 * nside * nside
+    rng = np.random.default_rng(12)
+    w = sht.ring_weights(nside)
+    q, u = rng.standard_normal(npix), rng.standard_normal(npix)
+    e, b = sht.map2alm_spin2_adjoint(q, u, nside, lmax, w)
+    ms = [0, 1, 7, 19, 20]
+    er, br = sht.map2alm_spin2_adjoint(q, u, nside, lmax, w, ms=ms)
+    m_of = np.concatenate([np.full(lmax + 1 - m, m) for m in range(lmax + 1)])
+    sel = np.isin(m_of, ms)
+    assert np.array_equal(er[sel], e[sel]) and np.array_equal(br[sel], b[sel])
+    assert not er[~sel].any() and not br[~sel].any()
+    # a map on the ring pairs 0, 5, 2 nside - 1 (the equator) and the south mirrors of 0 and 5
+    ri = healpix.ring_info(nside)
+    nring = 4 * nside - 1
+    pairs = [0, 5, 2 * nside - 1]
+    x = np.zeros(npix)
+    for r in pairs + [nring - 1, nring - 1 - 5]:
+        s, n = int(ri["start"][r]), int(ri["nphi"][r])
+        x[s : s + n] = rng.standard_normal(n)
+    full = sht.map2alm_adjoint(x, nside, lmax, w)
+    part = sht.map2alm_adjoint(x, nside, lmax, w, pairs=pairs)
+    assert np.abs(part - full).max() <= 1e-15 * np.abs(full).max()
+
+
 @pytest.mark.parametrize("nside,lmax", [(1, 2), (2, 5), (4, 11), (8, 23), (16, 32), (32, 95)])
 def test_c_ring_stage_equals_the_numpy_definition(nside, lmax):
     """oracle_ring_synth (C/OpenMP: the ring stage of the timed CPU baseline) == oracle.sht.ring_synthesis ring by
