@@ -103,6 +103,8 @@ SIGNATURES = {
     "corahip_cube_affine": (c_int, [c_void_p, PTR, PTR, PTR, PTR, PTR, c_int, ctypes.c_int64, PTR]),
     "corahip_raytrace_slices": (c_int, [c_void_p, PTR, c_int, c_int, c_int, PTR, PTR, PTR, PTR, c_double, c_double,
                                         c_int, c_int, c_int, PTR]),
+    "corahip_healpix_neighbours": (c_int, [c_void_p, c_int, PTR]),
+    "corahip_za_density_sph": (c_int, [c_void_p, PTR, PTR, PTR, PTR, c_int, c_int, c_double, c_double, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -929,6 +931,22 @@ class Context:
         _check(self.lib.corahip_raytrace_slices(self.h, self._f64(cube), n0, n1, n2, self._f64(zc), self._f64(scale),
                                                 self._f64(tx), self._f64(ty), float(wx), float(wy), numz, numx, numy,
                                                 self._f64(out)))
+        return out
+
+    def healpix_neighbours(self, nside):
+        """RING neighbour table [npix, 9] int32: the pixel itself, then healpy.get_all_neighbours' 8 (-1: none)."""
+        torch = _torch()
+        out = torch.empty((12 * int(nside) ** 2, 9), dtype=torch.int32, device=self.device)
+        _check(self.lib.corahip_healpix_neighbours(self.h, int(nside), self._p(out)))
+        return out
+
+    def za_density_sph(self, psi, delta_bias, delta_m, chi, out, sigma_ang, sigma_chi):
+        """Zel'dovich SPH assignment into ``out`` [nchi, npix] (added to, then minus 1); shapes checked by the caller."""
+        nchi, npix = delta_bias.shape
+        nside = int(round((npix // 12) ** 0.5))
+        _check(self.lib.corahip_za_density_sph(self.h, self._f64(psi), self._f64(delta_bias), self._f64(delta_m),
+                                               self._f64(chi), int(nchi), nside, float(sigma_ang), float(sigma_chi),
+                                               self._f64(out)))
         return out
 
     def sht_rings(self, nside, lmax):

@@ -1,0 +1,420 @@
+// pmesh.hip - Zel'dovich SPH density assignment (cora/signal/lss.py:1305-1419 za_density_sph with
+// cora/util/pmesh.pyx:29-279 + pmesh_util.c:4-42) and the HEALPix RING neighbour table it needs.
+//
+// Geometry: RING ang2pix / pix2vec / ang2vec and get_all_neighbours restated from the published HEALPix
+// algorithm (Gorski et al. 2005; ring -> (x, y, face), step within or across base faces, back to ring).  The
+// z / phi of a pixel centre and ang2pix repeat, operation for operation, cora_amd/util/hputil.py (pix2ang,
+// ang2pix) so that the host oracle and the kernel pick the same pixels; no contraction into FMAs there.
+//
+// Deposit: one workgroup owns a 16 x 16 block of one base face (RING pixels of those (x, y)) and 8 slices.  Its
+// particles add into an LDS f64 tile of that block with a 4-pixel halo and 3 radial bins of halo on each side
+// (ds_add_f64); a target outside the tile (another face, farther away) goes straight to a global f64 atomic add.  The
+// tile is flushed once with global atomic adds of its non-zero cells.  Sums therefore depend on arrival order: repeated
+// calls agree to rounding, not bit for bit.
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int TB = 16;                 // face block edge (pixels) owned by a workgroup
+constexpr int TH = 4;                  // angular halo of the tile (pixels)
+constexpr int TE = TB + 2 * TH;        // tile edge
+constexpr int TS = 8;                  // slices per workgroup
+constexpr int TRH = 3;                 // radial halo (bins) on each side
+constexpr int TNB = TS + 2 * TRH;      // radial bins of the tile
+constexpr int TCELLS = TNB * TE * TE;  // 8064 doubles = 63 KiB of LDS
+
+// base-face neighbour of face f across the side / corner nbnum (0..8, 4 = same face) and the (x, y) flips that go with
+// it (bit 1: x -> n-1-x, 2: y -> n-1-y, 4: swap), by face row (face >> 2)
+__constant__ int8_t c_nb_face[9][12] = {
+    {8, 9, 10, 11, -1, -1, -1, -1, 10, 11, 8, 9},  // S
+    {5, 6, 7, 4, 8, 9, 10, 11, 9, 10, 11, 8},      // SE
+    {-1, -1, -1, -1, 5, 6, 7, 4, -1, -1, -1, -1},  // E
+    {4, 5, 6, 7, 11, 8, 9, 10, 11, 8, 9, 10},      // SW
+    {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11},        // centre
+    {1, 2, 3, 0, 0, 1, 2, 3, 5, 6, 7, 4},          // NE
+    {-1, -1, -1, -1, 7, 4, 5, 6, -1, -1, -1, -1},  // W
+    {3, 0, 1, 2, 3, 0, 1, 2, 4, 5, 6, 7},          // NW
+    {2, 3, 0, 1, -1, -1, -1, -1, 0, 1, 2, 3}};     // N
+__constant__ int8_t c_nb_swap[9][3] = {{0, 0, 3}, {0, 0, 6}, {0, 0, 0}, {0, 0, 5}, {0, 0, 0},
+                                       {5, 0, 0}, {0, 0, 0}, {6, 0, 0}, {3, 0, 0}};
+// healpy's order of get_all_neighbours: SW, W, NW, N, NE, E, SE, S
+__constant__ int8_t c_nb_dx[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
+__constant__ int8_t c_nb_dy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+
+struct Geom {
+    long nside, npix, ncap;
+};
+
+__device__ inline int face_jrll(int f) { return (f >> 2) + 2; }
+__device__ inline int face_jpll(int f) { return 2 * (f & 3) + ((f >> 2) == 1 ? 0 : 1); }
+
+__device__ inline long isqrt_l(long v) {
+    long r = (long)sqrt((double)v);
+    while (r * r > v) --r;
+    while ((r + 1) * (r + 1) <= v) ++r;
+    return r;
+}
+
+__device__ inline long floordiv_l(long a, long b) {
+    long q = a / b;
+    return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
+}
+__device__ inline long floormod_l(long a, long b) { return a - floordiv_l(a, b) * b; }
+
+// numpy's float remainder (npy_divmod): fmod, moved to the sign of the divisor
+__device__ inline double np_mod(double a, double b) {
+    double m = fmod(a, b);
+    if (m != 0.0) {
+        if ((b < 0.0) != (m < 0.0)) m += b;
+    } else {
+        m = copysign(0.0, b);
+    }
+    return m;
+}
+
+__device__ void ring2xyf(const Geom &g, long pix, int &ix, int &iy, int &face) {
+    const long ns = g.nside, nl2 = 2 * ns;
+    long iring, iphi, kshift, nr;
+    if (pix < g.ncap) {
+        iring = (1 + isqrt_l(1 + 2 * pix)) >> 1;
+        iphi = (pix + 1) - 2 * iring * (iring - 1);
+        kshift = 0;
+        nr = iring;
+        face = (int)((iphi - 1) / nr);
+    } else if (pix < g.npix - g.ncap) {
+        long ip = pix - g.ncap;
+        long tmp = ip / (4 * ns);
+        iring = tmp + ns;
+        iphi = ip - tmp * 4 * ns + 1;
+        kshift = (iring + ns) & 1;
+        nr = ns;
+        long ire = tmp + 1, irm = nl2 + 1 - tmp;
+        long ifm = (iphi - (ire >> 1) + ns - 1) / ns;
+        long ifp = (iphi - (irm >> 1) + ns - 1) / ns;
+        face = (int)((ifp == ifm) ? (ifp | 4) : ((ifp < ifm) ? ifp : (ifm + 8)));
+    } else {
+        long ip = g.npix - pix;
+        iring = (1 + isqrt_l(2 * ip - 1)) >> 1;
+        iphi = 4 * iring + 1 - (ip - 2 * iring * (iring - 1));
+        kshift = 0;
+        nr = iring;
+        iring = 2 * nl2 - iring;
+        face = (int)((iphi - 1) / nr + 8);
+    }
+    long irt = iring - (long)face_jrll(face) * ns + 1;
+    long ipt = 2 * iphi - (long)face_jpll(face) * nr - kshift - 1;
+    if (ipt >= nl2) ipt -= 8 * ns;
+    ix = (int)((ipt - irt) >> 1);
+    iy = (int)((-ipt - irt) >> 1);
+}
+
+__device__ long xyf2ring(const Geom &g, int ix, int iy, int face) {
+    const long ns = g.nside, nl4 = 4 * ns;
+    long jr = (long)face_jrll(face) * ns - ix - iy - 1;
+    long nr, n_before;
+    bool shifted;
+    if (jr < ns) {
+        nr = jr;
+        n_before = 2 * jr * (jr - 1);
+        shifted = true;
+    } else if (jr < 3 * ns) {
+        nr = ns;
+        n_before = g.ncap + (jr - ns) * nl4;
+        shifted = ((jr - ns) & 1) == 0;
+    } else {
+        nr = 4 * ns - jr;
+        n_before = g.npix - 2 * nr * (nr + 1);
+        shifted = true;
+    }
+    long kshift = shifted ? 0 : 1;
+    long jp = ((long)face_jpll(face) * nr + ix - iy + 1 + kshift) / 2;
+    if (jp < 1) jp += nl4;
+    return n_before + jp - 1;
+}
+
+// the 8 neighbours of (ix, iy, face) in healpy's order: (x, y, face) each, face -1 where there is none
+__device__ void neighbours_xyf(const Geom &g, int ix, int iy, int face, int nx[8], int ny[8], int nf[8]) {
+    const int ns = (int)g.nside;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        int x = ix + c_nb_dx[i], y = iy + c_nb_dy[i];
+        int nbnum = 4;
+        if (x < 0) {
+            x += ns;
+            nbnum -= 1;
+        } else if (x >= ns) {
+            x -= ns;
+            nbnum += 1;
+        }
+        if (y < 0) {
+            y += ns;
+            nbnum -= 3;
+        } else if (y >= ns) {
+            y -= ns;
+            nbnum += 3;
+        }
+        int f = c_nb_face[nbnum][face];
+        if (f >= 0) {
+            int bits = c_nb_swap[nbnum][face >> 2];
+            if (bits & 1) x = ns - x - 1;
+            if (bits & 2) y = ns - y - 1;
+            if (bits & 4) {
+                int t = x;
+                x = y;
+                y = t;
+            }
+        }
+        nx[i] = x;
+        ny[i] = y;
+        nf[i] = f;
+    }
+}
+
+// z and phi of a pixel centre: the arithmetic of hputil.pix2ang, in the same order
+__device__ void pix2zphi(const Geom &g, long ipix, double &z, double &phi) {
+#pragma clang fp contract(off)
+    const long ns = g.nside;
+    const double dn = (double)ns;
+    if (ipix < g.ncap || ipix >= g.npix - g.ncap) {
+        const bool south = ipix >= g.ncap;
+        long p = south ? g.npix - 1 - ipix : ipix;
+        long i = (1 + isqrt_l(1 + 2 * p)) >> 1;     // ring (1-based) holding 2 i (i - 1) .. 2 i (i + 1) - 1
+        long j = p - 2 * i * (i - 1);
+        double zc = 1.0 - (double)i * (double)i / (3.0 * dn * dn);
+        double pc = ((double)j + 0.5) * M_PI / (2.0 * (double)i);
+        z = south ? -zc : zc;
+        phi = south ? 2.0 * M_PI - pc : pc;
+    } else {
+        long pb = ipix - g.ncap;
+        long i = pb / (4 * ns) + ns;
+        long j = pb % (4 * ns);
+        long s = (i - ns + 1) & 1;
+        z = 4.0 / 3.0 - 2.0 * (double)i / (3.0 * dn);
+        phi = ((double)j + 0.5 * (double)s) * M_PI / (2.0 * dn);
+    }
+}
+
+// healpy.pix2vec: (sin theta cos phi, sin theta sin phi, z) with sin theta = sqrt((1 - z)(1 + z))
+__device__ void pix2vec(const Geom &g, long ipix, double v[3]) {
+#pragma clang fp contract(off)
+    double z, phi;
+    pix2zphi(g, ipix, z, phi);
+    double st = sqrt((1.0 - z) * (1.0 + z));
+    double s, c;
+    sincos(phi, &s, &c);
+    v[0] = st * c;
+    v[1] = st * s;
+    v[2] = z;
+}
+
+// RING ang2pix: the arithmetic of hputil.ang2pix, in the same order
+__device__ long ang2pix(const Geom &g, double theta, double phi) {
+#pragma clang fp contract(off)
+    const long ns = g.nside;
+    const double dn = (double)ns;
+    double z = cos(theta);
+    double za = fabs(z);
+    double tt = np_mod(phi, 2.0 * M_PI) / (M_PI / 2.0);
+    if (za <= 2.0 / 3.0) {
+        double t1 = dn * (0.5 + tt);
+        double t2 = dn * z * 0.75;
+        long jp = (long)floor(t1 - t2);
+        long jm = (long)floor(t1 + t2);
+        long ir = ns + 1 + jp - jm;
+        long kshift = 1 - (ir & 1);
+        long ip = floormod_l(floordiv_l(jp + jm - ns + kshift + 1, 2), 4 * ns);
+        return g.ncap + (ir - 1) * 4 * ns + ip;
+    }
+    double tp = tt - floor(tt);
+    double tmp = dn * sqrt(3.0 * (1.0 - za));
+    long jp = (long)floor(tp * tmp);
+    long jm = (long)floor((1.0 - tp) * tmp);
+    long irc = jp + jm + 1;
+    long ipc = floormod_l((long)floor(tt * (double)irc), 4 * irc);
+    return z > 0 ? 2 * irc * (irc - 1) + ipc : g.npix - 2 * irc * (irc + 1) + ipc;
+}
+
+__global__ __launch_bounds__(256) void neighbours_kernel(Geom g, int32_t *__restrict__ out) {
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < g.npix; p += (long)gridDim.x * blockDim.x) {
+        int ix, iy, f;
+        ring2xyf(g, p, ix, iy, f);
+        int nx[8], ny[8], nf[8];
+        neighbours_xyf(g, ix, iy, f, nx, ny, nf);
+        int32_t *o = out + p * 9;
+        o[0] = (int32_t)p;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[1 + k] = nf[k] >= 0 ? (int32_t)xyf2ring(g, nx[k], ny[k], nf[k]) : -1;
+    }
+}
+
+// grid: x = face block (nbf^2 per face), y = base face, z = group of TS slices
+__global__ __launch_bounds__(256) void za_sph_kernel(Geom g, const double *__restrict__ psi,
+                                                     const double *__restrict__ delta_b,
+                                                     const double *__restrict__ delta_m,
+                                                     const double *__restrict__ chi, int nchi, double sigma_ang,
+                                                     double sigma_chi, double *__restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double acc[TCELLS];
+    const int nbf = (int)((g.nside + TB - 1) / TB);
+    const int face = blockIdx.y;
+    const int x0 = (int)(blockIdx.x % nbf) * TB, y0 = (int)(blockIdx.x / nbf) * TB;
+    const int s0 = blockIdx.z * TS;
+    const int b0 = s0 - TRH;
+    const int tx0 = x0 - TH, ty0 = y0 - TH;
+    const long npix = g.npix;
+    const long plane = (long)nchi * npix;
+
+    for (int c = threadIdx.x; c < TCELLS; c += blockDim.x) acc[c] = 0.0;
+    __syncthreads();
+
+    const int x = x0 + (int)(threadIdx.x % TB), y = y0 + (int)(threadIdx.x / TB);
+    if (x < g.nside && y < g.nside) {
+        const long p = xyf2ring(g, x, y, face);
+        double zp, php;
+        pix2zphi(g, p, zp, php);
+        const double thp = acos(zp);
+        const int s1 = min(s0 + TS, nchi);
+        for (int ii = s0; ii < s1; ++ii) {
+            const long e = (long)ii * npix + p;                    // 64-bit particle index
+            const double rho = 1.0 + delta_b[e];
+            const double dr = psi[e], dth = psi[plane + e], dph = psi[2 * plane + e];
+            double sc = fmin(fmax(1.0 + delta_m[e], 0.1), 3.0);
+            sc = pow(sc, -1.0 / 3.0);
+
+            // pmesh.calculate_positions
+            double th = thp + dth, ph = php + dph;
+            if (th > M_PI || th < 0.0) {
+                th = M_PI - np_mod(th, M_PI);
+                ph = ph + M_PI;
+            }
+            ph = np_mod(ph, 2.0 * M_PI);
+            const double nchi_pos = chi[ii] + dr;
+
+            // angular weights over the pixel of the new position and its 8 neighbours (pmesh._pixel_weights).
+            // sin^2 of the angle as |v x w|^2, not 1 - (v.w)^2: equal for unit vectors, without the cancellation
+            const long q = ang2pix(g, th, ph);
+            double st, ct, sp, cp;
+            sincos(th, &st, &ct);
+            sincos(ph, &sp, &cp);
+            const double w0 = st * cp, w1 = st * sp, w2 = ct;
+            int cx[9], cy[9], cf[9];
+            ring2xyf(g, q, cx[0], cy[0], cf[0]);
+            neighbours_xyf(g, cx[0], cy[0], cf[0], cx + 1, cy + 1, cf + 1);
+            const double sa = sc * sigma_ang;
+            const double inv_sa2 = 1.0 / (sa * sa);
+            long cpix[9];
+            double pw[9], wsum = 0.0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                if (cf[k] >= 0) {
+                    cpix[k] = k == 0 ? q : xyf2ring(g, cx[k], cy[k], cf[k]);
+                    double v[3];
+                    pix2vec(g, cpix[k], v);
+                    const double c0 = v[1] * w2 - v[2] * w1, c1 = v[2] * w0 - v[0] * w2, c2 = v[0] * w1 - v[1] * w0;
+                    const double d2 = c0 * c0 + c1 * c1 + c2 * c2;
+                    pw[k] = exp(-0.5 * d2 * inv_sa2);
+                } else {
+                    cpix[k] = 0;
+                    pw[k] = 0.0;
+                }
+                wsum += pw[k];
+            }
+
+            // radial weights over 3 bins (pmesh._radial_weights, nnh = 1); ind = searchsorted(chi, new_chi, 'left')
+            int lo = 0, hi = nchi;
+            while (lo < hi) {
+                int mid = (lo + hi) >> 1;
+                if (chi[mid] < nchi_pos) lo = mid + 1;
+                else hi = mid;
+            }
+            const int low = min(max(0, lo - 1), nchi - 3);
+            const double sr = sc * sigma_chi;
+            const double inv_sr2 = 1.0 / (sr * sr);
+            double rw[3], rsum = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double dc = chi[low + j] - nchi_pos;
+                rw[j] = exp(-0.5 * (dc * dc) * inv_sr2);
+                rsum += rw[j];
+            }
+
+            // deposit rho w_pix w_bin: into the tile when the voxel is in it, else straight to out
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                if (cf[k] < 0) continue;
+                const double v = rho * (pw[k] / wsum);
+                const int lx = cx[k] - tx0, ly = cy[k] - ty0;
+                const bool in_xy = cf[k] == face && (unsigned)lx < (unsigned)TE && (unsigned)ly < (unsigned)TE;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    const double d = v * (rw[j] / rsum);
+                    const int b = low + j;
+                    const int lb = b - b0;
+                    if (in_xy && (unsigned)lb < (unsigned)TNB)
+                        atomicAdd(&acc[(lb * TE + ly) * TE + lx], d);
+                    else
+                        atomicAdd(&out[(long)b * npix + cpix[k]], d);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // flush the tile: one global add per non-zero cell (cells off the face or outside [0, nchi) never receive one)
+    for (int c = threadIdx.x; c < TCELLS; c += blockDim.x) {
+        const double v = acc[c];
+        if (v == 0.0) continue;
+        const int lb = c / (TE * TE), r = c % (TE * TE);
+        const int gx = tx0 + r % TE, gy = ty0 + r / TE, b = b0 + lb;
+        if (b < 0 || b >= nchi || gx < 0 || gy < 0 || gx >= g.nside || gy >= g.nside) continue;
+        atomicAdd(&out[(long)b * npix + xyf2ring(g, gx, gy, face)], v);
+    }
+}
+
+__global__ __launch_bounds__(256) void minus_one_kernel(double *__restrict__ out, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] -= 1.0;
+}
+
+Geom make_geom(int nside) {
+    Geom g;
+    g.nside = nside;
+    g.npix = 12L * nside * nside;
+    g.ncap = 2L * nside * (nside - 1);
+    return g;
+}
+
+}  // namespace
+
+int corahip_healpix_neighbours(corahip_ctx *ctx, int nside, int32_t *out) {
+    ARG_CHECK(ctx && out && nside >= 1 && nside <= 8192);
+    StageTimer st(ctx, "healpix_neighbours");
+    const Geom g = make_geom(nside);
+    long blocks = (g.npix + 255) / 256;
+    const long cap = (long)ctx->num_cu * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(neighbours_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, g, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_za_density_sph(corahip_ctx *ctx, const double *psi, const double *delta_bias, const double *delta_m,
+                           const double *chi, int nchi, int nside, double sigma_ang, double sigma_chi, double *out) {
+    ARG_CHECK(ctx && psi && delta_bias && delta_m && chi && out);
+    ARG_CHECK(nchi >= 3 && nside >= 1 && nside <= 8192 && (nchi + TS - 1) / TS <= 65535);
+    ARG_CHECK(sigma_ang > 0.0 && sigma_chi > 0.0);
+    StageTimer st(ctx, "za_density_sph");
+    const Geom g = make_geom(nside);
+    const long nbf = (nside + TB - 1) / TB;
+    hipLaunchKernelGGL(za_sph_kernel, dim3((unsigned)(nbf * nbf), 12u, (unsigned)((nchi + TS - 1) / TS)), dim3(256), 0,
+                       ctx->stream, g, psi, delta_bias, delta_m, chi, nchi, sigma_ang, sigma_chi, out);
+    LAUNCH_CHECK();
+    const long n = (long)nchi * g.npix;
+    long blocks = (n + 255) / 256;
+    const long cap = (long)ctx->num_cu * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(minus_one_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, out, n);
+    LAUNCH_CHECK();
+    return 0;
+}

@@ -53,6 +53,12 @@ def ang2pix(nside, theta, phi, lonlat=False):
 def pix2ang(nside, ipix):
     """(theta, phi) of RING pixel centres (what the reference takes from ``healpy.pix2ang``): caps
     z = 1 - i^2/(3 nside^2), phi = (j + 1/2) pi/(2 i); belt z = 4/3 - 2 i/(3 nside), phi = (j + s/2) pi/(2 nside)."""
+    z, phi = _pix2zphi(nside, ipix)
+    return np.arccos(z), phi
+
+
+def _pix2zphi(nside, ipix):
+    """(z, phi) of RING pixel centres; csrc/pmesh.hip repeats this arithmetic operation for operation."""
     nside = int(nside)
     ipix = np.asarray(ipix, dtype=np.int64)
     npix = 12 * nside * nside
@@ -78,7 +84,42 @@ def pix2ang(nside, ipix):
     z = np.where(in_n, z_cap, np.where(in_s, -z_cap, z_b))
     # a mirrored south-cap pixel runs backwards in phi on its ring
     phi = np.where(in_n, phi_cap, np.where(in_s, 2.0 * np.pi - phi_cap, phi_b))
-    return np.arccos(z), phi
+    return z, phi
+
+
+def pix2vec(nside, ipix):
+    """Unit vectors (x, y, z) of RING pixel centres, as ``healpy.pix2vec``: sin(theta) = sqrt((1 - z)(1 + z))."""
+    z, phi = _pix2zphi(nside, ipix)
+    st = np.sqrt((1.0 - z) * (1.0 + z))
+    return st * np.cos(phi), st * np.sin(phi), z
+
+
+def ang2vec(theta, phi):
+    """Unit vectors [..., 3] of directions (colatitude, longitude in radians), as ``healpy.ang2vec``."""
+    theta = np.asarray(theta, dtype=np.float64)
+    phi = np.asarray(phi, dtype=np.float64)
+    st = np.sin(theta)
+    return np.stack([st * np.cos(phi), st * np.sin(phi), np.cos(theta)], axis=-1)
+
+
+def nside2resol(nside):
+    """Approximate pixel size in radians, sqrt(4 pi / npix) (``healpy.nside2resol``)."""
+    return np.sqrt(4.0 * np.pi / nside2npix(nside))
+
+
+def get_all_neighbours(nside, ipix):
+    """The 8 RING neighbours of each pixel of ``ipix`` as ``healpy.get_all_neighbours(nside, ipix)`` gives them:
+    [8, n] (or [8] for a scalar) in the order SW, W, NW, N, NE, E, SE, S, -1 where a pixel has none.  The table comes
+    from the device (corahip_healpix_neighbours)."""
+    ipix = np.asarray(ipix, dtype=np.int64)
+    npix = nside2npix(nside)
+    if ipix.size and (ipix.min() < 0 or ipix.max() >= npix):
+        raise ValueError("pixel index out of range for nside %d" % int(nside))
+    ctx = _lib.get_context()
+    table = ctx.healpix_neighbours(int(nside))
+    rows = ctx.to_device(ipix.reshape(-1), dtype=np.int64)
+    nb = table[rows, 1:].cpu().numpy()
+    return nb.T.astype(np.int64).reshape((8,) + ipix.shape)
 
 
 def ang_positions(nside):

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 4      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run */
+#define CORAHIP_ABI_MINOR 5      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -480,6 +480,22 @@ int corahip_cube_affine(corahip_ctx *ctx, const double *df, const double *vf, co
 int corahip_raytrace_slices(corahip_ctx *ctx, const double *cube, int n0, int n1, int n2, const double *zc,
                             const double *scale, const double *tx, const double *ty, double wx, double wy,
                             int numz, int numx, int numy, double *out);
+
+/* ---- large-scale structure: Zel'dovich SPH density assignment -------------------------------
+ * healpix_neighbours: out [npix, 9] int32 (npix = 12 nside^2, RING): entry 0 the pixel itself, 1..8 its
+ *            neighbours in healpy.get_all_neighbours order (SW, W, NW, N, NE, E, SE, S), -1 where none exists
+ *            (the nn_ind table of cora/signal/lss.py:1353-1355).  1 <= nside <= 8192.
+ * za_density_sph: cora/signal/lss.py:1305-1419 (pmesh.pyx:29-279, pmesh_util.c:4-42): every voxel (ii, p) of
+ *            delta_bias [nchi, npix] is a particle of mass 1 + delta_bias moved by psi [3, nchi, npix] (radial,
+ *            theta, phi) from (chi[ii], centre of p); its mass is spread over the 9 pixels around its new
+ *            direction x 3 radial bins with Gaussian weights of width sigma_ang (pixels) and sigma_chi (bins)
+ *            x clip(1 + delta_m, 0.1, 3)^(-1/3); out [nchi, npix] is ADDED to, then 1 is subtracted from every
+ *            element.  Bin ri goes to out[ri, pix] (the reference's C scatter uses a row stride of 9 instead
+ *            of npix).  chi ascending, nchi >= 3 (else CORAHIP_EINVAL).  Float atomics: repeated
+ *            calls agree to rounding, not bit for bit.                                                    */
+int corahip_healpix_neighbours(corahip_ctx *ctx, int nside, int32_t *out);
+int corahip_za_density_sph(corahip_ctx *ctx, const double *psi, const double *delta_bias, const double *delta_m,
+                           const double *chi, int nchi, int nside, double sigma_ang, double sigma_chi, double *out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
