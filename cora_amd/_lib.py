@@ -105,6 +105,9 @@ SIGNATURES = {
                                         c_int, c_int, c_int, PTR]),
     "corahip_healpix_neighbours": (c_int, [c_void_p, c_int, PTR]),
     "corahip_za_density_sph": (c_int, [c_void_p, PTR, PTR, PTR, PTR, c_int, c_int, c_double, c_double, PTR]),
+    "corahip_der1_alm_prep": (c_int, [c_void_p, c_void_p, PTR, c_int, c_int, c_int, PTR]),
+    "corahip_der1_combine": (c_int, [c_void_p, c_void_p, PTR, c_int, c_int, PTR, PTR, c_int, PTR, PTR]),
+    "corahip_radial_gradient": (c_int, [c_void_p, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -817,6 +820,132 @@ class Context:
             out = self.empty((nalm, gout, 2, 4))
         assert tuple(out.shape) == (nalm, gout, 2, 4), out.shape
         _check(self.lib.corahip_spin2_combine(self.h, plan, self._f64(a6), a6.shape[1], nf, self._f64(out), gout))
+        return out
+
+    # -- derivative synthesis (composition around the scalar synthesis, csrc/sht_der1.hip) --------------
+    def der1_alm_prep(self, alm, nside, lmax, g0=0, g_in=None, out=None):
+        """Channel groups g0 .. g0 + g_in - 1 of alm_dev [nalm, G, 2, 4] -> alm3_dev [nalm, 3 g_in, 2, 4], group blocks
+        [l a | c_{l+1,m} a_{l+1,m} | i m a] (corahip_der1_alm_prep)."""
+        plan = self.sht_plan(nside, lmax)
+        nalm = (lmax + 1) * (lmax + 2) // 2
+        G = int(alm.shape[1])
+        g_in = G - g0 if g_in is None else int(g_in)
+        assert tuple(alm.shape) == (nalm, G, 2, 4), alm.shape
+        a3 = out if out is not None else self.empty((nalm, 3 * g_in, 2, 4))
+        assert tuple(a3.shape) == (nalm, 3 * g_in, 2, 4), a3.shape
+        _check(self.lib.corahip_der1_alm_prep(self.h, plan, self._f64(alm), G, int(g0), g_in, self._f64(a3)))
+        return a3
+
+    def der1_combine(self, maps3, nside, lmax, g_in, nfields, out_theta, out_phi, scale_theta=None, scale_phi=None,
+                     phi_extra=0):
+        """maps3 [12 g_in, npix] (the synthesis of alm3_dev) -> out_theta, out_phi [nfields, npix]
+        (corahip_der1_combine); scale_theta / scale_phi: device [nfields] per-field factors or None."""
+        plan = self.sht_plan(nside, lmax)
+        npix = 12 * nside * nside
+        assert tuple(maps3.shape) == (12 * g_in, npix), maps3.shape
+        assert tuple(out_theta.shape) == (nfields, npix) and tuple(out_phi.shape) == (nfields, npix)
+        for s in (scale_theta, scale_phi):
+            assert s is None or s.numel() == nfields
+        _check(self.lib.corahip_der1_combine(self.h, plan, self._f64(maps3), int(g_in), int(nfields),
+                                             None if scale_theta is None else self._f64(scale_theta),
+                                             None if scale_phi is None else self._f64(scale_phi), int(phi_extra),
+                                             self._f64(out_theta), self._f64(out_phi)))
+        return out_theta, out_phi
+
+    def alm2map_der1_bytes(self, nside, lmax, nfields=16):
+        """Device bytes :meth:`alm2map_der1` takes for a chunk of ``nfields`` fields: alm3 (3 coefficient sets) + the
+        three synthesised maps per field + the synthesis workspace of 3 x 4 ceil(nfields / 4) channels."""
+        g = (int(nfields) + 3) // 4
+        nalm = (lmax + 1) * (lmax + 2) // 2
+        ws = self.alm2map_workspace_bytes(self.sht_plan(nside, lmax), 12 * g)
+        return nalm * 3 * g * 64 + 12 * g * 12 * nside * nside * 8 + ws
+
+    def alm2map_der1(self, alm, nside, lmax, nnu, scale_theta=None, scale_phi=None, phi_extra=0, out=None,
+                     max_bytes=None):
+        """healpy.alm2map_der1 without its first row: alm_dev [nalm, G, 2, 4] of ``nnu`` fields ->
+        ``(dT/dtheta, (1/sin theta) dT/dphi)``, two device tensors [nnu, npix] (``out``: the pair to write, e.g. two
+        rows of a displacement field).  T itself is :meth:`alm2map`.
+
+        ``scale_theta`` / ``scale_phi``: device [nnu] factors multiplied into the components of each field;
+        ``phi_extra=1`` divides the phi component by sin theta once more.  Both are applied by the combining kernel.
+
+        The fields go through prep -> alm2map over 3 x 4 channels per group of four fields -> combine in chunks of
+        whole groups whose temporaries (:meth:`alm2map_der1_bytes`) stay within ``max_bytes``; default: what 16 fields
+        need at this nside and lmax (12.9e9 bytes at nside 1024, lmax 2048).  A chunk is never smaller than one
+        group.  The result does not depend on the chunking beyond the rounding of the synthesis."""
+        npix = 12 * nside * nside
+        G = int(alm.shape[1])
+        assert 1 <= nnu <= 4 * G
+        if out is None:
+            out = (self.empty((nnu, npix)), self.empty((nnu, npix)))
+        ot, op = out
+        assert tuple(ot.shape) == (nnu, npix) and tuple(op.shape) == (nnu, npix)
+        budget = self.alm2map_der1_bytes(nside, lmax, 16) if max_bytes is None else int(max_bytes)
+        gall = (nnu + 3) // 4
+        gc = gall
+        while gc > 1 and self.alm2map_der1_bytes(nside, lmax, 4 * gc) > budget:
+            gc -= 1
+        plan = self.sht_plan(nside, lmax)
+        for g0 in range(0, gall, gc):
+            g = min(gc, gall - g0)
+            f0, nf = 4 * g0, min(4 * g, nnu - 4 * g0)
+            a3 = self.der1_alm_prep(alm, nside, lmax, g0, g)
+            maps3 = self.empty((12 * g, npix))
+            need = self.alm2map_workspace_bytes(plan, 12 * g)
+            ws = self.workspace(need)
+            _check(self.lib.corahip_alm2map(self.h, plan, self._f64(a3), 12 * g, self._f64(maps3), self._p(ws), need))
+            del a3
+            self.der1_combine(maps3, nside, lmax, g, nf, ot[f0:f0 + nf], op[f0:f0 + nf],
+                              None if scale_theta is None else scale_theta[f0:f0 + nf],
+                              None if scale_phi is None else scale_phi[f0:f0 + nf], phi_extra)
+            del maps3
+        return ot, op
+
+    @staticmethod
+    def gradient_coefficients(x):
+        """Host table [n, 3] of numpy.gradient's coefficients (a, b, c) for coordinates ``x`` (edge_order 1):
+        interior ``a = -hd / (hs (hd + hs))``, ``b = (hd - hs) / (hd hs)``, ``c = hs / (hd (hd + hs))`` with
+        ``hd = x[i+1] - x[i]``, ``hs = x[i] - x[i-1]``; first row (0, -1/h, 1/h), last row (-1/h, 1/h, 0)."""
+        x = np.asarray(x, dtype=np.float64)
+        n = x.size
+        if x.ndim != 1 or n < 2:
+            raise ValueError("gradient needs at least 2 coordinates along the axis (got shape %r)" % (x.shape,))
+        d = np.diff(x)
+        coef = np.zeros((n, 3))
+        hs, hd = d[:-1], d[1:]
+        coef[1:-1, 0] = -hd / (hs * (hd + hs))
+        coef[1:-1, 1] = (hd - hs) / (hd * hs)
+        coef[1:-1, 2] = hs / (hd * (hd + hs))
+        coef[0, 1], coef[0, 2] = -1.0 / d[0], 1.0 / d[0]
+        coef[-1, 0], coef[-1, 1] = -1.0 / d[-1], 1.0 / d[-1]
+        return coef
+
+    def radial_gradient(self, f, x, scale=None, out=None):
+        """``numpy.gradient(f, x, axis=0) * scale[:, None]`` of a device array f [n, npix] (n >= 2) for host
+        coordinates ``x`` [n] (any spacing, ascending or descending); ``scale``: host or device [n] or None.
+        ``out`` must not share memory with ``f`` (ValueError)."""
+        torch = _torch()
+        if f.dim() != 2:
+            raise ValueError("radial_gradient takes a [n, npix] array (got %r)" % (tuple(f.shape),))
+        n, npix = f.shape
+        coef = self.gradient_coefficients(x)
+        if coef.shape[0] != n:
+            raise ValueError("x has %d entries, f %d rows" % (coef.shape[0], n))
+        if out is None:
+            out = self.empty((n, npix))
+        if tuple(out.shape) != (n, npix):
+            raise ValueError("out has shape %r, expected %r" % (tuple(out.shape), (n, npix)))
+        nbytes = n * npix * 8
+        if out.data_ptr() < f.data_ptr() + nbytes and f.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError("radial_gradient: out overlaps f")
+        if scale is not None and not isinstance(scale, torch.Tensor):
+            scale = self.to_device(np.asarray(scale, dtype=np.float64))
+        if scale is not None and scale.numel() != n:
+            raise ValueError("scale has %d entries, f %d rows" % (scale.numel(), n))
+        cdev = self.to_device(coef)
+        _check(self.lib.corahip_radial_gradient(self.h, self._f64(f), self._f64(cdev),
+                                                None if scale is None else self._f64(scale), int(n), int(npix),
+                                                self._f64(out)))
         return out
 
     # -- n3: xi(r) -> C_l --------------------------------------------------------------

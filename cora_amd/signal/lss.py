@@ -2,6 +2,11 @@
 SPH mass assignment behind ``ZeldovichDynamics(sph=True)``.  One fused HIP kernel (csrc/pmesh.hip) moves every
 HEALPix voxel as a particle and spreads its mass over 9 pixels x 3 radial bins.
 
+``zeldovich_displacement`` makes the displacement field that kernel takes from the potential (lss.py:806-828:
+iterated analysis, derivative synthesis and radial gradient, csrc/sht_der1.hip), and ``zeldovich_density`` is the
+numerical content of ``ZeldovichDynamics.process(sph=True)`` (lss.py:777-856) from ``phi, delta`` to the final
+density without leaving the device.
+
 The reference's scatter (pmesh_util.c:37, called from pmesh.pyx:_bin_delta) indexes ``out`` with a row stride of 9
 (the number of pixel weights) instead of the map's npix, so mass meant for radial bin ``ri`` lands ri (npix - 9)
 elements early.  This port implements the intended ``out[ri, pix]`` (tests/test_lss_host.py).
@@ -10,16 +15,9 @@ import numpy as np
 
 from .. import _lib
 from ..util import hputil
+from . import lssutil
 
-
-def _assert_shape(arr, shape, name):
-    """lssutil.assert_shape (cora/signal/lssutil.py:630-640)."""
-    if len(arr.shape) != len(shape):
-        raise ValueError(
-            f"Array {name} has wrong number of dimensions (got {len(arr.shape)}, expected {len(shape)}"
-        )
-    if tuple(arr.shape) != tuple(shape):
-        raise ValueError(f"Array {name} has the wrong shape (got {tuple(arr.shape)}, expected {tuple(shape)}")
+_assert_shape = lssutil.assert_shape
 
 
 def _check(psi, delta_bias, delta_m, chi, out):
@@ -95,3 +93,89 @@ def za_density_sph(psi, delta_bias, delta_m, chi, out, sigma_chi=None):
     res = ctx.za_density_sph(*dev, sigma_ang, sigma_chi)
     out[...] = res.cpu().numpy()
     return out
+
+
+# ------------------------------------------------------------------------------------
+# the displacement field and the whole Zel'dovich step (cora/signal/lss.py:777-856)
+# ------------------------------------------------------------------------------------
+def _host(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def _check_displacement(phi, chi, D, f, nmin):
+    nchi, nside = lssutil.check_maps(phi, chi, name="phi", xname="chi", nmin=nmin)
+    _assert_shape(D, (nchi,), "D")
+    if f is not None:
+        _assert_shape(f, (nchi,), "f")
+    return nchi, nside
+
+
+def zeldovich_displacement_device(phi, chi, D, f=None, lmax=None, niter=3, out=None):
+    """The Zel'dovich displacement field of cora/signal/lss.py:806-828 on device tensors.
+
+    ``psi[0] = np.gradient(phi, chi, axis=0) * D * (1 + f)`` (no ``(1 + f)`` when ``f is None``, the reference's
+    ``redshift_space=False``), ``psi[1] = D / chi * dphi/dtheta``, ``psi[2] = D / chi * (1/sin theta) dphi/dphi /
+    sin theta``: the displacement in comoving distance, theta and phi that :func:`za_density_sph_device` takes.
+
+    ``phi`` [nchi, npix] is a float64 device tensor (nchi >= 2); ``chi``, ``D`` (growth factor ratio) and ``f`` (growth
+    rate) are [nchi] host or device arrays supplied by the caller.  ``lmax`` defaults to ``3 nside - 1``, ``niter``
+    to healpy's 3 (see :func:`cora_amd.signal.lssutil.gradient`).  All three components are written by the kernels
+    of csrc/sht_der1.hip with the factors fused; temporaries stay below
+    ``lssutil.gradient_bytes(nside, lmax)`` (13.4e9 bytes at nside 1024, lmax 2048).  Returns ``psi``
+    [3, nchi, npix] (``out`` if given)."""
+    chi_h, D_h = _host(chi), _host(D)
+    f_h = None if f is None else _host(f)
+    _check_displacement(phi, chi_h, D_h, f_h, 2)
+    D_h = np.asarray(D_h, dtype=np.float64)
+    scale_r = D_h if f_h is None else D_h * (1.0 + np.asarray(f_h, dtype=np.float64))
+    return lssutil.gradient_device(phi, np.asarray(chi_h, dtype=np.float64), grad0=True, out=out, lmax=lmax,
+                                   niter=niter, scale_r=scale_r, scale_ang=D_h, phi_extra=1)
+
+
+def zeldovich_displacement(phi, chi, D, f=None, lmax=None, niter=3):
+    """:func:`zeldovich_displacement_device` for numpy arrays: ``phi`` [nchi, npix] -> ``psi`` [3, nchi, npix]."""
+    phi, chi, D = np.asarray(phi), np.asarray(chi), np.asarray(D)
+    f = None if f is None else np.asarray(f)
+    _check_displacement(phi, chi, D, f, 2)
+    ctx = _lib.get_context()
+    return ctx.to_host(zeldovich_displacement_device(ctx.to_device(phi), chi, D, f, lmax=lmax, niter=niter))
+
+
+def _check_density(phi, delta, delta_bias, chi, D, f):
+    nchi, nside = _check_displacement(phi, chi, D, f, 3)
+    _assert_shape(delta, tuple(phi.shape), "delta")
+    _assert_shape(delta_bias, tuple(phi.shape), "delta_bias")
+    return nchi, nside
+
+
+def zeldovich_density_device(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lmax=None, niter=3):
+    """The numerical content of ``ZeldovichDynamics.process(sph=True)`` (cora/signal/lss.py:777-856) on device tensors:
+    ``psi = zeldovich_displacement_device(phi, chi, D, f)``, ``delta_m = delta * D[:, None]``, ``out = 0``, then
+    ``za_density_sph_device(psi, delta_bias, delta_m, chi, out, sigma_chi)``.  ``phi``, ``delta`` (the matter
+    density at the initial time) and ``delta_bias`` (the biased Lagrangian field) are [nchi, npix], nchi >= 3, ``chi``
+    ascending.  Returns the final density contrast [nchi, npix].  Device memory beyond the three inputs: ``psi``,
+    ``delta_m`` and the result (5 nchi npix doubles) plus ``lssutil.gradient_bytes(nside, lmax)``."""
+    import torch
+
+    chi_h, D_h = _host(chi), _host(D)
+    f_h = None if f is None else _host(f)
+    _check_density(phi, delta, delta_bias, chi_h, D_h, f_h)
+    ctx = _lib.get_context()
+    psi = zeldovich_displacement_device(phi, chi_h, D_h, f_h, lmax=lmax, niter=niter)
+    D_dev = ctx.to_device(np.asarray(D_h, dtype=np.float64))
+    delta_m = delta * D_dev[:, None]
+    out = torch.zeros_like(delta_bias)
+    chi_dev = chi if isinstance(chi, torch.Tensor) else ctx.to_device(np.asarray(chi_h, dtype=np.float64))
+    return za_density_sph_device(psi, delta_bias, delta_m, chi_dev, out, sigma_chi)
+
+
+def zeldovich_density(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lmax=None, niter=3):
+    """:func:`zeldovich_density_device` for numpy arrays; returns the final density contrast [nchi, npix]."""
+    phi, delta, delta_bias = np.asarray(phi), np.asarray(delta), np.asarray(delta_bias)
+    chi, D = np.asarray(chi), np.asarray(D)
+    f = None if f is None else np.asarray(f)
+    _check_density(phi, delta, delta_bias, chi, D, f)
+    ctx = _lib.get_context()
+    res = zeldovich_density_device(ctx.to_device(phi), ctx.to_device(delta), ctx.to_device(delta_bias), chi, D, f,
+                                   sigma_chi=sigma_chi, lmax=lmax, niter=niter)
+    return ctx.to_host(res)

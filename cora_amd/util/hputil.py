@@ -480,3 +480,35 @@ def sph_ps(map1, map2=None, lmax=None):
     prod = alm1 * alm2.conj()
     s = prod[:, 0] + 2 * prod[:, 1:].sum(axis=1).real
     return s / (2.0 * np.arange(lmax + 1) + 1.0)
+
+
+# ------------------------------------------------------------------------------------
+# derivative synthesis: healpy.alm2map_der1 (cora/signal/lssutil.py:225-261)
+# ------------------------------------------------------------------------------------
+def alm2map_der1_device(alm_dev, nside, lmax, nnu, **scales):
+    """alm_dev [nalm, G, 2, 4] of ``nnu`` fields -> device ``(dT/dtheta, (1/sin theta) dT/dphi)``, [nnu, npix] each:
+    rows 1 and 2 of ``healpy.alm2map_der1`` for all fields at once (``Context.alm2map_der1``; keywords
+    ``scale_theta``, ``scale_phi``, ``phi_extra``, ``out``, ``max_bytes`` are passed through)."""
+    return _lib.get_context().alm2map_der1(alm_dev, int(nside), int(lmax), int(nnu), **scales)
+
+
+def alm2map_der1(alm, nside):
+    """``healpy.alm2map_der1(alm, nside)`` for one packed complex ``alm`` (lmax from its length): host
+    ``ndarray[3, npix]`` = ``[T, dT/dtheta, (1/sin theta) dT/dphi]``, RING order.  The derivatives are composed from
+    three scalar syntheses per field (csrc/sht_der1.hip)."""
+    import torch
+
+    alm = np.ascontiguousarray(alm, dtype=np.complex128)
+    if alm.ndim != 1:
+        raise ValueError("alm2map_der1 takes one packed alm array (got shape %r)" % (alm.shape,))
+    lmax = int(round((-3 + np.sqrt(1 + 8 * alm.size)) / 2))
+    if (lmax + 1) * (lmax + 2) // 2 != alm.size:
+        raise ValueError("alm has %d entries, not (lmax + 1)(lmax + 2) / 2 for any lmax" % alm.size)
+    nside = int(nside)
+    ctx = _lib.get_context()
+    dev = ctx.alm_packed_to_dev(torch.from_numpy(alm[None]).to(ctx.device), lmax)
+    out = np.empty((3, nside2npix(nside)))
+    out[0] = ctx.alm2map(dev, nside, lmax, 1)[0].cpu().numpy()
+    dth, dph = ctx.alm2map_der1(dev, nside, lmax, 1)
+    out[1], out[2] = dth[0].cpu().numpy(), dph[0].cpu().numpy()
+    return out

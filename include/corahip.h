@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 5      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph */
+#define CORAHIP_ABI_MINOR 6      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -496,6 +496,31 @@ int corahip_raytrace_slices(corahip_ctx *ctx, const double *cube, int n0, int n1
 int corahip_healpix_neighbours(corahip_ctx *ctx, int nside, int32_t *out);
 int corahip_za_density_sph(corahip_ctx *ctx, const double *psi, const double *delta_bias, const double *delta_m,
                            const double *chi, int nchi, int nside, double sigma_ang, double sigma_chi, double *out);
+
+/* ---- large-scale structure: the displacement field (cora/signal/lssutil.py:225-261 gradient -> healpy.alm2map_der1,
+ * cora/signal/lss.py:806-828) ----------------------------------------------------------------------
+ * Derivative synthesis composed around corahip_alm2map (csrc/sht_der1.hip): with x = cos theta of the ring,
+ *   dT/dtheta = (x S[a1] - S[a2]) / sin theta,  (1/sin theta) dT/dphi = S[a3] / sin theta,
+ *   a1_lm = l a_lm,  a2_{l-1,m} = sqrt((2l+1)/(2l-1) (l^2 - m^2)) a_lm,  a3_lm = i m a_lm.
+ * der1_alm_prep: channel groups g0 .. g0 + g_in - 1 of alm_dev [nalm][g_src][2][4] -> alm3_dev [nalm][3 g_in][2][4],
+ *            group blocks [a1 | a2 | a3].  The caller then runs corahip_alm2map(alm3_dev, 12 g_in channels) into
+ *            maps3 [12 g_in, npix] (cut_exp of the plan as for alm2map: terms below 2^cut_exp per unit coefficient are
+ *            dropped, which bounds the error of the derivative by 2 sum |l a_lm| 2^cut_exp / sin theta).
+ * der1_combine: for fields f < nfields <= 4 g_in: out_theta[f] = s_theta[f] (x A - B) / sin theta and
+ *            out_phi[f] = s_phi[f] C / sin^(1 + phi_extra) theta with A, B, C = rows f, 4 g_in + f, 8 g_in + f of
+ *            maps3; s_theta, s_phi: device arrays of per-field factors or NULL (= 1); phi_extra 0 or 1;
+ *            out_theta, out_phi [nfields, npix] each (separate, 16-byte aligned).
+ * radial_gradient: numpy.gradient(f, x, axis=0) * s_r[:, None] for f [n, npix], n >= 2: row i is
+ *            (a f[i-1] + b f[i]) + c f[i+1] with (a, b, c) = x_coef[i] (device [n][3]; numpy's second-order interior
+ *            coefficients for non-uniform x, the one-sided pair and a 0 on the end rows); s_r device [n] or NULL;
+ *            out [n, npix] must not overlap f.
+ * All three return CORAHIP_EINVAL on arguments they cannot take.                                            */
+int corahip_der1_alm_prep(corahip_ctx *ctx, corahip_sht_plan *plan, const double *alm_dev, int g_src, int g0, int g_in,
+                          double *alm3_dev);
+int corahip_der1_combine(corahip_ctx *ctx, corahip_sht_plan *plan, const double *maps3, int g_in, int nfields,
+                         const double *s_theta, const double *s_phi, int phi_extra, double *out_theta, double *out_phi);
+int corahip_radial_gradient(corahip_ctx *ctx, const double *f, const double *x_coef, const double *s_r, int n, long npix,
+                            double *out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
