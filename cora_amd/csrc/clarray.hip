@@ -16,15 +16,6 @@
 #include <cstring>
 #include <type_traits>
 
-#ifndef CL_BUILD_BY_ROW
-#define CL_BUILD_BY_ROW 1   // profile build with the row loop outside the profile loop (0: the profile-major loops of rounds 1-4, A/B)
-#endif
-#ifndef CL_BUILD_X4
-#define CL_BUILD_X4 1       // dense rows of the row-major build two at a time with 16-byte loads (0: one row per thread, A/B)
-#endif
-#ifndef CL_ABLATE
-#define CL_ABLATE 0  // diagnostic builds: 1 no table loads in the (profile-major) build, 2 interpolation for one multipole per thread only, 3 the row-major build without the loads of its dense part, 4 = 3 + 2
-#endif
 #define CL_MAXZ 17  // zint <= 17 (zromb <= 4)
 
 #define CL_XS 512      // padded row length of the transposed tables (nkperp <= 511)
@@ -154,7 +145,6 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
     for (int a = 0; a < zint; a++) {
         __syncthreads();
         // ---- profiles of the zint sub-sample pairs (a, b = 0..zint-1)
-#if (CL_ABLATE == 0 || CL_ABLATE >= 3) && CL_BUILD_BY_ROW
         if (ZINT > 0 && all_fast) {
             // Row-major build (round 5): a thread takes table row x for ALL ZINT profiles - over the union of their row
             // ranges; a row outside a profile's own range is never read by the interpolation - so that its 6 ZINT table
@@ -171,20 +161,10 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
                 xhi = max(xhi, ipar[(a * ZN + b) * 4 + 2]);
             }
             if (nsp >= l_end - l_base) xlo = xhi;                                    // (every entry is built individually)
-            auto row_of = [&](int b, int x, double (&v)[6]) {
-                const double *r0 = tt + (size_t)ipar[(a * ZN + b) * 4 + 0] * CL_XS + x, *r1 = r0 + CL_XS;
-                v[0] = r0[0];
-                v[1] = r1[0];
-                v[2] = r0[tsz];
-                v[3] = r1[tsz];
-                v[4] = r0[2 * tsz];
-                v[5] = r1[2 * tsz];
-            };
             auto combine = [&](int b, const double (&v)[6]) {
                 const double *pp = par + (a * ZN + b) * 8;
                 return pp[0] * v[0] + pp[1] * v[1] + pp[2] * v[2] + pp[3] * v[3] + pp[4] * v[4] + pp[5] * v[5];
             };
-#if CL_BUILD_X4
             {
                 // two rows per thread and 16-byte loads: threads 0 .. 127 build the first (ZN + 1) / 2 profiles, threads
                 // 128 .. 255 the others (the table columns past nkperp are zero padding, the profile has room for them)
@@ -197,11 +177,6 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
                         double2 v[QB][6];
 #pragma unroll
                         for (int q = 0; q < QB; q++) {
-#if CL_ABLATE >= 3   // diagnostic: the row-major build without its table loads
-                            if (q0 + q < nb) {
-                                for (int i6 = 0; i6 < 6; i6++) v[q][i6] = make_double2((double)x, 1.0 + i6);
-                            } else
-#endif
                             if (q0 + q < nb) {
                                 const double *r0 = tt + (size_t)ipar[(a * ZN + b0 + q0 + q) * 4 + 0] * CL_XS + x, *r1 = r0 + CL_XS;
                                 v[q][0] = *reinterpret_cast<const double2 *>(r0);
@@ -225,15 +200,6 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
                     }
                 }
             }
-#else
-            for (int x = xlo + tid; x < xhi; x += 256) {
-                double v[ZN][6];
-#pragma unroll
-                for (int b = 0; b < ZN; b++) row_of(b, x, v[b]);
-#pragma unroll
-                for (int b = 0; b < ZN; b++) prof[b * PS + x] = combine(b, v[b]);
-            }
-#endif
             // the two rows of every early entry, per profile (slot nkperp, if an entry reaches it, repeats row nkperp - 1)
             // (one thread per (entry, profile): its twelve loads are in flight together; 25 x 9 = 225 of them at cfg 3)
             for (int e = tid; e < nsp * ZN; e += 256) {
@@ -260,7 +226,6 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
                 if (tid < ZN) prof[tid * PS + nkperp] = prof[tid * PS + nkperp - 1];
             }
         } else
-#endif
         for (int b = 0; b < zint; b++) {
             const int t = a * zint + b;
             const double *pp = par + t * 8;
@@ -268,14 +233,9 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
             const int y0 = ipar[t * 4 + 0], x0r = ipar[t * 4 + 1], nx = ipar[t * 4 + 2];
             const double *r0 = tt + (size_t)y0 * CL_XS, *r1 = r0 + CL_XS;
             double *pb = prof + b * PS;
-#if CL_ABLATE == 1   // diagnostic: no table loads
-            for (int x = x0r + tid; x < nx; x += 256) pb[x] = c0 + c1 * x;
-            (void)r0; (void)r1; (void)c2; (void)c3; (void)c4; (void)c5;
-#else
             for (int x = x0r + tid; x < nx; x += 256)
                 pb[x] = c0 * r0[x] + c1 * r1[x] + c2 * r0[tsz + x] + c3 * r1[tsz + x] + c4 * r0[2 * tsz + x] +
                         c5 * r1[2 * tsz + x];
-#endif
             if (tid == 0) lxcs_s[b] = pp[6];
             // slot nkperp repeats the last row: the interpolation reads (x0, x0 + 1) unclamped, which is then the
             // clamped x1 = min(x0 + 1, nkperp - 1) of the reference's intent (the thread that wrote row nkperp - 1, if the
@@ -306,9 +266,6 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
             constexpr bool FAST = decltype(fast_c)::value;
 #pragma unroll
             for (int k = 0; k < CL_LPT; k++) {
-#if CL_ABLATE == 2 || CL_ABLATE == 4   // diagnostic: no interpolation phase
-                if (k >= 1) continue;
-#endif
                 // (uniform: l-sharded callers pass short l ranges; the LAST slot of a range is usually almost empty - 2049 =
                 //  8 x 256 + 1: one lane of the workgroup has a ninth multipole - and the waves without one skip it)
                 if (k < kmax && (k < kmax - 1 || l_base + tid + 256 * k < nl_total)) {
@@ -349,9 +306,6 @@ clarray21_kernel(const double *__restrict__ tt, int nkperp, int nkpar, double kp
 // this order, profiles/r02_pmc.json); and consecutive slots are consecutive j of one row i, so the transpose into
 // [l][i][j] writes contiguous segments (a plain diagonal-major order made every write an isolated 8 bytes).
 #define CL_BAND 32
-#ifndef CL_XCD_ORDER
-#define CL_XCD_ORDER 1   // 0: plain i-major order inside a band (A/B)
-#endif
 __host__ __device__ static inline long cl_band_count(int n) {   // pairs of a band that has n rows (n = F - CL_BAND B)
     return n >= CL_BAND ? (long)CL_BAND * (n - (CL_BAND - 1)) + (long)(CL_BAND - 1) * CL_BAND / 2 : (long)n * (n + 1) / 2;
 }
@@ -366,7 +320,6 @@ __host__ __device__ static inline int2 pair_of_index(long p, int F) {
     const int nfull = n >= CL_BAND ? n - (CL_BAND - 1) : 0;         // rows with all CL_BAND separations
     int i, dd;
     if (p < (long)nfull * CL_BAND) {
-#if CL_XCD_ORDER
         // Round 6: inside a band's full rows index p = 8 s + x is pair (row s / 4, separation 4 x + s % 4).  Workgroups are
         // dealt round-robin over the 8 XCDs, each with its own L2: with the plain i-major order (p = 32 i + d) XCD x got the
         // separations x, x + 8, x + 16, x + 24 of every row - four groups of k_par columns 8 channels (430 columns) apart -
@@ -377,10 +330,6 @@ __host__ __device__ static inline int2 pair_of_index(long p, int F) {
         const int xq = (int)(p & 7), sq = (int)(p >> 3);
         i = sq >> 2;
         dd = 4 * xq + (sq & 3);
-#else
-        i = (int)(p / CL_BAND);
-        dd = (int)(p % CL_BAND);
-#endif
     } else {
         p -= (long)nfull * CL_BAND;
         int e = n >= CL_BAND ? CL_BAND - 1 : n;                     // entries of the first tail row

@@ -46,14 +46,8 @@ __global__ void normals_kernel(uint64_t seed, int lmax, int F, double *__restric
 // ------------------------------------------------------------------------------------
 // K3: per-l GEMM on FP64 MFMA
 // ------------------------------------------------------------------------------------
-#ifndef DRAW_ABLATE
-#define DRAW_ABLATE 0  // diagnostic builds of the fused-RNG kernel: 1 no RNG, 2 no MFMA, 3 no a_lm stores, 4 no staging of T
-#endif
 #ifndef DRAW_KK_UNROLL
 #define DRAW_KK_UNROLL 2   // unroll factor of the k-step loop of a chunk in the fused-RNG kernel (two generator chains interleaved: 7.58 -> 7.45 ms; 4: the same)
-#endif
-#ifndef DRAW_BEARLY
-#define DRAW_BEARLY 0  // 1: B-operand LDS reads of a k-step issued before its generator chain
 #endif
 #define DRAW_KC 32   // nu' per LDS stage
 #define DRAW_ROWS 64 // (c,m) rows per block (4 waves x 16)
@@ -158,7 +152,7 @@ draw_kernel(const double *__restrict__ T, size_t t_ldl, int t_row0, const int32_
 // owns whole 64-byte a_lm cells ([re x4 | im x4]) and stores them as full lines (16 bytes per lane after a quad
 // exchange).  T_l is staged by LDS-DMA through a ring of three 32-nu' stages that runs on across items: the first
 // two stages of the next item are requested before the epilogue stores of the current one.
-// Round-2 form, for the record (stamps, `make k3stamps`): 4-wave workgroups of one (l, 64 m, column group) each
+// Round-2 form, for the record (DRAW_STAMPS build): 4-wave workgroups of one (l, 64 m, column group) each
 // spent 13 % of their wave cycles in the prologue (tables, first stage), 30 % issuing / waiting for the LDS-DMA of
 // T_l - every 64 m re-staged the same 256 KB - and 28 % in an epilogue of half-line (32-byte) stores.
 // ------------------------------------------------------------------------------------
@@ -174,7 +168,7 @@ __device__ static inline void draw_glds16(const void *gsrc, unsigned lds_byte_ad
 }
 
 #ifndef DRAW_STAMPS
-#define DRAW_STAMPS 0   // diagnostic build (make k3stamps): s_memtime per phase, summed over all waves
+#define DRAW_STAMPS 0   // diagnostic build (make ab ... DEFS=-DDRAW_STAMPS=1): s_memtime per phase, summed over all waves
 #endif
 #if DRAW_STAMPS
 __device__ unsigned long long g_draw_stamps[8];
@@ -223,7 +217,7 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
     // Bs[n][slot' = slot ^ (n & 15)][2]: the 16-byte slots of a row are XOR-swizzled with the row number
     // (applied on the DMA source address), so that 16 rows read at the same k hit 16 distinct slots
     extern __shared__ __attribute__((aligned(16))) double lds[];  // [NB][NC][ROWD]
-    static_assert(NB == 3 || (NB == 2 && !FROMG), "two stages: the Philox instantiation only (no operand loads to count)");
+    static_assert(NB == 3, "the counted waits below assume three stages");
     __shared__ double2 lg_s[257], sc_s[256];   // LDS copies of the Box-Muller tables (rng_dev.h): 8 KB
     __shared__ int s_next[2];                  // next work item, double-buffered (written one item ahead)
 
@@ -293,11 +287,7 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
             const int k = k0 + 2 * slot_src;
             const double *src = zeros;  // F is even on this path (host wrapper), so k + 1 < F whenever k < F
             if (w.lbase + n < w.lend && nu < F && k + 1 < F) src = w.Tl + (size_t)n * F + k;
-#if DRAW_ABLATE != 4   // diagnostic 4: no staging of T
             draw_glds16(src, lds_base + (unsigned)((slot * BUF + 4 * rq * ROWD) * sizeof(double)));
-#else
-            (void)src;
-#endif
         }
     };
 
@@ -338,7 +328,7 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
     item_t w = decode(item);
     int ring = 0, par = 0;
     stage(w, 0, 0);
-    if (NB > 2 && w.nchunk > 1) stage(w, 1, 1);
+    if (w.nchunk > 1) stage(w, 1, 1);
     if constexpr (FROMG) {
         if (w.mb * DRAW_MB + 16 * wave < w.l + 1) issue_a(w, 0, 0, a_x);
     }
@@ -361,45 +351,26 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
         auto half_steps = [&](auto tmin_c, const double *sb, int k0, auto half_c) {
             constexpr int TMIN = decltype(tmin_c)::value;
             constexpr int half = decltype(half_c)::value;
-            constexpr int UNR = FROMG ? 4 : (NCT > 8 ? 1 : DRAW_KK_UNROLL);     // (FROMG indexes its operand registers by kk; the 256-column shape has no registers for a second chain)
+            constexpr int UNR = FROMG ? 4 : DRAW_KK_UNROLL;     // (FROMG indexes its operand registers by kk)
 #pragma unroll UNR
             for (int kk = 4 * half; kk < 4 * half + 4; kk++) {
                 const int kp = k0 + 4 * kk + kq;
                 const int kl = 4 * kk + kq;          // k within the chunk
-                // all B operands of the k-step are read up front (one address + immediate offsets; the 256-column shape:
-                // the first eight tiles' - the others behind the first MFMAs)
-                double bv[NCT > 8 ? 8 : NCT];
+                // all B operands of the k-step are read up front (one address + immediate offsets)
+                double bv[NCT];
                 const double *brow = sb + ri * ROWD + 2 * ((kl >> 1) ^ ri) + (kl & 1);
 #pragma unroll
-                for (int t = TMIN; t < (NCT > 8 ? 8 : NCT); t++) bv[t] = brow[16 * t * ROWD];
-#if DRAW_ABLATE == 1   // diagnostic: no RNG
-                double2 a = make_double2(1.0 + kp, 0.5 * m_lane);
-#else
+                for (int t = TMIN; t < NCT; t++) bv[t] = brow[16 * t * ROWD];
                 // (rows past l and nu' >= F are generated like any other: their products meet staged zeros or are
                 //  never stored - no exec masking around the chain)
                 double2 a;
                 if constexpr (FROMG) a = half ? make_double2(a_y[2 * (kk - 4 * half)], a_y[2 * (kk - 4 * half) + 1])
                                               : make_double2(a_x[2 * (kk - 4 * half)], a_x[2 * (kk - 4 * half) + 1]);
                 else a = philox_normal_pair(seed, l, F, kp, m_lane, lg_s, sc_s);
-#endif
 #pragma unroll
-                for (int t = TMIN; t < (NCT > 8 ? 8 : NCT); t++) {
-#if DRAW_ABLATE == 2   // diagnostic: no MFMA
-                    asm volatile("" ::"v"(a.x), "v"(a.y), "v"(bv[t]));
-#else
+                for (int t = TMIN; t < NCT; t++) {
                     acc0[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bv[t], acc0[t], 0, 0, 0);
                     acc1[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bv[t], acc1[t], 0, 0, 0);
-#endif
-                }
-                if constexpr (NCT > 8) {
-#pragma unroll
-                    for (int t = (TMIN > 8 ? TMIN : 8); t < NCT; t++) bv[t - 8] = brow[16 * t * ROWD];
-#pragma unroll
-                    for (int t = (TMIN > 8 ? TMIN : 8); t < NCT; t++) {
-                        acc0[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bv[t - 8], acc0[t], 0, 0, 0);
-                        acc1[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bv[t - 8], acc1[t], 0, 0, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);      // (the next k-step's generator chain must not be scheduled across: no registers for it)
                 }
             }
         };
@@ -425,9 +396,7 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
             // FROMG: the first-half operands of this chunk were requested at the middle of the previous one, BEHIND the
             // DMA pieces of stage c + 1 - they are the youngest requests in flight, so everything is waited for (stage
             // c + 1 has then had one chunk, not two, to land; the counted wait is the one in front of the second half)
-            // (NB = 2 - the 256-column shape, whose three stages would not fit the LDS -: stage c was requested behind the
-            //  barrier of chunk c - 1 and nothing younger is in flight)
-            if (NB == 2 || FROMG || c == 0 || c + 1 >= nchunk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (FROMG || c == 0 || c + 1 >= nchunk) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(QPW) : "memory");
             if constexpr (FROMG) {
                 if (wave_has_rows) pin_a(a_x);
@@ -484,7 +453,7 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
         if (have_next) {
             w = decode(item);
             stage(w, 0, ring);
-            if (NB > 2 && w.nchunk > 1) stage(w, 1, (ring + 1) % NB);      // (NB = 2: that slot is the last chunk's, maybe still read)
+            if (w.nchunk > 1) stage(w, 1, (ring + 1) % NB);
             if constexpr (FROMG) {
                 if (w.mb * DRAW_MB + 16 * wave < w.l + 1) issue_a(w, 0, 0, a_x);
             }
@@ -521,9 +490,6 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
                     const int m = mw + kq + 4 * r;
                     if (col_ok && m < lp1) {
                         const long idx = (long)m * (2 * lmax + 1 - m) / 2 + l;
-#if DRAW_ABLATE == 3   // diagnostic: no a_lm stores
-                        if (re == 1.2345e300)
-#endif
                         *reinterpret_cast<double2 *>(alm + ((size_t)idx * Gout + (col >> 2)) * 8 + 2 * q) =
                             upper ? make_double2(im_a, im_b) : make_double2(re_a, re_b);
                     }
@@ -730,14 +696,6 @@ static int draw_philox(corahip_ctx *ctx, const double *T, int rows, const int32_
     if (ncol <= 16) return launch_draw_rng<1>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
     if (ncol <= 32) return launch_draw_rng<2>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
     if (ncol <= 64) return launch_draw_rng<4>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
-    // Round-6 experiment, OFF by default (CORAHIP_K3_WIDE=1 selects it; tools/k3_wide_probe.py): ONE column group of 256 per
-    // (l, m block) where there are two of 128 - every normal pair generated once per 256 columns instead of once per 128
-    // (the generator is half of this kernel's issue time), two 64 KB stages instead of three.  Same a_lm - and 23.1 ms
-    // against 7.32: 128 accumulator registers + the generator chain do not fit the 256 of two waves per SIMD (1228 bytes
-    // of scratch per lane, ~25 scratch operations per k-step in the MFMA loop, each a vmcnt-ordered memory instruction).
-    static const bool wide = getenv("CORAHIP_K3_WIDE") && atoi(getenv("CORAHIP_K3_WIDE")) != 0;
-    if (wide && ncol >= 256 && ch.nu1 == 0 && ch.cw >= ch.nnu)
-        return launch_draw_rng<16, false, 2>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
     return launch_draw_rng<8>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
 }
 

@@ -30,8 +30,7 @@ int ring_setup(corahip_ctx *ctx) {
         // its small latency-bound launches - the jump tree of the legacy stream - get the CUs that come free first
         int prio_lo = 0, prio_hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        static const bool flat = getenv("CORAHIP_GEN_PRIO_OFF") != nullptr;     // A/B: default priority
-        HIP_TRY(hipStreamCreateWithPriority(&ctx->gen_stream, hipStreamNonBlocking, flat ? 0 : prio_hi));
+        HIP_TRY(hipStreamCreateWithPriority(&ctx->gen_stream, hipStreamNonBlocking, prio_hi));
         for (auto &e : ctx->ev_ring) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     return 0;

@@ -199,16 +199,13 @@ chol_kernel(const double *__restrict__ C, int F, double jitter_rel, double *__re
 // ------------------------------------------------------------------------------------
 #define CHM_S 34    // doubles per staged block row
 #ifndef CHM_STAMPS
-#define CHM_STAMPS 0   // diagnostic build (make k2stamps): s_memtime per phase of chol_ll_kernel, summed over the waves
+#define CHM_STAMPS 0   // diagnostic build (make ab ... DEFS=-DCHM_STAMPS=1): s_memtime per phase of chol_ll_kernel, summed over the waves
 #endif
 #if CHM_STAMPS
 __device__ unsigned long long g_chm_stamps[8];
 #define CSTAMP(k) { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory"); c_acc[k] += _t - c_last; c_last = _t; }
 #else
 #define CSTAMP(k)
-#endif
-#ifndef CHM_ABLATE
-#define CHM_ABLATE 0   // diagnostic builds (wrong results): 1 no diagonal-block factorisation, 2 no panel solve, 3 no MFMA updates
 #endif
 
 // TALL = true (F >= 384): the wave tiles of step A are 64 rows x 32 columns (two block rows) and the factor block
@@ -308,7 +305,7 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
                             if (has && row < F && col <= row) v = A[(size_t)row * F + col] + (row == col ? jit : 0.0);
                             acc[a][b][r] = v;
                         }
-                if (j > 0 && CHM_ABLATE != 3) {
+                if (j > 0) {
                     double2 va0[8], va1[8], vb[2];
                     if (has) {
                         load_block(i0, 0, va0);
@@ -407,7 +404,7 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
                         if (row < F && col <= row) v = A[(size_t)row * F + col] + (row == col ? jit : 0.0);
                         acc[a][b][r] = v;
                     }
-            if (j > 0 && CHM_ABLATE != 3) {
+            if (j > 0) {
                 double2 va[8], vb[8];
                 load_block(i0, 0, va);
                 load_block(kb, 0, vb);
@@ -466,7 +463,7 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
         __syncthreads();
         CSTAMP(1);           // barrier behind A
         // ---- B. factor the diagonal block with ONE wave, row i of the block in the registers of lane i
-        if (tid < 64 && CHM_ABLATE != 1) {
+        if (tid < 64) {
             auto bcast = [](double v, int src) {
                 const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
                 const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
@@ -510,7 +507,7 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
         }
         const int r0 = kb + nb;
         // ---- C. the tiles below: X = S L_jj^{-T}, one row per thread, in place (nb == 32 whenever there are rows below)
-        for (int r = r0 + tid; r < F && CHM_ABLATE != 2; r += 256) {
+        for (int r = r0 + tid; r < F; r += 256) {
             double x[CH_NB];
             double *row = Tl + (size_t)r * F + kb;
 #pragma unroll
@@ -804,7 +801,7 @@ chol_coop_kernel(const double *__restrict__ C, int F, double jitter_rel, double 
     }
     if (wgl == 0 && tid == 0) {
         info[mat0 + mi] = failed;
-        xcc_max[mi] = same_xcc ? 0x100 : 0x200;       // (diagnostics: which barrier the group took - CORAHIP_K2_COOP_DEBUG)
+        xcc_max[mi] = same_xcc ? 0x100 : 0x200;       // (diagnostics: which barrier the group took)
     }
 }
 
@@ -973,11 +970,8 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
     ARG_CHECK(ctx != nullptr && C != nullptr && T != nullptr && info != nullptr);
     ARG_CHECK(nl >= 1 && F >= 1);
     StageTimer t(ctx, "factor");
-    static const bool no_mfma = getenv("CORAHIP_K2_VALU") != nullptr;   // A/B: the VALU kernel for every size
-    if (F >= 64 && (F % 2) == 0 && !no_mfma) {
-        // tall tiles + shared L_jk from F = 384 on (CORAHIP_K2_TALL=0 / 1 forces one form: A/B runs)
-        static const char *tall_env = getenv("CORAHIP_K2_TALL");
-        const bool tall = tall_env ? atoi(tall_env) != 0 : F >= 384;
+    if (F >= 64 && (F % 2) == 0) {
+        const bool tall = F >= 384;   // tall tiles + shared L_jk (see chol_ll_kernel)
         const size_t shm = sizeof(double) * (CH_NB * (CH_NB + 1) + 256 + 2 + CH_NB + (tall ? 6 : 8) * 32 * CHM_S) + 16;
         // The last nl mod (2 x CUs) matrices of a tall batch, if they are few, go to the cooperative kernel behind the batch:
         // a straggler round of the one-workgroup form costs a whole single-matrix latency (4.4 ms at F = 1024) for them.
@@ -1022,14 +1016,6 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
                 HIP_TRY(hipMemsetAsync(xmin, 0x7f, sizeof(int) * nrem, ctx->stream));   // (min starts high; max at 0)
                 chol_coop_kernel<<<((nrem + 7) / 8) * 8 * G, 256, shm2, ctx->stream>>>(C, F, jitter_rel, T, info, nmain, nrem, G, bar, gflag, rd,
                                                                                      xmin, xmax);
-                if (getenv("CORAHIP_K2_COOP_DEBUG")) {
-                    std::vector<int> hx(nrem);
-                    HIP_TRY(hipMemcpyAsync(hx.data(), xmax, sizeof(int) * nrem, hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_TRY(hipStreamSynchronize(ctx->stream));
-                    int same = 0;
-                    for (int v : hx) same += v == 0x100;
-                    fprintf(stderr, "K2 cooperative kernel: %d matrices, %d workgroups each, %d groups on one XCC\n", nrem, G, same);
-                }
             }
         } else {
             HIP_TRY(hipFuncSetAttribute((const void *)chol_ll_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));

@@ -3,10 +3,6 @@
 #pragma once
 #include "sht_internal.h"
 
-#ifndef CT_ABLATE_TW
-#define CT_ABLATE_TW 0
-#endif
-
 // LDS padding of a channel buffer, per kernel family (PK, a template parameter of everything below that touches a
 // buffer): 0 = one spare 16-byte slot per 8 elements plus 8 per 128 (rounds 1-3), 1 = one spare slot per 16 elements.
 // In the lane-group simulation of ds_read_b128 / ds_write_b128 (tools/lds_bank_sim.py) padding 0 makes every read of
@@ -323,11 +319,7 @@ __device__ __forceinline__ static void tw_apply(double2 (&x)[R], double2 w1) {
 #pragma unroll
     for (int r = 2; r < R; r++) {
         const int lb = r & (-r);
-#if CT_ABLATE_TW     // diagnostic (wrong results): no twiddle powers - what would a table of them be worth?
-        w[r] = make_double2(w1.x + (double)r, w1.y);
-#else
         w[r] = (lb == r) ? csqr(w[r >> 1]) : cmul(w[r - lb], w[lb]);
-#endif
         x[r] = cmul(x[r], w[r]);
     }
 }

@@ -23,9 +23,6 @@
 #include "common.h"
 #include "rng_dev.h"
 
-#ifndef FS_ABLATE
-#define FS_ABLATE 0   // diagnostic builds (wrong results): 1 no LDS passes, 2 also no bit-reversed commit
-#endif
 #ifndef FS_PAIR_XCD
 #define FS_PAIR_XCD 3   // log2 of the adjacent tiles given to one XCD at a time (0: off); measured 1024^3 axis-1 pass: 7.05 / 6.44 / 6.2 / 6.08 ms for 0 / 1 / 2 / 3
 #endif
@@ -44,9 +41,6 @@ __device__ static inline double2 cadd(double2 a, double2 b) { return make_double
 __device__ static inline double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 __device__ static inline double2 mul_mi(double2 a) { return make_double2(a.y, -a.x); }  // a * (-i)
 __device__ static inline unsigned brev_n(unsigned i, int logP) {
-#if FS_ABLATE == 2
-    return i;
-#endif
     return logP ? (__brev(i) >> (32 - logP)) : 0u;
 }
 
@@ -385,7 +379,7 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
                 lds_dif(fs_lds, P, logP, cur.teff, twl);
             else
                 lds_dif(fs_lds, P, logP, cur.teff, A.tw);
-        } else if (FS_ABLATE == 0) {
+        } else {
             if (A.twl)
                 lds_dit(fs_lds, P, logP, cur.teff, twl);
             else

@@ -473,7 +473,7 @@ int flat_c2c_ct(corahip_ctx *ctx, const double *in, double *out, long nouter, in
     int rc;
     if (n == 256 && inner >= 16) rc = launch_linec2c<256, 16, 256>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 512 && inner >= 16) rc = launch_linec2c<512, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else if (n == 1024 && inner >= 16 && !getenv("CORAHIP_FLAT_NOH2")) rc = launch_linec2c_h2<1024, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
+    else if (n == 1024 && inner >= 16) rc = launch_linec2c_h2<1024, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 1024 && inner >= 8) rc = launch_linec2c<1024, 8, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 384 && inner >= 16) rc = launch_linec2c<384, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 768 && inner >= 8) rc = launch_linec2c<768, 8, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);

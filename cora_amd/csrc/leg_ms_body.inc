@@ -27,14 +27,6 @@
                     // nothing of this wave starts before l0+14: skip the macro-step entirely
                     if (LEG_CLEAN != 1 && ws_min > l0 + 13) continue;
                     double ae[RT], ao[RT];
-#if LEG_ABLATE == 2  // diagnostic: no recurrence
-#pragma unroll
-                    for (int q = 0; q < RT; q++) {
-                        ae[q] = x[q];
-                        ao[q] = x[q] + 1.0;
-                        asm volatile("" : "+v"(ae[q]), "+v"(ao[q]));
-                    }
-#else
                     double2 c[8];
 #pragma unroll
                     for (int j = 0; j < 8; j++) c[j] = sc[8 * LEG_MS + j];
@@ -58,44 +50,18 @@
                             if (j == 1) ao[q] = vv * c[1].y;
                         }
                     }
-#endif
                     if (LEG_CLEAN != 1 && ws_min > l0 + 7) continue;  // all A operands of this macro-step are zero
 #if LEG_STAMPS && !LEG_CLEAN
                     n_tail_ms++;
 #endif
-#if LEG_ABLATE == 5  // diagnostic: 16 extra INTEGER VALU instructions per macro-step (does non-matrix VALU issue hide behind MFMAs?)
-                    {
-                        unsigned dummy = (unsigned)l0;
-#pragma unroll
-                        for (int q = 0; q < 16; q++) asm volatile("v_add_u32 %0, %0, %1" : "+v"(dummy) : "v"(lane));
-                        asm volatile("" ::"v"(dummy));
-                    }
-#endif
-#if LEG_ABLATE == 6  // diagnostic: 16 extra SALU instructions per macro-step
-                    {
-                        unsigned sd0 = (unsigned)l0;
-#pragma unroll
-                        for (int q = 0; q < 16; q++) asm volatile("s_add_u32 %0, %0, 1" : "+s"(sd0));
-                        asm volatile("" ::"s"(sd0));
-                    }
-#endif
                     const double *be = sb + (8 * LEG_MS + d) * STRIDE + ri;
                     const double *bo = be + STRIDE;
-#if LEG_ABLATE == 1  // diagnostic: no MFMA (keep the operands alive)
-                    asm volatile("" ::"v"(ae[0]), "v"(ao[0]), "v"(be), "v"(bo));
-#else
 #pragma unroll
                     for (int t = 0; t < NT; t++) {
-#if LEG_ABLATE == 3  // diagnostic: no B operand reads from LDS
-                        const double bev = ae[0] + t, bov = ao[0] - t;
-                        asm volatile("" ::"v"(be), "v"(bo));
-#else
                         const double bev = be[16 * t], bov = bo[16 * t];
-#endif
 #pragma unroll
                         for (int q = 0; q < RT; q++) {
                             acce[q][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[q], bev, acce[q][t], 0, 0, 0);
                             acco[q][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ao[q], bov, acco[q][t], 0, 0, 0);
                         }
                     }
-#endif

@@ -51,9 +51,6 @@ typedef unsigned __int128 u128;
 #define ZIG_ROWS 16         // rows of 64 consecutive positions per block: lane p of row j holds position 64 j + p
 #define ZIG_BLK (64 * ZIG_ROWS)
 #define ZIG_WG 256          // threads per workgroup of the count / emit kernels (independent waves, one block each)
-#ifndef ZIG_ABLATE
-#define ZIG_ABLATE 0        // diagnostic builds (make zigablate; wrong results, timing only): 1 no wedge gather / tests,
-#endif                      //   2 also no classification (generator only), 3 no chain in pass 1, 4 pass 2 without stores
 
 namespace {
 
@@ -536,17 +533,9 @@ __device__ inline uint64_t block_classify(cols_t &c, u128 s_blk, u128 inc, u128 
         s = s * M64 + c64;
         const uint64_t raw_next = pcg_out(s);                    // row j + 1 (row 16: the next block's first row)
         const unsigned idx = (unsigned)(raw_cur & 0xff);
-#if ZIG_ABLATE == 2
-        const bool slow = (raw_cur >> 9) == 12345;
-#else
         const bool slow = ((raw_cur >> 9) & M52) >= L.ki[idx];
-#endif
         const uint64_t NF = __ballot(slow), Z = __ballot(slow && idx == 0);
-#if ZIG_ABLATE == 1 || ZIG_ABLATE == 2
-        const uint64_t Wm = 0;
-#else
         const uint64_t Wm = NF & ~Z;
-#endif
         if (Wm) {
             // the wedge draw of position p is the draw of position p + 1: the next lane, or lane 0 of the next row
             uint64_t r1 = wave_shl1(raw_cur);
@@ -619,10 +608,6 @@ zig_count_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64
         }
         if (lane == 0) tails[b] = tt;
         unsigned kb0, total0, kb1, total1;
-#if ZIG_ABLATE == 3
-        kb0 = kb1 = 0;
-        total0 = total1 = 1000 + (c.nf_lo & 1);
-#else
         {
             const bool row = lane < ZIG_ROWS;
             const uint64_t nf = ((uint64_t)c.nf_hi << 32) | c.nf_lo, z = ((uint64_t)c.z_hi << 32) | c.z_lo,
@@ -651,7 +636,6 @@ zig_count_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64
             kb1 = kk[1];
             total1 = tt_[1];
         }
-#endif
         if (lane == 0) *reinterpret_cast<uint2 *>(fun + 2 * b) = make_uint2((kb0 << 16) | total0, (kb1 << 16) | total1);
         // rare: a tail sample (or several) reaches across the end of the block
         for (int e = 0; e < 2; e++) {
@@ -1017,11 +1001,7 @@ zig_emit_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64_
                         }
                     } else if ((e >> lane) & 1) {
                         const unsigned long long o = ord_blk + readlane32(base_col, j) + mbcnt64(e);
-#if ZIG_ABLATE == 4
-                        if (o - o_lo < o_n && raw == 12345) {
-#else
                         if (o - o_lo < o_n) {
-#endif
                             g[o - o_lo] = zig_value(raw, L.wi);
                             if (o + 1 == n) st->n_raw = blk_pos + 64u * j + lane + 1 + ((readlane64(ew_col, j) >> lane) & 1);
                         }
@@ -1116,9 +1096,6 @@ __global__ void zig_range_kernel(const ulonglong2 *__restrict__ entry, long nblk
 struct zc_head {
     unsigned ticket, pad0;
     unsigned long long pad1;
-#ifdef ZC_STATS
-    unsigned long long polls, folds, cyc_classify, cyc_lookback, cyc_emit, cyc_total, chunks, dist;
-#endif
 };
 
 __device__ inline unsigned long long zc_ld(const unsigned long long *p) {
@@ -1213,9 +1190,6 @@ __device__ inline bool zc_lookback(long c, const unsigned long long *agg, const 
         unsigned long long pc[2] = {0ull, 0ull};
         bool any_pending = false, failed = false;
         for (long base = c - 1; !failed; base -= 64 * ZC_NWIN) {
-#ifdef ZC_STATS
-            if (lane == 0) atomicAdd(&head->polls, 1ull);
-#endif
             unsigned long long iw[ZC_NWIN], aw[ZC_NWIN];
 #pragma unroll
             for (int w = 0; w < ZC_NWIN; w++) {
@@ -1267,9 +1241,6 @@ __device__ inline bool zc_lookback(long c, const unsigned long long *agg, const 
                     }
                     k_out = k;
                     ord_out = ord;
-#ifdef ZC_STATS
-                    if (lane == 0) atomicAdd(&head->dist, (unsigned long long)(c - 1 - base + 64 * w + li));
-#endif
                     return true;
                 }
                 // 64 aggregates, no inclusive word: pending <- pending o f
@@ -1285,9 +1256,6 @@ __device__ inline bool zc_lookback(long c, const unsigned long long *agg, const 
                 }
                 pk[0] = nk[0], pk[1] = nk[1], pc[0] = nc[0], pc[1] = nc[1];
                 any_pending = true;
-#ifdef ZC_STATS
-                if (lane == 0) atomicAdd(&head->folds, 1ull);
-#endif
             }
         }
         if (spin >= ZC_SPIN_CAP) {
@@ -1423,9 +1391,6 @@ zig_chain_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64
         const long chunk = s_chunk;
         if (chunk >= nchunk) break;
         const long b = chunk * ZC_WAVES + wave;
-#ifdef ZC_STATS
-        const unsigned long long tA = __builtin_readcyclecounter();
-#endif
         const ulonglong2 bs = blk_state[b];
         const u128 s_blk = mk128(uni64(bs.x), uni64(bs.y));
         cols_t c;
@@ -1496,17 +1461,7 @@ zig_chain_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64
         unsigned k_c = 0;
         unsigned long long ord_c = 0;
         bool lb_ok = true;
-#ifdef ZC_STATS
-        const unsigned long long tB = __builtin_readcyclecounter();
-#endif
-#if defined(ZC_ABLATE) && ZC_ABLATE == 1      // (timing only, wrong ordinals: no look-back at all - the work of the kernel by itself)
-        ord_c = (unsigned long long)chunk * 4000ull;
-#else
         if (wave == 0) lb_ok = zc_lookback(chunk, agg, incw, k_c, ord_c, &st->error, head);
-#endif
-#ifdef ZC_STATS
-        const unsigned long long tC = __builtin_readcyclecounter();
-#endif
         for (;;) {
             if (threadIdx.x == 0) {
                 unsigned req = ZC_NONE, kx = 0, cx = 0;
@@ -1554,32 +1509,7 @@ zig_chain_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64
         if (!s_skip)
             block_emit(raw, c, tt, tv, G, C1, s_blk, inc, s_ent[wave], s_ord + s_off[wave], o_n, g,
                        pos_base + (unsigned long long)b * ZIG_BLK, carry_out, L.wi, &st->error);
-#ifdef ZC_STATS
-        if (threadIdx.x == 0) {
-            const unsigned long long tD = __builtin_readcyclecounter();
-            atomicAdd(&head->cyc_classify, tB - tA);
-            atomicAdd(&head->cyc_lookback, tC - tB);
-            atomicAdd(&head->cyc_emit, tD - tC);
-            atomicAdd(&head->chunks, 1ull);
-        }
-#endif
     }
-}
-
-__global__ void zig_debug_kernel(const ulonglong2 *blk_state, uint64_t i_hi, uint64_t i_lo, long b, uint64_t *out) {
-    const u128 inc = mk128(i_hi, i_lo);
-    const int lane = threadIdx.x & 63;
-    const jump_t lj = ZIG_LANE.v[lane];
-    const u128 lane_m = mk128(lj.mhi, lj.mlo), lane_c = inc * mk128(lj.ghi, lj.glo);
-    const ulonglong2 bs = blk_state[b];
-    const u128 s_blk = mk128(uni64(bs.x), uni64(bs.y));
-    const u128 s = lane_m * s_blk + lane_c;
-    out[lane] = pcg_out(s);
-    const u128 s2 = jump_apply(ZIG_LANE.v[lane], mk128(bs.x, bs.y), inc);
-    out[64 + lane] = pcg_out(s2);
-    constexpr u128 M64 = mk128(H_POW2.v[6].mhi, H_POW2.v[6].mlo);
-    const u128 c64 = inc * mk128(H_POW2.v[6].ghi, H_POW2.v[6].glo);
-    out[128 + lane] = pcg_out(s2 * M64 + c64);
 }
 
 }  // namespace
@@ -1657,34 +1587,6 @@ static int zig_round_count_scan(corahip_ctx *ctx, hipStream_t stream, const uint
         LAUNCH_CHECK();
     }
     return 0;
-}
-static void zig_debug_dump(corahip_ctx *ctx, const zig_round &rd, const uint64_t inc[2], const zig_status &hs) {
-    const long nb = std::min<long>(rd.nblk, 8);
-    std::vector<unsigned> hf(2 * nb);
-    std::vector<ulonglong2> he(nb), hb(nb);
-    uint4 tf;
-    ulonglong2 te;
-    (void)hipMemcpy(hf.data(), rd.fun, sizeof(unsigned) * 2 * nb, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(he.data(), rd.entry, sizeof(ulonglong2) * nb, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(hb.data(), rd.blk_state, sizeof(ulonglong2) * nb, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(&tf, rd.tile_fun, sizeof(tf), hipMemcpyDeviceToHost);
-    (void)hipMemcpy(&te, rd.tile_entry, sizeof(te), hipMemcpyDeviceToHost);
-    fprintf(stderr, "zig debug: nblk %ld ntile %ld total %llu k_last %u npatch %u err %u n_raw %llu | tile0 fun (%u %u %u %u) entry (%llu %llu)\n",
-            rd.nblk, rd.ntile, hs.total, hs.k_last, hs.npatch, hs.error, hs.n_raw, tf.x, tf.y, tf.z, tf.w, te.x, te.y);
-    {
-        uint64_t *dbg = nullptr, h[192];
-        (void)hipMalloc(&dbg, sizeof(h));
-        zig_debug_kernel<<<1, 64, 0, ctx->stream>>>(rd.blk_state, inc[0], inc[1], 1, dbg);
-        (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
-        (void)hipFree(dbg);
-        fprintf(stderr, "  blk 1 raws: hoisted %016llx %016llx %016llx | table %016llx %016llx %016llx | row 1 %016llx %016llx\n",
-                (unsigned long long)h[0], (unsigned long long)h[1], (unsigned long long)h[63], (unsigned long long)h[64],
-                (unsigned long long)h[65], (unsigned long long)h[127], (unsigned long long)h[128], (unsigned long long)h[129]);
-    }
-    for (long i = 0; i < nb; i++)
-        fprintf(stderr, "  blk %ld: state %016llx%016llx fun0 (k %u cnt %u) fun1 (k %u cnt %u) entry (k %llu ord %llu)\n", i,
-                hb[i].x, hb[i].y, hf[2 * i] >> 16, hf[2 * i] & 0xffff, hf[2 * i + 1] >> 16, hf[2 * i + 1] & 0xffff,
-                he[i].x, he[i].y);
 }
 
 // ---- the stream in ranges, two-pass form (the default; CORAHIP_ZIG_ONEPASS=1 takes the single pass below) ---------------
@@ -1788,7 +1690,7 @@ static long zc_blocks(unsigned long long want) {
     return (nblk + ZC_WAVES - 1) / ZC_WAVES * ZC_WAVES;
 }
 // The two-pass form is the default: measured at cfg 3 (HISTORY.md, round 6) the single pass takes 14.5 ms against 6.3 -
-// its work alone (look-back ablated) is 5.5 ms, and the chunks wait ~19 polls each for the aggregates of stragglers that
+// its work alone (without the look-back) is 5.5 ms, and the chunks wait ~19 polls each for the aggregates of stragglers that
 // the LDS-bound run-ahead (768 chunks) cannot absorb.  CORAHIP_ZIG_ONEPASS=1 selects it (tests/test_gpu_npnormal.py runs both).
 static bool zig_two_pass() {
     const char *e = getenv("CORAHIP_ZIG_ONEPASS");
@@ -1888,20 +1790,6 @@ int zig_stream_finish(corahip_ctx *ctx, hipStream_t stream, zig_session *s, uint
     HIP_TRY(hipMemcpyAsync(&hs, s->st, sizeof(hs), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(&last, s->carry + s->nr, sizeof(last), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-#ifdef ZC_STATS
-    {
-        zc_head hh;
-        (void)hipMemcpy(&hh, s->head, sizeof(hh), hipMemcpyDeviceToHost);
-        const double nc = (double)std::max<unsigned long long>(1, hh.chunks);
-        fprintf(stderr, "zc stats (last range): chunks %llu polls/chunk %.2f folds/chunk %.3f distance %.1f | cycles per chunk (100 MHz clock): classify %.0f "
-                "lookback %.0f emit %.0f\n", hh.chunks, hh.polls / nc, hh.folds / nc, hh.dist / nc, hh.cyc_classify / nc, hh.cyc_lookback / nc,
-                hh.cyc_emit / nc);
-    }
-#endif
-#ifdef ZC_ABLATE
-    *n_raw = 1;
-    return 0;
-#endif
     if (hs.error) {
         corahip_set_error("normals_pcg64: device status %u (1 tail loop cap, 2 patch list full, 8 look-back gave up, 16 a range's raw blocks "
                           "did not hold its normals)", hs.error);
@@ -1977,7 +1865,6 @@ int corahip_normals_pcg64(corahip_ctx *ctx, const uint64_t state[2], const uint6
         zig_status hs;
         HIP_TRY(hipMemcpyAsync(&hs, rd.st, sizeof(hs), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (getenv("CORAHIP_ZIG_DEBUG")) zig_debug_dump(ctx, rd, inc, hs);
         if (hs.error) {
             corahip_set_error("normals_pcg64: device status %u (1 tail loop cap, 2 patch list full, 4 patch missing)", hs.error);
             return CORAHIP_ESTATE;

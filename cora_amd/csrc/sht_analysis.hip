@@ -2,12 +2,6 @@
 // deterministic reduction over ring tiles.  See sht_internal.h.
 #include "sht_internal.h"
 
-#ifndef ADJ_MU
-#define ADJ_MU 1         // 1: scaled two-instruction recurrence (mu form), scale applied per output row; 0: (A, B) form (A/B builds)
-#endif
-#ifndef ADJ_ROWS_REDUCE
-#define ADJ_ROWS_REDUCE 1   // 1: the tile reduction goes row by row (m) and skips what a ring tile cannot reach; 0: flat sum over zero-filled partial buffers (A/B)
-#endif
 #ifndef ADJ_CUNROLL
 #define ADJ_CUNROLL 8    // recurrence steps whose (scalar-loaded) coefficients are fetched together; measured 8 / 16 / 32: 25.1 / 26.9 / 25.5 ms
 #endif
@@ -19,10 +13,10 @@
 // into the A-operand layout (16 same-parity l x 4 rings), and the wave's G tile (64 rings x 16 NCT columns, even = N+S and
 // odd = N-S combinations) stays in REGISTERS as the B operand for the whole item.  The eight waves hold
 // different rings, so their [32 l x 16 NCT] partial sums are added through LDS once per l-block; the four
-// ring tiles of an (m, column group) go to separate partial buffers summed by alm_reduce_kernel
+// ring tiles of an (m, column group) go to separate partial buffers summed by alm_reduce_rows_kernel
 // (deterministic - no atomics).
 // Round 5, tried and withdrawn: ONE workgroup walking the four ring tiles of its (m, column group) and adding the later
-// tiles' sums onto its own earlier stores (no partial buffers, no alm_reduce_kernel: 1.9 of 21 ms).  Correct, but the
+// tiles' sums onto its own earlier stores (no partial buffers, no reduction kernel: 1.9 of 21 ms).  Correct, but the
 // kernel sits at 256 VGPRs (128 of them the G tile) and the restructured loop made the allocator spill B operands into
 // the MFMA loop (scratch 28 -> 450-520 bytes): 20.96 ms against 21.05, a single l block per reduction 24.5 ms.
 // Round 5: the recurrence runs in the synthesis kernel's scaled two-instruction form mu_l = (alpha_l x) mu_{l-1} - mu_{l-2}
@@ -71,11 +65,7 @@ legendre_adj_kernel(int lmax, int npair, int nring, int ncols, const double *__r
         const long base_m = alm_idx(0, m, lmax);
         const int lb0 = lmin <= lmax ? m + ((lmin - m) & ~(LB - 1)) : lmax + 1;
         double *pout = part + ((size_t)rtile * nalm + base_m) * ncols + (size_t)cg * TCOLS;
-#if !ADJ_ROWS_REDUCE
-        // multipoles this tile cannot reach contribute zero
-        for (int e = tid; e < (lb0 - m) * TCOLS; e += 512) pout[(size_t)(m + e / TCOLS) * ncols + e % TCOLS] = 0.0;
-#endif
-        // (ADJ_ROWS_REDUCE: the rows below lb0 are neither written here nor read by alm_reduce_rows_kernel, which forms the
+        // (the rows below lb0 are neither written here nor read by alm_reduce_rows_kernel, which forms the
         //  same lb0 per (m, ring tile) - a fifth of the partial buffers' traffic was zeros)
 
         if (lb0 <= lmax) {
@@ -128,11 +118,7 @@ legendre_adj_kernel(int lmax, int npair, int nring, int ncols, const double *__r
                     for (int j = 0; j < LB; j++) {
                         const int l = lb + j;
                         const double2 c = cf[l];
-#if ADJ_MU
                         double vv = fma(c.x * x, p1, -p0);
-#else
-                        double vv = fma(c.x * x, p1, -(c.y * p0));
-#endif
                         const bool inj = (l == my_ls);
                         vv = inj ? sd.y : vv;
                         p0 = inj ? sd.x : p1;
@@ -143,11 +129,7 @@ legendre_adj_kernel(int lmax, int npair, int nring, int ncols, const double *__r
 #pragma unroll ADJ_CUNROLL
                     for (int j = 0; j < LB; j++) {
                         const double2 c = cf[lb + j];
-#if ADJ_MU
                         const double vv = fma(c.x * x, p1, -p0);
-#else
-                        const double vv = fma(c.x * x, p1, -(c.y * p0));
-#endif
                         p0 = p1;
                         p1 = vv;
                         lamw[lane * LSTR + (j & 1) * 16 + (j >> 1)] = vv;
@@ -195,7 +177,6 @@ legendre_adj_kernel(int lmax, int npair, int nring, int ncols, const double *__r
             // transpose buffer exactly)
             for (int lb = lb0; lb <= lmax; lb += 2 * LB) {
                 d4_t acc0[2][NCT], acc1[2][NCT];
-#if ADJ_MU
                 // the row scales s_l of this thread's outputs of the reduction below, requested now: behind the barrier
                 // their latency would be exposed to the whole workgroup
                 double srow[2 * NCT];
@@ -205,7 +186,6 @@ legendre_adj_kernel(int lmax, int npair, int nring, int ncols, const double *__r
                     const int el = e & 63, r = (e >> 6) & 3, q = e >> 8, par = (q / NCT) & 1, blk = q / (2 * NCT);
                     srow[u] = cf[min(lb + blk * LB + 2 * ((el >> 4) + 4 * r) + par, lmax + 31)].y;   // (the table is padded by 32 entries; rows past lmax are discarded)
                 }
-#endif
 #pragma unroll
                 for (int par = 0; par < 2; par++)
 #pragma unroll
@@ -234,11 +214,7 @@ legendre_adj_kernel(int lmax, int npair, int nring, int ncols, const double *__r
                     for (int w = 0; w < ADJ_WAVES; w++) sum += lds[w * WREG + e];
                     const int el = e & 63, r = (e >> 6) & 3, q = e >> 8, t = q % NCT, par = (q / NCT) & 1, blk = q / (2 * NCT);
                     const int l = lb + blk * LB + 2 * ((el >> 4) + 4 * r) + par;
-#if ADJ_MU
                     if (l <= lmax) pout[(size_t)l * ncols + 16 * t + (el & 15)] = sum * srow[u];    // lambda_l = s_l mu_l: the scale is a property of the ROW
-#else
-                    if (l <= lmax) pout[(size_t)l * ncols + 16 * t + (el & 15)] = sum;
-#endif
                 }
                 __syncthreads();
             }
@@ -249,17 +225,9 @@ legendre_adj_kernel(int lmax, int npair, int nring, int ncols, const double *__r
     }
 }
 
-// alm_dev[idx][col] = sum over ring tiles of part[rt][idx][col]
-__global__ void alm_reduce_kernel(const double *__restrict__ part, long n, int ntile, double *__restrict__ alm) {
-    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
-        double s = 0.0;
-        for (int t = 0; t < ntile; t++) s += part[(size_t)t * n + q];
-        alm[q] = s;
-    }
-}
-// the same sum by rows: block (chunk of 64 multipoles, m).  Ring tile t reaches row m from lb0_t(m) on (the block of
-// 32 l that holds the first l any of its rings contributes to - legendre_adj_kernel's own expression); below that the
-// tile's partial buffer holds nothing and is not read.
+// alm_dev[idx][col] = sum over ring tiles of part[rt][idx][col], by rows: block (chunk of 64 multipoles, m).  Ring tile t
+// reaches row m from lb0_t(m) on (the block of 32 l that holds the first l any of its rings contributes to -
+// legendre_adj_kernel's own expression); below that the tile's partial buffer holds nothing and is not read.
 __global__ void __launch_bounds__(256)
 alm_reduce_rows_kernel(const double *__restrict__ part, long nalm, int ntile, int ncols, int lmax, int ntile128,
                        const int32_t *__restrict__ lmin_tab, const double *__restrict__ zeros, double *__restrict__ alm) {
@@ -337,8 +305,7 @@ static int launch_legendre_adj(corahip_ctx *ctx, const corahip_sht_plan *p, int 
     dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu));
     HIP_TRY(hipMemsetAsync(p->d_queue, 0, 64, ctx->stream));
     legendre_adj_kernel<NCT><<<grid, 512, shm, ctx->stream>>>(p->lmax, p->npair, p->nring, ncols, p->d_z,
-                                                             ADJ_MU ? p->d_coefmu : p->d_coef, p->d_lstart,
-                                                             ADJ_MU ? p->d_seedmu : p->d_seed, p->d_lmin, p->d_mcut, inter, part,
+                                                             p->d_coefmu, p->d_lstart, p->d_seedmu, p->d_lmin, p->d_mcut, inter, part,
                                                              p->d_queue);
     LAUNCH_CHECK();
     return 0;
@@ -352,20 +319,10 @@ int sht_legendre_adj(corahip_ctx *ctx, const corahip_sht_plan *p, int ncols, con
     else rc = launch_legendre_adj<1>(ctx, p, ncols, inter, part);
     if (rc) return rc;
     const int ntile = (p->npair + 64 * ADJ_WAVES - 1) / (64 * ADJ_WAVES);
-    const long n = p->nalm * (long)ncols;
-    (void)n;
-#if ADJ_ROWS_REDUCE
-    if (ntile <= 16) {
-        const int ntile128 = (p->npair + LMIN_RINGS - 1) / LMIN_RINGS;
-        dim3 grid((unsigned)((p->L + 63) / 64), (unsigned)p->L);
-        alm_reduce_rows_kernel<<<grid, 256, 0, ctx->stream>>>(part, p->nalm, ntile, ncols, p->lmax, ntile128, p->d_lmin, p->d_zeros, alm_dev);
-        LAUNCH_CHECK();
-        return 0;
-    }
-    return CORAHIP_EINVAL;      // (more than 16 ring tiles: nside > 16384)
-#else
-    alm_reduce_kernel<<<(int)std::min<long>((n + 255) / 256, 8192), 256, 0, ctx->stream>>>(part, n, ntile, alm_dev);
+    if (ntile > 16) return CORAHIP_EINVAL;      // (more than 16 ring tiles: nside > 16384)
+    const int ntile128 = (p->npair + LMIN_RINGS - 1) / LMIN_RINGS;
+    dim3 grid((unsigned)((p->L + 63) / 64), (unsigned)p->L);
+    alm_reduce_rows_kernel<<<grid, 256, 0, ctx->stream>>>(part, p->nalm, ntile, ncols, p->lmax, ntile128, p->d_lmin, p->d_zeros, alm_dev);
     LAUNCH_CHECK();
-#endif
     return 0;
 }

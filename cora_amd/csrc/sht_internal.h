@@ -99,9 +99,6 @@ static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // ------------------------------------------------------------------------------------
 // K4: Legendre contraction on FP64 MFMA
 // ------------------------------------------------------------------------------------
-#ifndef LEG_ABLATE
-#define LEG_ABLATE 0  // diagnostic builds only (make ablate): 1 no MFMA, 2 no recurrence, 3 no B reads, 4 no epilogue stores
-#endif
 #ifndef LEG_KT
 #define LEG_KT 56     // rows of l per LDS stage (re-tuned after the instruction-count pass: 48 x 3 68.5, 56 x 2 67.7, 48 x 2 68.9, 40 x 3 72.1, 32 x 4 69.8 ms)
 #endif
@@ -235,38 +232,17 @@ struct DftR<16, SIGN> {
 };
 
 // LDS layout of an FFT buffer: logical element i lives at fpad(i); fpad_len(n) slots hold n elements.
-// K5_SWZ = 0 (shipped): one spare slot per 8 elements plus 8 per 128.  A simulation of ds_read_b128 /
+// One spare slot per 8 elements plus 8 per 128.  A simulation of ds_read_b128 /
 // ds_write_b128 with their real lane groups (MI355X_MICROARCH.md LDS table: reads are served in 4 groups of 16
 // NON-contiguous lanes, writes in 8 x 8) gives this padding 1.5x the conflict-free LDS cycles on every
 // radix-16/8/4/2 pass of N = 1024 ... 4096 - the 0.31 = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE measured for all
 // three instantiations (profiles/r01_k5_lds_pmc.csv): a padded unit-stride run is no longer aligned to the bank
-// rows the lane groups assume.
-// K5_SWZ = 1: an XOR swizzle of the 16-byte slot inside its 256-byte bank row by parities of the row index
-// x = i >> 4 (bit0 = x0^x5, bit1 = x0^x1, bit2 = x0^x2^x4, bit3 = x0^x3^x4), found by hill-climbing in that
-// simulation: every pass conflict-free.  Measured: the counter ratio falls to 0.21 / 0.17 / 0.07 (belt / Bluestein
-// classes; the rest is the fold, cell and Hermitian stages), the kernel gets 0.7 ms SLOWER (26.9 -> 27.6 ms, A/B on
-// one box): the ring FFT is bound by its FP64 VALU work, not by the LDS array, and the swizzle costs four more
-// integer operations per element than the padding.  Kept as a switch; the flat-sky line FFT (flatsky.hip), whose
-// radix-4 stages ARE LDS-bound, ships its own swizzle.
-#ifndef K5_SWZ
-#define K5_SWZ 0
-#endif
-#if K5_SWZ
-__host__ __device__ static inline int fpad(int i) {
-    const int x = i >> 4;
-    int s = (0 - (x & 1)) & 15;        // x0 -> all four bits
-    s ^= (x & 14);                     // x1, x2, x3 -> bits 1, 2, 3
-    s ^= (0 - ((x >> 4) & 1)) & 12;    // x4 -> bits 2, 3
-    s ^= (x >> 5) & 1;                 // x5 -> bit 0
-    return i ^ s;
-}
-__host__ __device__ static inline int fpad_len(int n) { return (n + 15) & ~15; }
-#define K5_CH_SKEW 4                   // channel buffers start a quarter bank row apart
-#else
+// rows the lane groups assume.  (A conflict-free XOR swizzle was measured 0.7 ms SLOWER, 26.9 -> 27.6 ms: the ring FFT
+// is bound by its FP64 VALU work, not by the LDS array - HISTORY.md; the flat-sky line FFT (flatsky.hip), whose
+// radix-4 stages ARE LDS-bound, ships its own swizzle.)
 __host__ __device__ static inline int fpad(int i) { return i + (i >> 3) + ((i >> 7) << 3); }
 __host__ __device__ static inline int fpad_len(int n) { return fpad(n); }
-#define K5_CH_SKEW 1
-#endif
+#define K5_CH_SKEW 1                   // channel buffers start one slot apart
 
 // e^{+2 pi i idx/pmax} from the half-circle table in HBM, tw[k] = e^{+2 pi i k/pmax}, k < pmax/2
 __device__ static inline double2 tw_global(const double2 *__restrict__ tw, int pmax, int idx) {
@@ -275,35 +251,10 @@ __device__ static inline double2 tw_global(const double2 *__restrict__ tw, int p
     if (idx >= hp) w = make_double2(-w.x, -w.y);
     return w;
 }
-// The kernels look twiddles up in a two-level LDS table instead: tl[lo] = e^{2 pi i lo/pmax}, lo < 64, and
-// tl[64 + hi] = e^{2 pi i 64 hi/pmax}; e^{2 pi i idx/pmax} = tl[idx & 63] * tl[64 + (idx >> 6)].  A twiddle
-// fetched from HBM inside an FFT pass made every pass wait (vmcnt is in-order) for the register prefetch of
-// the NEXT ring's cells issued just before it - the whole HBM latency was exposed once per ring.
-// Measured at cfg 3: the extra LDS reads + complex multiply and the higher register pressure cost more
-// (belt class 13.2 -> 15.8 ms) than the exposed latency they remove, so the switch is OFF; kept for the record.
-#ifndef K5_LDS_TW
-#define K5_LDS_TW 0
-#endif
-#if K5_LDS_TW
-#define TWL_ENTRIES(pmax) (64 + ((pmax) >= 64 ? (pmax) / 64 : 1))
-#else
-#define TWL_ENTRIES(pmax) 0
-#endif
-__device__ static inline void twl_fill(double2 *tl, const double2 *__restrict__ tw, int pmax) {
-    const int nhi = pmax >= 64 ? pmax / 64 : 1;
-    for (int i = threadIdx.x; i < 64 + nhi; i += blockDim.x) {
-        const int idx = i < 64 ? (i < pmax ? i : 0) : 64 * (i - 64);
-        tl[i] = tw_global(tw, pmax, idx);
-    }
-    __syncthreads();
-}
+// (A two-level LDS table of the twiddles was measured slower, belt class 13.2 -> 15.8 ms: HISTORY.md.)
 template <int SIGN>
-__device__ static inline double2 tw_get(const double2 *tl, int pmax, int idx) {
-#if K5_LDS_TW
-    double2 w = cmul(tl[idx & 63], tl[64 + (idx >> 6)]);
-#else
-    double2 w = tw_global(tl, pmax, idx);
-#endif
+__device__ static inline double2 tw_get(const double2 *tw, int pmax, int idx) {
+    double2 w = tw_global(tw, pmax, idx);
     if (SIGN < 0) w.y = -w.y;
     return w;
 }
@@ -334,27 +285,6 @@ __device__ __forceinline__ static void fft_pass(double2 *buf, int bstride, int n
 #pragma unroll
         for (int b = 1; b < NB; b++) wp[b] = cmul(wp[b - 1], wp[b - 1]);
         auto twiddle_all = [&]() {
-#if K5_TW_4X4
-            if (R == 16) {
-                // w^r = (w^4)^a w^c for r = 4a + c: 5 multiplies for (w^2, w^3, w^4, w^8, w^12) + 24 to apply them,
-                // instead of 3 squarings + 32 selected binary powers (6 complex multiplies fewer per butterfly)
-                const double2 w1 = wp[0], w2 = wp[1], w4 = wp[2], w8 = wp[3];
-                const double2 w3 = cmul(w2, w1), w12 = cmul(w8, w4);
-#pragma unroll
-                for (int a = 0; a < 4; a++) {
-                    x[(4 * a + 1) % R] = cmul(x[(4 * a + 1) % R], w1);
-                    x[(4 * a + 2) % R] = cmul(x[(4 * a + 2) % R], w2);
-                    x[(4 * a + 3) % R] = cmul(x[(4 * a + 3) % R], w3);
-                }
-#pragma unroll
-                for (int c = 0; c < 4; c++) {
-                    x[(4 + c) % R] = cmul(x[(4 + c) % R], w4);
-                    x[(8 + c) % R] = cmul(x[(8 + c) % R], w8);
-                    x[(12 + c) % R] = cmul(x[(12 + c) % R], w12);
-                }
-                return;
-            }
-#endif
 #pragma unroll
             for (int r = 1; r < R; r++) {
 #pragma unroll
@@ -375,14 +305,9 @@ __device__ __forceinline__ static void fft_pass(double2 *buf, int bstride, int n
     __syncthreads();
 }
 
-#ifndef K5_TW_4X4
-#define K5_TW_4X4 0   // 1: radix-16 twiddles as (w^4)^a w^c, 29 complex multiplies per butterfly instead of 35 - measured: no difference (the passes are latency-bound, two waves per SIMD)
-#endif
-#ifndef K5_RADIX
-#define K5_RADIX 16    // largest butterfly: 16 -> 512-thread workgroups; 8 -> 1024 threads (<= 128 VGPRs: measured 30 % slower, spills)
-#endif
-#define K5_LOGR (K5_RADIX == 16 ? 4 : 3)
-#define K5_THREADS (K5_RADIX == 16 ? 512 : 1024)
+#define K5_RADIX 16    // largest butterfly (radix 8 with 1024-thread workgroups: measured 30 % slower, spills)
+#define K5_LOGR 4
+#define K5_THREADS 512
 // pass schedule for N = 2^k: radix K5_RADIX while it fits, then the remainder
 // `postmul` (optional) is multiplied into the output of the LAST pass, indexed by storage position
 template <int SIGN>
@@ -393,7 +318,7 @@ __device__ __forceinline__ static void fft_dif(double2 *buf, int bstride, int nc
         fft_pass<K5_RADIX, SIGN, false>(buf, bstride, nch, N, Ls, tw, pmax, Ls == K5_RADIX ? postmul : nullptr);
         Ls >>= K5_LOGR;
     }
-    if (K5_RADIX == 16 && Ls == 8) fft_pass<8, SIGN, false>(buf, bstride, nch, N, Ls, tw, pmax, postmul);
+    if (Ls == 8) fft_pass<8, SIGN, false>(buf, bstride, nch, N, Ls, tw, pmax, postmul);
     else if (Ls == 4) fft_pass<4, SIGN, false>(buf, bstride, nch, N, Ls, tw, pmax, postmul);
     else if (Ls == 2) fft_pass<2, SIGN, false>(buf, bstride, nch, N, Ls, tw, pmax, postmul);
 }
@@ -403,7 +328,7 @@ __device__ __forceinline__ static void fft_dit(double2 *buf, int bstride, int nc
     int rem = N;
     while (rem >= K5_RADIX) rem >>= K5_LOGR;  // remainder radix handled first (it was last in DIF)
     int Ls = rem;
-    if (K5_RADIX == 16 && rem == 8) fft_pass<8, SIGN, true>(buf, bstride, nch, N, Ls, tw, pmax);
+    if (rem == 8) fft_pass<8, SIGN, true>(buf, bstride, nch, N, Ls, tw, pmax);
     else if (rem == 4) fft_pass<4, SIGN, true>(buf, bstride, nch, N, Ls, tw, pmax);
     else if (rem == 2) fft_pass<2, SIGN, true>(buf, bstride, nch, N, Ls, tw, pmax);
     if (rem == 1) Ls = 1;
@@ -491,7 +416,7 @@ __device__ __forceinline__ static void fft_dit_last_out(const double2 *buf, int 
         double2 x[R];
 #pragma unroll
         for (int r = 0; r < R; r++) x[r] = cbuf[fpad(j + r * q)];
-        constexpr int NB = R == 16 ? 4 : 3;
+        constexpr int NB = K5_LOGR;
         double2 wp[NB];
         wp[0] = tw_get<SIGN>(tw, pmax, j * twstep);
 #pragma unroll
@@ -503,9 +428,6 @@ __device__ __forceinline__ static void fft_dit_last_out(const double2 *buf, int 
                 if (r & (1 << b)) x[r] = cmul(x[r], wp[b]);
         }
         DftR<R, SIGN>::run(x);
-#if K5_ABLATE == 2
-        if (x[0].x == 1.2345e300)
-#endif
         if (ch0 + ch < nnu) {
             double *out = maps + (size_t)(ch0 + ch) * npix + start;
 #pragma unroll
@@ -524,12 +446,9 @@ __device__ __forceinline__ static void fft_dit_last_out(const double2 *buf, int 
 #ifndef K5_MC_BLU4
 #define K5_MC_BLU4 2   // prefetched cells of the four-channel Bluestein instantiation (2 spills 11 VGPRs)
 #endif
-#define K5_MC (K5_RADIX == 16 ? 4 : 2)  // cells per thread held in registers for the next item (rest read in place)
+#define K5_MC 4  // cells per thread held in registers for the next item (rest read in place)
 #ifndef K5_STAMPS
 #define K5_STAMPS 0  // diagnostic build: s_memtime phase breakdown
-#endif
-#ifndef K5_ABLATE
-#define K5_ABLATE 0  // diagnostic builds (make k5ablate; wrong results, timing only): 1 no FFT, 2 no pixel stores, 3 no cell loads
 #endif
 #if K5_STAMPS
 __device__ unsigned long long g_k5_stamps[8];
@@ -562,9 +481,20 @@ int sht_ringfft_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sh
 int sht_blu3_tables(corahip_ctx *ctx, corahip_sht_plan *p, int64_t total);
 // creates ctx->stream2 and the fork / join events on first use
 int sht_second_stream(corahip_ctx *ctx);
-// belt + largest Bluestein class side by side on two streams (sht_ringfft_ct.hip): *took = both launched
-int sht_ringfft_ct_pair(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &belt,
-                        const corahip_sht_plan::ring_class &cap, const double *inter, int G, int nnu, double *maps, bool *took);
+// Guard of the per-class launch loops of sht_ringfft / sht_ringana, which switch ctx->stream per launch: puts the
+// caller's stream back on every exit path, and makes it wait for whatever was put on the second one (an error return in
+// the middle of the loop must not leave class kernels running on stream2 unordered against the caller's next
+// launches, or against its freeing of `inter` / `maps`).
+struct StreamRestore {
+    corahip_ctx *c;
+    hipStream_t s;
+    bool forked = false;
+    ~StreamRestore() {
+        c->stream = s;
+        if (forked && (hipEventRecord(c->ev_join, c->stream2) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess))
+            (void)hipStreamSynchronize(c->stream2);
+    }
+};
 // K5^T: maps -> weighted G_m cells for nnu_pad8 channels (nnu present in `maps`)
 int sht_ringana_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c, const double *maps, int nvalid,
                    int nnu_pad, const double *ring_w, int G, double *inter, bool *took);

@@ -5,15 +5,12 @@
 #ifndef LEG_ST_UNROLL
 #define LEG_ST_UNROLL 1   // unroll factor of the stage loop (3 would make the LDS ring offsets immediates)
 #endif
-#ifndef LEG_RING_BLOCKS
-#define LEG_RING_BLOCKS 0   // (measured neutral: 56.6 vs 56.5 ms, off) 1: a wave takes CONSECUTIVE rings of the tile (its own first contributing l), the two waves of a SIMD complementary blocks; 0: rings interleaved over the waves
-#endif
 #ifndef LEG_MS_UNROLL
 #define LEG_MS_UNROLL 7   // (= LEG_KT / 8 at the shipped stage length; only the rolled head / tail stages use it) macro-step loop of a stage fully unrolled (loop counters and pointer increments become immediates): 71.0 -> 69.5 ms; factors 2 and 3: no change
 #endif
 
 #ifndef LEG_STAMPS
-#define LEG_STAMPS 0      // diagnostic build (make k4stamps): s_memtime per phase of the item loop, summed over the workgroups' first waves
+#define LEG_STAMPS 0      // diagnostic build (make ab ... DEFS=-DLEG_STAMPS=1): s_memtime per phase of the item loop, summed over the workgroups' first waves
 #endif
 #if LEG_STAMPS
 __device__ unsigned long long g_leg_stamps[16];
@@ -78,13 +75,9 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
     const unsigned lds_base_bytes = (unsigned)(size_t)(__attribute__((address_space(3))) double *)lds;
     const bool odd_lane = lane & 1;
 
-    // Rings of a tile -> waves.  Interleaved (ring = 8 j + wave, round 1) every wave sees the tile's whole range of first
-    // contributing l, i.e. every wave starts at the tile's EARLIEST ring and multiplies zeros for the others.  With
-    // consecutive blocks a wave starts at its own block's first l (its skip tests are per wave); so that the SIMDs
-    // still finish a stage together, the two waves of a SIMD (waves w and w + 4) take complementary blocks (b, 7 - b):
-    // the first l grows monotonically over the tile, so every SIMD gets the same total.
+    // Rings of a tile -> waves: interleaved (ring = 8 j + wave), so every wave sees the tile's whole range of first
+    // contributing l.  (Consecutive blocks of rings per wave were measured neutral, 56.6 vs 56.5 ms: HISTORY.md.)
     auto ring_in_tile = [&](int j) {     // j-th ring (0 .. 16 RT - 1) of this wave
-        if (LEG_RING_BLOCKS && LEG_WAVES == 8) return (wave < 4 ? wave : 11 - wave) * (16 * RT) + j;
         return j * LEG_WAVES + wave;
     };
     // Persistent workgroups.  Work item = (m, column group, ring tile); consecutive items are the ring
@@ -352,11 +345,7 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
                         const double srecv = __shfl_xor(odd_lane ? s0 : s1, 1);
                         const int rr = odd_lane ? r1 : r0;
                         const int ro = cur_rtile * TRINGS + ring_in_tile(kq + 4 * rr + 16 * q);
-#if LEG_ABLATE == 4  // diagnostic: no epilogue stores (unless a value is absurd: keeps the arithmetic alive)
-                        if (ro < npair && n0 == 1.2345e300) {
-#else
                         if (ro < npair) {
-#endif
                             const double2 nv = odd_lane ? make_double2(nrecv, n1) : make_double2(n0, nrecv);
                             *reinterpret_cast<double2 *>(inter + (((size_t)ro * G + g) * L + cur_m) * 8 + cv) = nv;
                             const int rs = nring - 1 - ro;

@@ -311,16 +311,11 @@ __global__ void __launch_bounds__(256)
 bluestein_table_kernel(const int32_t *__restrict__ blu_P, const int64_t *__restrict__ boff,
                        const int64_t *__restrict__ foff, double2 *__restrict__ chirp,
                        double2 *__restrict__ filt, const double2 *__restrict__ tw, int pmax, int tl_off) {
-    extern __shared__ __attribute__((aligned(16))) double2 fbuf[];   // [fpad_len(maxlen) + 1] then the twiddle table
+    extern __shared__ __attribute__((aligned(16))) double2 fbuf[];   // [fpad_len(maxlen) + 1]
+    (void)tl_off;   // (size of fbuf; nothing lies behind it)
     const int i = blockIdx.x + 1;
     const int P = blu_P[i - 1];
     if (P == 0) return;
-#if K5_LDS_TW
-    double2 *tl = fbuf + tl_off;
-    twl_fill(tl, tw, pmax);
-#else
-    const double2 *tl = tw;
-#endif
     const int h = 2 * i;
     double2 *b = chirp + boff[i - 1];
     for (int j = threadIdx.x; j < fpad_len(P); j += blockDim.x) fbuf[j] = make_double2(0.0, 0.0);
@@ -334,7 +329,7 @@ bluestein_table_kernel(const int32_t *__restrict__ blu_P, const int64_t *__restr
         if (j > 0) fbuf[fpad(P - j)] = make_double2(c, -s);
     }
     __syncthreads();
-    fft_dif<-1>(fbuf, 0, 1, P, tl, pmax);
+    fft_dif<-1>(fbuf, 0, 1, P, tw, pmax);
     double2 *f = filt + foff[i - 1];
     for (int j = threadIdx.x; j < P; j += blockDim.x) f[j] = fbuf[fpad(j)];
 }
@@ -444,21 +439,14 @@ int corahip_sht_plan_k4_mfma_count(corahip_ctx *ctx, const corahip_sht_plan *p, 
     if (it == p->k4_macro_steps.end()) {
         HIP_TRY(hipSetDevice(ctx->device));
         unsigned long long *d_n = nullptr, h_n = 0;
-        HIP_TRY(hipMalloc((void **)&d_n, 2 * sizeof(h_n)));
-        HIP_TRY(hipMemsetAsync(d_n, 0, 2 * sizeof(h_n), ctx->stream));
-        static const bool dbg = getenv("CORAHIP_K4_COUNT_DEBUG") != nullptr;   // diagnostics: share of the steady-state stages
+        HIP_TRY(hipMalloc((void **)&d_n, sizeof(h_n)));
+        HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(h_n), ctx->stream));
         const int ntile = (p->npair + LEG_RINGS * RT - 1) / (LEG_RINGS * RT);
         const long total = (long)p->L * ntile * LEG_WAVES;
-        k4_count_kernel<<<(unsigned)((total + 255) / 256), 256, 0, ctx->stream>>>(p->lmax, p->npair, RT, p->d_lstart, p->d_lmin, d_n, dbg ? d_n + 1 : nullptr);
+        k4_count_kernel<<<(unsigned)((total + 255) / 256), 256, 0, ctx->stream>>>(p->lmax, p->npair, RT, p->d_lstart, p->d_lmin, d_n, nullptr);
         LAUNCH_CHECK();
         HIP_TRY(hipMemcpyAsync(&h_n, d_n, sizeof(h_n), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (dbg) {
-            unsigned long long h_c = 0;
-            HIP_TRY(hipMemcpy(&h_c, d_n + 1, sizeof(h_c), hipMemcpyDeviceToHost));
-            fprintf(stderr, "K4 macro-steps per column group (RT %d): %llu executed, %llu of them in steady-state stages (%.3f)\n", RT,
-                    h_n, h_c, (double)h_c / (double)std::max<unsigned long long>(h_n, 1));
-        }
         (void)hipFree(d_n);
         it = const_cast<corahip_sht_plan *>(p)->k4_macro_steps.emplace(RT, (uint64_t)h_n).first;
     }
@@ -650,7 +638,7 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
         HIP_TRY(hipMalloc((void **)&p->d_bfilt, sizeof(double2) * std::max<int64_t>(1, nf)));
         if (nside > 1) {
             const int tl_off = fpad_len(maxlen) + 1;
-            const size_t shm = sizeof(double2) * (size_t)(tl_off + TWL_ENTRIES(p->pmax));
+            const size_t shm = sizeof(double2) * (size_t)tl_off;
             HIP_TRY(hipFuncSetAttribute((const void *)bluestein_table_kernel,
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
             bluestein_table_kernel<<<nside - 1, 256, shm, s>>>(p->d_blu_P, p->d_blu_boff, p->d_blu_foff,
@@ -678,9 +666,9 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             // it still holds 2 h - 1, and P = 8192 itself (their 16 x 16 x 32 schedule differs from the generic passes)
             const int P3 = 3 * (P / 4);
             int alt = 0;
-            if (P == 4096 && 2560 >= 2 * h - 1 && !getenv("CORAHIP_K5_NO57")) alt = 2560;          // 5 * 2^9
+            if (P == 4096 && 2560 >= 2 * h - 1) alt = 2560;          // 5 * 2^9
             else if ((P3 == 1536 || P3 == 3072 || P3 == 6144) && P3 >= 2 * h - 1) alt = P3;
-            else if (P == 4096 && 3584 >= 2 * h - 1 && !getenv("CORAHIP_K5_NO57")) alt = 3584;     // 7 * 2^9
+            else if (P == 4096 && 3584 >= 2 * h - 1) alt = 3584;     // 7 * 2^9
             else if (P == 8192) alt = P;
             if (alt) {
                 p->h_blu3_P[i - 1] = alt;
@@ -716,8 +704,7 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             }
             by_len[P].push_back(r);
         }
-        size_t lds_budget = 160 * 1024;
-        if (getenv("CORAHIP_K5_LDS_KB")) lds_budget = (size_t)atoi(getenv("CORAHIP_K5_LDS_KB")) * 1024;
+        const size_t lds_budget = 160 * 1024;
         for (auto &kv : by_len) {
             corahip_sht_plan::ring_class c;
             c.P = kv.first > 0 ? kv.first / 8 : 0;
@@ -728,9 +715,8 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             c.N = kv.first < 0 ? -kv.first : 0;
             c.bstride = fpad_len(c.P ? c.P : 2 * nside + 1) + K5_CH_SKEW;
             c.nch = 4;
-            const size_t tl_bytes = sizeof(double2) * TWL_ENTRIES(p->pmax);   // LDS twiddle table behind the buffers
-            while (c.nch > 1 && (size_t)c.nch * c.bstride * sizeof(double2) + tl_bytes > lds_budget) c.nch >>= 1;
-            if ((size_t)c.nch * c.bstride * sizeof(double2) + tl_bytes > 160 * 1024) {
+            while (c.nch > 1 && (size_t)c.nch * c.bstride * sizeof(double2) > lds_budget) c.nch >>= 1;
+            if ((size_t)c.nch * c.bstride * sizeof(double2) > lds_budget) {
                 corahip_set_error("nside %d: ring FFT of length %d does not fit in LDS", nside, c.bstride);
                 return CORAHIP_ENOMEM;
             }

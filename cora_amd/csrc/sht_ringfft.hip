@@ -2,10 +2,6 @@
 // FFT -> weighted, phased G_m cells), with their per-class launch loops.  The LDS FFT passes are in sht_internal.h.
 #include "sht_internal.h"
 
-#ifndef K5_XCD_PAIR
-#define K5_XCD_PAIR 1
-#endif
-
 // Persistent workgroups: each loops over work items (ring of the class, NCH consecutive channels),
 // all NCH channels transformed together in LDS.  The F_m cells of the NEXT item are fetched into
 // registers while the current item is in its FFT passes, so HBM reads overlap the FP64 work and the
@@ -24,19 +20,13 @@ ringfft_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
     // cells per thread prefetched into registers for the next item (the rest are read in place): the Bluestein
     // instantiations need the registers for the fused filter pass (4 cells made them spill 66 VGPRs)
     constexpr int MC = BLU ? (NCH == 4 ? K5_MC_BLU4 : (K5_MC > 2 ? 2 : K5_MC)) : K5_MC;
-    extern __shared__ __attribute__((aligned(16))) double2 sm[];  // [NCH][bstride], then the twiddle table
+    extern __shared__ __attribute__((aligned(16))) double2 sm[];  // [NCH][bstride]
     const int tid = threadIdx.x, nt = blockDim.x;
     const int L = lmax + 1;
     const int ngrp = (nnu + NCH - 1) / NCH;
     const int nitems = nlist * ngrp;
     double *smd = reinterpret_cast<double *>(sm);
-#if K5_LDS_TW
-    double2 *tl = sm + (size_t)NCH * bstride;
-    twl_fill(tl, tw_hbm, pmax);
-    const double2 *tw = tl;   // every twiddle below comes from LDS
-#else
     const double2 *tw = tw_hbm;
-#endif
 
     // register prefetch of the cells m = tid + k nt, k < MC, of one item
     struct cell_t {
@@ -50,10 +40,6 @@ ringfft_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
     };
     auto load_cell = [&](const double *cell, int m) {
         cell_t c;
-#if K5_ABLATE == 3
-        for (int q = 0; q < NCH; q++) { c.re[q] = 1.0 + m; c.im[q] = 0.5; }
-        return c;
-#endif
         if (NCH == 4) {
             const double4 a = *reinterpret_cast<const double4 *>(cell + (unsigned)m * 8u);
             const double4 b = *reinterpret_cast<const double4 *>(cell + (unsigned)m * 8u + 4u);
@@ -92,9 +78,9 @@ ringfft_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
 #endif
     // With NCH < 4 the 4 / NCH items of one ring that share every 64-byte cell are consecutive.  Round-robin dispatch
     // puts consecutive workgroups on different XCDs, each L2 then fetches the cells for itself; workgroups b and
-    // b + 8 (same XCD, resident together) take such neighbours instead (K5_XCD_PAIR).
+    // b + 8 (same XCD, resident together) take such neighbours instead.
     constexpr int SH = NCH == 2 ? 1 : (NCH == 1 ? 2 : 0);             // log2 of the items sharing a cell
-    const bool xcd_pair = K5_XCD_PAIR && SH > 0 && (nitems & ((8 << SH) - 1)) == 0 && (gridDim.x & ((8 << SH) - 1)) == 0;
+    const bool xcd_pair = SH > 0 && (nitems & ((8 << SH) - 1)) == 0 && (gridDim.x & ((8 << SH) - 1)) == 0;
     auto remap = [&](int v) {
         if (!xcd_pair) return v;
         const int slot = v >> 3, xcd = v & 7;
@@ -227,17 +213,12 @@ ringfft_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
         K5STAMP(t_z);
 
         if (!BLU || P == 0) {
-#if K5_ABLATE != 1
             fft_dif<1>(sm, bstride, NCH, h, tw, pmax);
-#endif
             K5STAMP(t_fft);
             for (int j = tid; j < h; j += nt) {
                 const int pos = fpad(fft_dif_pos(j, h));
 #pragma unroll
                 for (int c = 0; c < NCH; c++) {
-#if K5_ABLATE == 2
-                    if (sm[(size_t)c * bstride + pos].x == 1.2345e300)
-#endif
                     if (ch0 + c < nnu)
                         *reinterpret_cast<double2 *>(maps + (size_t)(ch0 + c) * npix + start + 2 * j) =
                             sm[(size_t)c * bstride + pos];
@@ -246,11 +227,7 @@ ringfft_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
         } else {
             const double2 *f = filt + foff[icap - 1];
             const double invP = 1.0 / (double)P;
-#if K5_ABLATE == 1
-            if (false) {
-#else
             if (P >= K5_RADIX * K5_RADIX) {
-#endif
                 // >= 3 passes each way: the filter step and the final chirp/store are fused into the passes
                 const int rl = fft_dif_head<-1>(sm, bstride, NCH, P, tw, pmax);
                 K5STAMP(t_fft);      // stamps build: forward passes but the last
@@ -265,18 +242,13 @@ ringfft_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
                 K5STAMP(t_out);      // last inverse pass + chirp + pixel stores
                 continue;
             }
-#if K5_ABLATE != 1
             fft_dif<-1>(sm, bstride, NCH, P, tw, pmax, f);  // filter multiplied in by the last pass
             fft_dit<1>(sm, bstride, NCH, P, tw, pmax);
-#endif
             K5STAMP(t_fft);
             for (int j = tid; j < h; j += nt) {
                 const double2 bj = bch[j];
 #pragma unroll
                 for (int c = 0; c < NCH; c++) {
-#if K5_ABLATE == 2
-                    if (bj.x == 1.2345e300)
-#endif
                     if (ch0 + c < nnu) {
                         double2 zv = cmul(sm[(size_t)c * bstride + fpad(j)], bj);
                         zv.x *= invP;
@@ -323,15 +295,9 @@ ringana_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
                const double2 *__restrict__ chirp, const double2 *__restrict__ filt, int bstride,
                const int32_t *__restrict__ mcut, const double *__restrict__ ring_w, int nvalid) {
     // nnu: channels incl. padding (every cell K4^T reads gets written); nvalid: channels present in `maps`
-    extern __shared__ __attribute__((aligned(16))) double2 sm[];  // [NCH][bstride], then the twiddle table
+    extern __shared__ __attribute__((aligned(16))) double2 sm[];  // [NCH][bstride]
     const int tid = threadIdx.x, nt = blockDim.x;
-#if K5_LDS_TW
-    double2 *tl = sm + (size_t)NCH * bstride;
-    twl_fill(tl, tw_hbm, pmax);
-    const double2 *tw = tl;
-#else
     const double2 *tw = tw_hbm;
-#endif
     const int L = lmax + 1;
     const int ngrp = (nnu + NCH - 1) / NCH;
     const int nitems = nlist * ngrp;
@@ -356,9 +322,9 @@ ringana_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
             }
         }
     };
-    // (K5_XCD_PAIR as in ringfft_kernel: the items writing the two halves of a 64-byte cell go to one XCD)
+    // (as in ringfft_kernel: the items writing the two halves of a 64-byte cell go to one XCD)
     constexpr int SH = NCH == 2 ? 1 : (NCH == 1 ? 2 : 0);
-    const bool xcd_pair = K5_XCD_PAIR && SH > 0 && (nitems & ((8 << SH) - 1)) == 0 && (gridDim.x & ((8 << SH) - 1)) == 0;
+    const bool xcd_pair = SH > 0 && (nitems & ((8 << SH) - 1)) == 0 && (gridDim.x & ((8 << SH) - 1)) == 0;
     auto remap = [&](int v) {
         if (!xcd_pair) return v;
         const int slot = v >> 3, xcd = v & 7;
@@ -492,34 +458,13 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
         StageTimer t(ctx, "ringfft");
         const int G = nnu_chunk_pad / 4;
         static const bool class_times = getenv("CORAHIP_K5_TIMES") != nullptr;   // diagnostics: per-class ms on stderr
-        // the belt and the largest Bluestein class run side by side (two streams, co-resident workgroups)
-        const corahip_sht_plan::ring_class *pb = nullptr, *pc = nullptr;
-        for (const auto &c : p->classes) {
-            if (c.P == 0 && c.N > 0) pb = &c;
-            if (c.P == 4096 && c.P3 == 0) pc = &c;
-        }
-        bool paired = false;
-        if (pb && pc && !class_times) {
-            const int rcp = sht_ringfft_ct_pair(ctx, p, *pb, *pc, inter, G, nnu_valid, maps, &paired);
-            if (rcp) return rcp;
-        }
         // The class launches alternate between two streams: every class is a persistent grid that fills the chip, so the
         // two kernels in flight run one after the other EXCEPT for their tails - the workgroups of the next class start on
-        // the CUs the finishing one frees (12 launches, 0.1-0.3 ms of tail each on one stream).  CORAHIP_K5_ONE_STREAM=1
-        // or the per-class timing switch keep everything on the context's stream.
-        static const bool one_stream = getenv("CORAHIP_K5_ONE_STREAM") != nullptr;
-        const bool two = !one_stream && !class_times && !K5_STAMPS && p->classes.size() > 1;
+        // the CUs the finishing one frees (12 launches, 0.1-0.3 ms of tail each on one stream).  The per-class timing
+        // switch keeps everything on the context's stream.
+        const bool two = !class_times && !K5_STAMPS && p->classes.size() > 1;
         hipStream_t const main_stream = ctx->stream;
-        struct Restore {          // ctx->stream is switched per launch below: back to the caller's on every exit path -
-            corahip_ctx *c;       // and the caller's stream waits for whatever was put on the second one (an error return
-            hipStream_t s;        // in the middle of the loop must not leave class kernels running on stream2 unordered
-            bool forked = false;  // against the caller's next launches, or against its freeing of `inter` / `maps`)
-            ~Restore() {
-                c->stream = s;
-                if (forked && (hipEventRecord(c->ev_join, c->stream2) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess))
-                    (void)hipStreamSynchronize(c->stream2);
-            }
-        } restore{ctx, main_stream};
+        StreamRestore restore{ctx, main_stream};   // (ctx->stream is switched per launch below)
         if (two) {
             int rc2 = sht_second_stream(ctx);
             if (rc2) return rc2;
@@ -529,7 +474,6 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
         }
         int launch_no = 0;
         for (const auto &c : p->classes) {
-            if (paired && (&c == pb || &c == pc)) continue;
             if (two) ctx->stream = (launch_no++ & 1) ? ctx->stream2 : main_stream;   // (restored below; every launch of the loop uses ctx->stream)
             hipEvent_t ce0 = nullptr, ce1 = nullptr;
             if (class_times) {
@@ -539,8 +483,8 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
             }
             bool took = false;   // compile-time kernel for this class?
             const int rct = sht_ringfft_ct(ctx, p, c, inter, G, nnu_valid, maps, &took);
-            if (rct) return rct;   // (Restore puts the caller's stream back)
-            const size_t shm = sizeof(double2) * ((size_t)c.nch * c.bstride + TWL_ENTRIES(p->pmax));
+            if (rct) return rct;   // (StreamRestore puts the caller's stream back)
+            const size_t shm = sizeof(double2) * (size_t)c.nch * c.bstride;
             const long nitems = (long)c.count * ((nnu_valid + c.nch - 1) / c.nch);
             const int per_cu = std::max<int>(1, (int)((160 * 1024) / std::max<size_t>(shm, 1)));
             const int k5_threads = c.threads ? c.threads : K5_THREADS;
@@ -603,21 +547,11 @@ int sht_ringana(corahip_ctx *ctx, const corahip_sht_plan *p, const double *maps,
     const int k5_threads = K5_THREADS;
     // The class launches alternate between two streams, as in sht_ringfft: every class is a persistent grid that fills
     // the chip, so two kernels in flight run one after the other except for their tails - the workgroups of the next
-    // class start on the CUs the finishing one frees (CORAHIP_K5_ONE_STREAM=1: everything on the context's stream).
-    static const bool one_stream = getenv("CORAHIP_K5_ONE_STREAM") != nullptr;
+    // class start on the CUs the finishing one frees (the per-class timing switch keeps everything on the context's stream).
     static const bool class_times = getenv("CORAHIP_K5_TIMES") != nullptr;   // diagnostics: per-class ms on stderr
-    const bool two = !one_stream && !class_times && p->classes.size() > 1;
+    const bool two = !class_times && p->classes.size() > 1;
     hipStream_t const main_stream = ctx->stream;
-    struct Restore {          // (as in sht_ringfft: the caller's stream back, and joined with the second one, on every exit path)
-        corahip_ctx *c;
-        hipStream_t s;
-        bool forked = false;
-        ~Restore() {
-            c->stream = s;
-            if (forked && (hipEventRecord(c->ev_join, c->stream2) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess))
-                (void)hipStreamSynchronize(c->stream2);
-        }
-    } restore{ctx, main_stream};
+    StreamRestore restore{ctx, main_stream};
     if (two) {
         int rc2 = sht_second_stream(ctx);
         if (rc2) return rc2;
@@ -637,7 +571,7 @@ int sht_ringana(corahip_ctx *ctx, const corahip_sht_plan *p, const double *maps,
         bool took = false;   // compile-time kernel for this class?
         const int rct = sht_ringana_ct(ctx, p, c, maps, nnu, nnu_pad8, ring_w, G, inter, &took);
         if (rct) return rct;
-        const size_t shm = sizeof(double2) * ((size_t)c.nch * c.bstride + TWL_ENTRIES(p->pmax));
+        const size_t shm = sizeof(double2) * (size_t)c.nch * c.bstride;
         const long nitems = (long)c.count * ((nnu_pad8 + c.nch - 1) / c.nch);
         dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * 4));
 #define RINGANA_LAUNCH(NCH)                                                                                      \

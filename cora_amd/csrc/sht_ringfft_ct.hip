@@ -24,10 +24,9 @@
 // 4 for ds_read_b128, MI355X_MICROARCH.md section LDS), hence the count of write passes above.
 #include "sht_internal.h"
 
-static_assert(K5_SWZ == 0, "the compile-time kernels assume the padded LDS layout");
 #define CT_T 512
 #ifndef CT_STAMPS
-#define CT_STAMPS 0   // diagnostic build (make k5ctstamps): s_memtime per phase of the Bluestein kernel, summed over waves
+#define CT_STAMPS 0   // diagnostic build (make ab ... DEFS=-DCT_STAMPS=1): s_memtime per phase of the Bluestein kernel, summed over waves
 #endif
 #if CT_STAMPS
 __device__ unsigned long long g_ct_stamps[12];
@@ -167,7 +166,7 @@ struct FrontEnd {
     }
 };
 
-// blockIdx -> item with the workgroups of one XCD taking the items that share 64-byte cells (K5_XCD_PAIR of
+// blockIdx -> item with the workgroups of one XCD taking the items that share 64-byte cells (as in
 // sht_ringfft.hip)
 template <int NCH>
 __device__ __forceinline__ static int ct_remap(int v, int nitems) {
@@ -760,18 +759,14 @@ ringana_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
 // host side: launch one class with the compile-time kernel if there is one for it
 // ------------------------------------------------------------------------------------
 template <int N, int NCH, int MC, int T>
-static int launch_direct(corahip_ctx *ctx, hipStream_t stream, int wg_per_cu, const corahip_sht_plan *p,
+static int launch_direct(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_plan *p,
                          const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps) {
     constexpr int PK = K5_PK_DIRECT;
     constexpr int BS = fpc(N) + 1 + K5_CH_SKEW;
     const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu + NCH - 1) / NCH);
-    const int per_cu = wg_per_cu > 0 ? wg_per_cu : std::max<int>(1, (int)((160 * 1024) / shm));
+    const int per_cu = std::max<int>(1, (int)((160 * 1024) / shm));
     dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
-    // diagnostics (overlap table): the belt on fewer workgroups than CUs - it is HBM-bound, how many
-    // CUs does it need to stream at its rate?
-    static const char *belt_wgs = getenv("CORAHIP_K5_BELT_WGS");
-    if (belt_wgs && atoi(belt_wgs) > 0) grid.x = (unsigned)std::min<long>(grid.x, atol(belt_wgs));
     HIP_TRY(hipFuncSetAttribute((const void *)ringfft_direct_ct<N, NCH, MC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024));
     ringfft_direct_ct<N, NCH, MC, T><<<grid, T, shm, stream>>>(c.d_list, c.count, p->lmax, G, nnu, p->npix, p->d_start,
@@ -780,7 +775,7 @@ static int launch_direct(corahip_ctx *ctx, hipStream_t stream, int wg_per_cu, co
     return 0;
 }
 template <int P, int NCH, int MC, int T>
-static int launch_blu(corahip_ctx *ctx, hipStream_t stream, int wg_per_cu, const corahip_sht_plan *p,
+static int launch_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_plan *p,
                       const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps,
                       const int64_t *d_foff = nullptr, const double2 *d_filt = nullptr) {
     if (!d_foff) {
@@ -791,7 +786,7 @@ static int launch_blu(corahip_ctx *ctx, hipStream_t stream, int wg_per_cu, const
     constexpr int BS = fpc(P) + K5_CH_SKEW;
     const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu + NCH - 1) / NCH);
-    const int per_cu = wg_per_cu > 0 ? wg_per_cu : std::max<int>(1, (int)((160 * 1024) / shm));
+    const int per_cu = std::max<int>(1, (int)((160 * 1024) / shm));
     dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
     HIP_TRY(hipFuncSetAttribute((const void *)ringfft_blu_ct<P, NCH, MC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024));
@@ -819,42 +814,27 @@ static int launch_blu(corahip_ctx *ctx, hipStream_t stream, int wg_per_cu, const
 // never share the int with the status
 int sht_ringfft_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c, const double *inter,
                    int G, int nnu, double *maps, bool *took) {
-    static const bool off = getenv("CORAHIP_K5_GENERIC") != nullptr;   // diagnostics: force the generic kernel
     *took = false;
-    if (off) return 0;
     int rc = -1;
     hipStream_t st = ctx->stream;
     if (c.P == 0) {
-        // A/B: the belt as 2-channel items of 256 threads, TWO workgroups (78 KB each) per CU
-        static const bool belt2 = getenv("CORAHIP_K5_BELT2") != nullptr;
-        if (c.N == 2048 && belt2) rc = launch_direct<2048, 2, 8, 256>(ctx, st, 2, p, c, inter, G, nnu, maps);
-        else if (c.N == 2048) rc = launch_direct<2048, 4, 4, 512>(ctx, st, 0, p, c, inter, G, nnu, maps);
-        else if (c.N == 4096) rc = launch_direct<4096, 2, 8, 512>(ctx, st, 0, p, c, inter, G, nnu, maps);
+        if (c.N == 2048) rc = launch_direct<2048, 4, 4, 512>(ctx, st, p, c, inter, G, nnu, maps);
+        else if (c.N == 4096) rc = launch_direct<4096, 2, 8, 512>(ctx, st, p, c, inter, G, nnu, maps);
         else return 0;
     } else {
-        static const bool no3 = getenv("CORAHIP_K5_NO3") != nullptr;   // diagnostics: power-of-two lengths only
-        static const bool half = getenv("CORAHIP_K5_HALF") != nullptr;   // A/B: 256-thread workgroups of one channel, two per CU
-        // (one channel fills the LDS)
-        // Measured at the cfg-5 rank share (128 channels; the generic kernel took 30.6 ms for the two classes): 512 threads
-        // (two waves per SIMD, but the radix-32 / 24 butterflies then spill: 268 / 72 bytes) 16.5 / 10.1 ms, 256 threads
-        // (one wave per SIMD, no spill) 13.8 / 10.8 ms for P = 8192 / 6144: each takes the faster form.
-        // CORAHIP_K5_BIG=256|512 forces one form for both (A/B).
-        static const char *bigenv = getenv("CORAHIP_K5_BIG");
-        const int big = bigenv ? atoi(bigenv) : 0;
-        if (c.P3 == 8192 && big != 512) rc = launch_blu<8192, 1, 16, 256>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 8192) rc = launch_blu<8192, 1, 8, 512>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 6144 && big != 256) rc = launch_blu<6144, 1, 8, 512>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 6144) rc = launch_blu<6144, 1, 16, 256>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (half && c.P3 == 3072 && !no3) rc = launch_blu<3072, 1, 8, 256>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (half && c.P3 != 1536 && c.P == 4096) rc = launch_blu<4096, 1, 8, 256>(ctx, st, 0, p, c, inter, G, nnu, maps);
-        else if (c.P3 == 2560 && !no3) rc = launch_blu<2560, 2, 4, 512>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 3584 && !no3) rc = launch_blu<3584, 2, 4, 512>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 3072 && !no3) rc = launch_blu<3072, 2, 4, 512>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 1536 && !no3) rc = launch_blu<1536, 4, 2, 512>(ctx, st, 0, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P == 4096) rc = launch_blu<4096, 2, 4, 512>(ctx, st, 0, p, c, inter, G, nnu, maps);
-        else if (c.P == 2048 && half) rc = launch_blu<2048, 2, 4, 256>(ctx, st, 2, p, c, inter, G, nnu, maps);   // A/B: 2-channel items, two per CU
-        else if (c.P == 2048) rc = launch_blu<2048, 4, 2, 512>(ctx, st, 0, p, c, inter, G, nnu, maps);
-        else if (c.P == 1024) rc = launch_blu<1024, 4, 2, 256>(ctx, st, 0, p, c, inter, G, nnu, maps);   // (256 threads, two workgroups per CU: 0.61 -> 0.54 ms)
+        // P3 = 8192 / 6144: one channel fills the LDS.  Measured at the cfg-5 rank share (128 channels; the generic kernel
+        // took 30.6 ms for the two classes): 512 threads (two waves per SIMD, but the radix-32 / 24 butterflies then spill:
+        // 268 / 72 bytes) 16.5 / 10.1 ms, 256 threads (one wave per SIMD, no spill) 13.8 / 10.8 ms for P = 8192 / 6144:
+        // each takes the faster form.
+        if (c.P3 == 8192) rc = launch_blu<8192, 1, 16, 256>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 6144) rc = launch_blu<6144, 1, 8, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 2560) rc = launch_blu<2560, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 3584) rc = launch_blu<3584, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 3072) rc = launch_blu<3072, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 1536) rc = launch_blu<1536, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P == 4096) rc = launch_blu<4096, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps);
+        else if (c.P == 2048) rc = launch_blu<2048, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps);
+        else if (c.P == 1024) rc = launch_blu<1024, 4, 2, 256>(ctx, st, p, c, inter, G, nnu, maps);   // (256 threads, two workgroups per CU: 0.61 -> 0.54 ms)
         else return 0;
     }
     if (rc) return rc;
@@ -1114,10 +1094,8 @@ static int launch_ana_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sh
 }
 int sht_ringana_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c, const double *maps, int nvalid,
                    int nnu_pad, const double *ring_w, int G, double *inter, bool *took) {
-    static const bool off = getenv("CORAHIP_K5_GENERIC") != nullptr;
-    static const bool no3 = getenv("CORAHIP_K5_NO3") != nullptr;
     *took = false;
-    if (off || nvalid < 1) return 0;
+    if (nvalid < 1) return 0;
     hipStream_t st = ctx->stream;
     int rc;
 #define ANA_ARGS ctx, st, p, c, maps, nvalid, nnu_pad, ring_w, G, inter
@@ -1125,10 +1103,10 @@ int sht_ringana_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sh
     //  N < m < mcut hold aliases they do not write, and the class goes to the run-time ringana_kernel, which folds them)
     if (c.P == 0 && c.N == 2048 && p->lmax <= c.N) rc = launch_ana_direct<2048, 4, 512>(ANA_ARGS);
     else if (c.P == 0 && c.N == 4096 && p->lmax <= c.N) rc = launch_ana_direct<4096, 2, 512>(ANA_ARGS);
-    else if (c.P3 == 2560 && !no3) rc = launch_ana_blu<2560, 2, 512>(ANA_ARGS, true);
-    else if (c.P3 == 3584 && !no3) rc = launch_ana_blu<3584, 2, 512>(ANA_ARGS, true);
-    else if (c.P3 == 3072 && !no3) rc = launch_ana_blu<3072, 2, 512>(ANA_ARGS, true);
-    else if (c.P3 == 1536 && !no3) rc = launch_ana_blu<1536, 4, 512>(ANA_ARGS, true);
+    else if (c.P3 == 2560) rc = launch_ana_blu<2560, 2, 512>(ANA_ARGS, true);
+    else if (c.P3 == 3584) rc = launch_ana_blu<3584, 2, 512>(ANA_ARGS, true);
+    else if (c.P3 == 3072) rc = launch_ana_blu<3072, 2, 512>(ANA_ARGS, true);
+    else if (c.P3 == 1536) rc = launch_ana_blu<1536, 4, 512>(ANA_ARGS, true);
     else if (c.P == 4096 && c.P3 <= 4096) rc = launch_ana_blu<4096, 2, 512>(ANA_ARGS, false);
     else if (c.P == 2048) rc = launch_ana_blu<2048, 4, 512>(ANA_ARGS, false);
     else if (c.P == 1024) rc = launch_ana_blu<1024, 4, 256>(ANA_ARGS, false);
@@ -1145,33 +1123,6 @@ int sht_second_stream(corahip_ctx *ctx) {
         HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
     }
-    return 0;
-}
-
-// The belt (HBM-bound: 2/3 of the pixels, little arithmetic) and the largest Bluestein class (LDS / FP64-bound, a third
-// of the traffic) run CONCURRENTLY: each as 256-thread workgroups with half the channels per item (78 KB of LDS), one
-// workgroup of each kernel per CU, launched on two streams - the compute-bound items of one kernel fill the memory
-// stalls of the other on every CU.  *took = true if it launched both classes (the caller then skips them); the return
-// value is the error status only.
-int sht_ringfft_ct_pair(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &belt,
-                        const corahip_sht_plan::ring_class &cap, const double *inter, int G, int nnu, double *maps, bool *took) {
-    *took = false;
-    // Measured at cfg 3 (one box, A/B): 18.6 ms paired against 17.0 ms with the two classes one after the other at
-    // full width - the half-width kernels lose more per item than the overlap returns - so the pairing is OFF unless
-    // CORAHIP_K5_PAIR is set; kept for the record and for other shapes.
-    static const bool on = getenv("CORAHIP_K5_PAIR") != nullptr && getenv("CORAHIP_K5_GENERIC") == nullptr;
-    if (!on || !(belt.P == 0 && belt.N == 2048 && cap.P == 4096 && cap.P3 == 0)) return 0;
-    int rcs = sht_second_stream(ctx);
-    if (rcs) return rcs;
-    HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-    HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    int rc = launch_blu<4096, 1, 8, 256>(ctx, ctx->stream2, 1, p, cap, inter, G, nnu, maps);
-    if (!rc) rc = launch_direct<2048, 2, 8, 256>(ctx, ctx->stream, 1, p, belt, inter, G, nnu, maps);
-    // joined on the error path as well: nothing may stay on stream2 unordered against the caller's stream
-    if (hipEventRecord(ctx->ev_join, ctx->stream2) != hipSuccess || hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0) != hipSuccess)
-        HIP_TRY(hipStreamSynchronize(ctx->stream2));
-    if (rc) return rc;
-    *took = true;
     return 0;
 }
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostics: time of corahip_factor_batched for NL matrices of F x F (env NL, F); CORAHIP_K2_VALU=1 forces the
-right-looking VALU kernel, CORAHIP_LIB=cora_amd/libcorahip_k2abN.so the ablation builds."""
+"""Diagnostics: time of corahip_factor_batched for NL matrices of F x F (env NL, F);
+CORAHIP_LIB=cora_amd/libcorahip_k2s.so selects the phase-stamp build (`make ab`, see cora_amd/csrc/Makefile)."""
 import os
 import sys
 

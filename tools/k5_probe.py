@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostics: per-class K5 (ring FFT) times at the cfg-3 geometry; run with CORAHIP_K5_TIMES=1 and,
-for the ablation builds, CORAHIP_LIB=cora_amd/libcorahip_k5abN.so."""
+"""Diagnostics: per-class K5 (ring FFT) times at the cfg-3 geometry; run with CORAHIP_K5_TIMES=1
+(CORAHIP_LIB=cora_amd/libcorahip_k5s.so selects the phase-stamp build: `make ab`, see cora_amd/csrc/Makefile)."""
 import os
 import sys
 

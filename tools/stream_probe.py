@@ -52,12 +52,9 @@ if 8 * n < 40e9:
     ref = alm.clone()
     old_pcg()
     ref_p = alm.clone()
-for serial in (False, True):
-    if serial:
-        os.environ["CORAHIP_GEN_SERIAL"] = "1"
-    for mb in (32, 64, 128, 256, 512, 1024, 2048, 4096):
-        tp = timed(lambda: ctx.draw_alm_numpy(T, info, ("pcg64", st["state"], st["inc"]), lmax, F, out=alm, ring_bytes=mb << 20))
-        okp = torch.equal(alm, ref_p) if 8 * n < 40e9 else None
-        tl = timed(lambda: ctx.draw_alm_numpy(T, info, ("legacy", lst), lmax, F, out=alm, ring_bytes=mb << 20))
-        okl = torch.equal(alm, ref) if 8 * n < 40e9 else None
-        print("ring %5d MB %s: pcg64 %.2f ms (%s)   legacy %.2f ms (%s)" % (mb, "serial " if serial else "overlap", tp, okp, tl, okl))
+for mb in (32, 64, 128, 256, 512, 1024, 2048, 4096):
+    tp = timed(lambda: ctx.draw_alm_numpy(T, info, ("pcg64", st["state"], st["inc"]), lmax, F, out=alm, ring_bytes=mb << 20))
+    okp = torch.equal(alm, ref_p) if 8 * n < 40e9 else None
+    tl = timed(lambda: ctx.draw_alm_numpy(T, info, ("legacy", lst), lmax, F, out=alm, ring_bytes=mb << 20))
+    okl = torch.equal(alm, ref) if 8 * n < 40e9 else None
+    print("ring %5d MB: pcg64 %.2f ms (%s)   legacy %.2f ms (%s)" % (mb, tp, okp, tl, okl))
