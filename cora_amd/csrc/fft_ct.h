@@ -350,3 +350,14 @@ __device__ __forceinline__ static void ct_pass(double2 *sm, const double2 w1, co
     }
 }
 
+// the two pass twiddles a thread keeps for the whole kernel (its butterfly index within a pass never changes):
+// wA = e^{2 pi i j0 / N}, j0 = tid0 mod Q0, for the pass of sub-length N and stride Q0 = N / R0;
+// wB = e^{2 pi i j1 / Q0}, j1 = tid0 mod (Q0 / R1), for the pass of sub-length Q0.  The last pass (stride 1) has none.
+// (sincospi writes the members directly: through temporaries the compiler orders the sine / cosine selects of the
+//  Bluestein line kernels differently from the code they were measured with)
+template <int N, int Q0, int R1>
+__device__ __forceinline__ static void pass_twiddles(const int tid0, double2 &wA, double2 &wB) {
+    const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
+    sincospi(2.0 * (double)j0 / (double)N, &wA.y, &wA.x);
+    sincospi(2.0 * (double)j1 / (double)Q0, &wB.y, &wB.x);
+}

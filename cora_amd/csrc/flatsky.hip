@@ -22,10 +22,8 @@
 
 #include "common.h"
 #include "rng_dev.h"
+#include "tile_walk.h"
 
-#ifndef FS_PAIR_XCD
-#define FS_PAIR_XCD 3   // log2 of the adjacent tiles given to one XCD at a time (0: off); measured 1024^3 axis-1 pass: 7.05 / 6.44 / 6.2 / 6.08 ms for 0 / 1 / 2 / 3
-#endif
 #ifndef FS_THREADS
 #define FS_THREADS 512
 #endif
@@ -200,9 +198,9 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
     const int h = A.h, hp = (h >> 1) + 1;      // modes 3/4: pairs (k, h - k), k = 0 .. h/2
     const double2 *in2 = reinterpret_cast<const double2 *>(A.in);
     double2 *out2 = reinterpret_cast<double2 *>(A.out);
-    const long chunks = (A.inner + T - 1) / T;  // tiles per outer index (inner > 1)
+    tile_walk<0> tiles(A.inner, T);             // (inner > 1; the tile split below is this kernel's own: its tiles carry rcp_teff)
     const long nlines = A.nouter * A.inner;
-    const long ntiles = A.inner == 1 ? (nlines + T - 1) / T : A.nouter * chunks;
+    const long ntiles = A.inner == 1 ? (nlines + T - 1) / T : A.nouter * tiles.chunks;
     const int nin = MODE == 1 ? A.nh : (MODE == 3 ? n + 1 : n);   // input elements per line (mode 4: double2 = 2 reals)
     const int nout = MODE == 2 ? A.nh : (MODE == 4 ? n + 1 : n);  // output elements per line (mode 3: double2 = 2 reals)
 
@@ -215,20 +213,20 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
     double2 *lg_l = twl + (A.twl ? (P >> 2) : 0), *sc_l = lg_l + 257;
     const double2 *lg_t = (MODE == 5 && A.gen_lds) ? lg_l : RNG_LOG_TAB, *sc_t = (MODE == 5 && A.gen_lds) ? sc_l : RNG_SC_TAB;
 
-    struct tile_t {
+    struct ltile_t {
         long outer, i0;
         int teff;
         float rcp_teff;
     };
     auto tile_of = [&](long tile) {
-        tile_t tl;
+        ltile_t tl;
         if (A.inner == 1) {
             tl.outer = tile * T;  // first line
             tl.i0 = 0;
             tl.teff = (int)min((long)T, nlines - tl.outer);
         } else {
-            tl.outer = tile / chunks;
-            tl.i0 = (tile - tl.outer * chunks) * T;
+            tl.outer = tile / tiles.chunks;
+            tl.i0 = (tile - tl.outer * tiles.chunks) * T;
             tl.teff = (int)min((long)T, A.inner - tl.i0);
         }
         tl.rcp_teff = 1.0f / (float)tl.teff;
@@ -236,7 +234,7 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
     };
     // element e of a tile -> (line t, index j along the axis, global element offset) for `len` elements per line
     const float rcp_nin = 1.0f / (float)nin, rcp_nout = 1.0f / (float)nout, rcp_hp = 1.0f / (float)hp;
-    auto locate = [&](const tile_t &tl, int e, int len, float rcp_len, int &t, int &j) -> long {
+    auto locate = [&](const ltile_t &tl, int e, int len, float rcp_len, int &t, int &j) -> long {
         if (A.inner == 1) {
             t = fastdiv(e, len, rcp_len, j);
             return (tl.outer + t) * len + j;
@@ -245,7 +243,7 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
         return (tl.outer * len + j) * A.inner + tl.i0 + t;
     };
     double2 R[FS_NLOAD];
-    auto prefetch = [&](const tile_t &tl) {
+    auto prefetch = [&](const ltile_t &tl) {
 #pragma unroll
         for (int u = 0; u < FS_NLOAD; u++) {
             const int e = threadIdx.x + u * FS_THREADS;
@@ -256,7 +254,7 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
             }
         }
     };
-    auto commit = [&](const tile_t &tl) {
+    auto commit = [&](const ltile_t &tl) {
         if (A.blu) {
             const float rcp_z = 1.0f / (float)(P - n);
             for (int e = threadIdx.x; e < tl.teff * (P - n); e += FS_THREADS) {
@@ -273,8 +271,7 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
                 const long addr = locate(tl, e, nin, rcp_nin, t, j);
                 double2 v = R[u];
                 if (MODE == 5) {      // the k-weight arrived in R[u].x: the normals of this element are made here
-                    const double2 z = philox_boxmuller((uint64_t)addr, A.seed, lg_t, sc_t);
-                    v = make_double2(z.x * v.x, z.y * v.x);
+                    v = philox_weighted_pair((uint64_t)addr, A.seed, v.x, lg_t, sc_t);
                 }
                 if (MODE == 3) {
                     // raw spectrum at natural positions; the packing pass below works on pairs in place
@@ -312,30 +309,19 @@ __global__ void __launch_bounds__(FS_THREADS, FS_WG_PER_CU * FS_THREADS / 256) l
     if (MODE == 3 || MODE == 4)
         for (int k = threadIdx.x; k < hp; k += FS_THREADS) rtwl[k] = A.rtw[k];
     if (MODE == 5 && A.gen_lds) {
-        for (int k = threadIdx.x; k < 257; k += FS_THREADS) lg_l[k] = RNG_LOG_TAB[k];
-        for (int k = threadIdx.x; k < 256; k += FS_THREADS) sc_l[k] = RNG_SC_TAB[k];
+        rng_tabs_to_lds(lg_l, sc_l, threadIdx.x, FS_THREADS);
         __syncthreads();
     }
-    // Strided axes read and write 16 T-byte segments: two tiles that are neighbours along the contiguous axis share
-    // every 128-byte line.  Workgroups b and b + 8 run on the same XCD (round-robin dispatch) at the same time, so
-    // they (and b + 16, ...) are given adjacent tiles and a line is fetched into that XCD's L2 once instead of into several L2s.
-    constexpr int GL = FS_PAIR_XCD;    // log2 of the tiles per group (1: pairs)
-    const long gmask = (8L << GL) - 1;
-    const bool pair_xcd = GL > 0 && A.inner != 1 && (ntiles & gmask) == 0 && (gridDim.x & gmask) == 0;
-    auto remap = [&](long v) {
-        if (!pair_xcd) return v;
-        const long slot = v >> 3, xcd = v & 7;
-        return (((slot >> GL) * 8 + xcd) << GL) + (slot & ((1 << GL) - 1));
-    };
-    tile_t cur = tile_of(remap(tile));
+    tiles.pair_xcds(ntiles, A.inner != 1);             // (tile_walk.h; contiguous lines are tiled T whole lines at a time and not paired)
+    ltile_t cur = tile_of(tiles.remap(tile));
     prefetch(cur);
     while (true) {
         commit(cur);
         __syncthreads();
         const long next = tile + gridDim.x;
-        tile_t nxt = cur;
+        ltile_t nxt = cur;
         if (next < ntiles) {
-            nxt = tile_of(remap(next));
+            nxt = tile_of(tiles.remap(next));
             prefetch(nxt);
         }
         if (MODE == 3) {

@@ -11,6 +11,7 @@
 // below 17 or above 2048, contiguous complex transforms; CORAHIP_FLAT_GENERIC=1 forces it (A/B, tests/test_flatsky.py).
 #include "fft_ct.h"
 #include "rng_dev.h"
+#include "tile_walk.h"
 
 // ------------------------------------------------------------------------------------
 // Flat-sky fields (cora/core/gaussianfield.py:102-120, numpy.fft.irfftn's last axis): the half-complex -> real transform
@@ -35,7 +36,7 @@ linec2r_ct(const double2 *in, double *out, long nlines, double scale) {
     const long nitems = (nlines + NCH - 1) / NCH;
 
     double2 wH, wA, wB;     // e^{i pi j0 / N}, e^{2 pi i j0 / N}, e^{2 pi i j1 / (N / R0)}
-    {
+    {   // (pass_twiddles written out: wH shares (double)j0 with wA, and the code the compiler makes of this kernel depends on that)
         const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
         double s, c;
         sincospi((double)j0 / (double)N, &s, &c);
@@ -167,42 +168,12 @@ linec2c_ct(const double *in, double2 *out, long nouter, long inner, double scale
     double2 *lg_l = sm + NCH * BS, *sc_l = lg_l + 257;       // GEN: the generator's tables (rng_dev.h)
     const int tid0 = threadIdx.x;
     const double2 *in2 = reinterpret_cast<const double2 *>(in);
-    const long chunks = (inner + NCH - 1) / NCH;
-    const long ntiles = nouter * chunks;
-    if (GEN) {
-        for (int k = tid0; k < 257; k += T) lg_l[k] = RNG_LOG_TAB[k];
-        for (int k = tid0; k < 256; k += T) sc_l[k] = RNG_SC_TAB[k];
-    }
-    double2 wA, wB;     // e^{2 pi i j0 / N}, e^{2 pi i j1 / (N / R0)}
-    {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
-        double s, c;
-        sincospi(2.0 * (double)j0 / (double)N, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
-    // tiles that are neighbours along the contiguous axis share 128-byte lines (the row pitch is odd in 16-byte units):
-    // the workgroups of one XCD take eight adjacent tiles at a time (flatsky.hip, FS_PAIR_XCD)
-    constexpr int GL = 3;
-    const long gmask = (8L << GL) - 1;
-    const bool pair_xcd = (ntiles & gmask) == 0 && (gridDim.x & gmask) == 0;
-    auto remap = [&](long v) {
-        if (!pair_xcd) return v;
-        const long slot = v >> 3, xcd = v & 7;
-        return (((slot >> GL) * 8 + xcd) << GL) + (slot & ((1 << GL) - 1));
-    };
-    struct tile_t {
-        long base;
-        int teff;
-    };
-    auto tile_of = [&](long v) {
-        const long outer = v / chunks, i0 = (v - outer * chunks) * NCH;
-        tile_t t;
-        t.base = outer * N * inner + i0;
-        t.teff = (int)min((long)NCH, inner - i0);
-        return t;
-    };
+    tile_walk<NCH, N> tiles(inner);
+    const long ntiles = nouter * tiles.chunks;
+    if (GEN) rng_tabs_to_lds(lg_l, sc_l, tid0, T);
+    double2 wA, wB;
+    pass_twiddles<N, Q0, R1>(tid0, wA, wB);
+    tiles.pair_xcds(ntiles);
     double2 R[U];
     auto prefetch = [&](const tile_t &tl, int tid) {
 #pragma unroll
@@ -215,7 +186,7 @@ linec2c_ct(const double *in, double2 *out, long nouter, long inner, double scale
     };
     long vt = blockIdx.x;
     if (vt >= ntiles) return;
-    tile_t cur = tile_of(remap(vt));
+    tile_t cur = tiles.tile_of(vt);
     prefetch(cur, tid0);
     while (true) {
         int tid = tid0;                                   // opaque per item: see ringfft_direct_ct
@@ -228,13 +199,12 @@ linec2c_ct(const double *in, double2 *out, long nouter, long inner, double scale
             double2 v = R[u];
             if (GEN) {
                 const long addr = cur.base + (long)j * inner + min(c, cur.teff - 1);
-                const double2 z = philox_boxmuller((uint64_t)addr, seed, lg_l, sc_l);
-                v = make_double2(z.x * v.x, z.y * v.x);
+                v = philox_weighted_pair((uint64_t)addr, seed, v.x, lg_l, sc_l);
             }
             sm[c * BS + fpad(j)] = v;
         }
         const long vnext = vt + gridDim.x;
-        const tile_t nxt = tile_of(remap(min(vnext, ntiles - 1)));
+        const tile_t nxt = tiles.tile_of(min(vnext, ntiles - 1));
         prefetch(nxt, tid);                               // (unconditional: the last iteration re-reads a tile)
         __syncthreads();
         ct_pass<PK, N, NCH, BS, N, R0, SIGN, false, T>(sm, wA, tid);
@@ -293,20 +263,13 @@ linec2c_h2_ct(const double *in, double2 *out, long nouter, long inner, double sc
     double2 *lg_l = sm + NCH * BS, *sc_l = lg_l + 257;
     const int tid0 = threadIdx.x;
     const double2 *in2 = reinterpret_cast<const double2 *>(in);
-    const long chunks = (inner + NCH - 1) / NCH;
-    const long ntiles = nouter * chunks;
-    if (GEN) {
-        for (int k = tid0; k < 257; k += T) lg_l[k] = RNG_LOG_TAB[k];
-        for (int k = tid0; k < 256; k += T) sc_l[k] = RNG_SC_TAB[k];
-    }
+    tile_walk<NCH, N> tiles(inner);
+    const long ntiles = nouter * tiles.chunks;
+    if (GEN) rng_tabs_to_lds(lg_l, sc_l, tid0, T);
     double2 wA, wB, wK, wK2;   // pass twiddles; w^k of this thread's first butterfly and the step w^2 between its butterflies
+    pass_twiddles<NH, Q0, R1>(tid0, wA, wB);
     {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
         double s, c;
-        sincospi(2.0 * (double)j0 / (double)NH, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
         // butterfly idx = tid + it T of line idx & 15: t = idx >> 4 = 16 k0 + k1, bin k = k0 + 16 k1 = (tid >> 8) + 2 it + 16 ((tid >> 4) & 15)
         const int kb = (tid0 >> 8) + 16 * ((tid0 >> 4) & 15);
         sincospi(2.0 * (double)kb / (double)N, &s, &c);
@@ -314,25 +277,7 @@ linec2c_h2_ct(const double *in, double2 *out, long nouter, long inner, double sc
         sincospi(4.0 / (double)N, &s, &c);
         wK2 = make_double2(c, SIGN > 0 ? s : -s);
     }
-    constexpr int GL = 3;
-    const long gmask = (8L << GL) - 1;
-    const bool pair_xcd = (ntiles & gmask) == 0 && (gridDim.x & gmask) == 0;
-    auto remap = [&](long v) {
-        if (!pair_xcd) return v;
-        const long slot = v >> 3, xcd = v & 7;
-        return (((slot >> GL) * 8 + xcd) << GL) + (slot & ((1 << GL) - 1));
-    };
-    struct tile_t {
-        long base;
-        int teff;
-    };
-    auto tile_of = [&](long v) {
-        const long outer = v / chunks, i0 = (v - outer * chunks) * NCH;
-        tile_t t;
-        t.base = outer * N * inner + i0;
-        t.teff = (int)min((long)NCH, inner - i0);
-        return t;
-    };
+    tiles.pair_xcds(ntiles);
     double2 R[U];
     // rows 2 jj + par of the tile
     auto prefetch = [&](const tile_t &tl, int par, int tid) {
@@ -352,15 +297,14 @@ linec2c_h2_ct(const double *in, double2 *out, long nouter, long inner, double sc
             double2 v = R[u];
             if (GEN) {
                 const long addr = tl.base + (long)(2 * jj + par) * inner + min(c, tl.teff - 1);
-                const double2 z = philox_boxmuller((uint64_t)addr, seed, lg_l, sc_l);
-                v = make_double2(z.x * v.x, z.y * v.x);
+                v = philox_weighted_pair((uint64_t)addr, seed, v.x, lg_l, sc_l);
             }
             sm[c * BS + fpad(jj)] = v;
         }
     };
     long vt = blockIdx.x;
     if (vt >= ntiles) return;
-    tile_t cur = tile_of(remap(vt));
+    tile_t cur = tiles.tile_of(vt);
     prefetch(cur, 0, tid0);
     while (true) {
         int tid = tid0;                                   // opaque per item: see ringfft_direct_ct
@@ -386,7 +330,7 @@ linec2c_h2_ct(const double *in, double2 *out, long nouter, long inner, double sc
         __syncthreads();                                  // every E has been read
         commit(cur, 1, tid);
         const long vnext = vt + gridDim.x;
-        const tile_t nxt = tile_of(remap(min(vnext, ntiles - 1)));
+        const tile_t nxt = tiles.tile_of(min(vnext, ntiles - 1));
         prefetch(nxt, 0, tid);                            // (unconditional: the last iteration re-reads a tile)
         __syncthreads();
         ct_pass<PK, NH, NCH, BS, NH, R0, SIGN, false, T>(sm, wA, tid);
@@ -423,44 +367,31 @@ linec2c_h2_ct(const double *in, double2 *out, long nouter, long inner, double sc
     }
 }
 
-template <int N, int NCH, int T>
+// linec2c_ct (H2 = false) or linec2c_h2_ct (one workgroup per CU: its half tiles fill the LDS) of the strided pass
+template <int N, int NCH, int T, bool H2, int SIGN, bool GEN>
+static constexpr auto linec2c_kernel() {
+    if constexpr (H2) return &linec2c_h2_ct<N, NCH, T, SIGN, GEN>;
+    else return &linec2c_ct<N, NCH, T, SIGN, GEN>;
+}
+template <int N, int NCH, int T, bool H2 = false>
 static int launch_linec2c(corahip_ctx *ctx, const double *in, double *out, long nouter, long inner, int inverse, double scale, bool gen,
                           uint64_t seed) {
     constexpr int PK = 1;
-    constexpr int BS = fpc(N) + K5_CH_SKEW;
+    constexpr int BS = fpc(H2 ? N / 2 : N) + K5_CH_SKEW;
     const size_t shm = sizeof(double2) * ((size_t)NCH * BS + (gen ? 513 : 0));
     const long ntiles = nouter * ((inner + NCH - 1) / NCH);
-    const long per_cu = std::max<long>(1, std::min<long>((160 * 1024) / shm, 2048 / T));
+    const long per_cu = H2 ? 1 : std::max<long>(1, std::min<long>((160 * 1024) / shm, 2048 / T));
     dim3 grid((unsigned)std::min<long>(ntiles, (long)ctx->num_cu * per_cu));
     double2 *o2 = reinterpret_cast<double2 *>(out);
-#define C2C_LAUNCH(SG, GN)                                                                                                  \
-    HIP_TRY(hipFuncSetAttribute((const void *)linec2c_ct<N, NCH, T, SG, GN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-    linec2c_ct<N, NCH, T, SG, GN><<<grid, T, shm, ctx->stream>>>(in, o2, nouter, inner, scale, seed)
-    if (gen) { C2C_LAUNCH(1, true); }
-    else if (inverse) { C2C_LAUNCH(1, false); }
-    else { C2C_LAUNCH(-1, false); }
-#undef C2C_LAUNCH
-    LAUNCH_CHECK();
-    return 0;
-}
-template <int N, int NCH, int T>
-static int launch_linec2c_h2(corahip_ctx *ctx, const double *in, double *out, long nouter, long inner, int inverse, double scale, bool gen,
-                             uint64_t seed) {
-    constexpr int PK = 1;
-    constexpr int BS = fpc(N / 2) + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * ((size_t)NCH * BS + (gen ? 513 : 0));
-    const long ntiles = nouter * ((inner + NCH - 1) / NCH);
-    dim3 grid((unsigned)std::min<long>(ntiles, (long)ctx->num_cu));
-    double2 *o2 = reinterpret_cast<double2 *>(out);
-#define C2C_LAUNCH(SG, GN)                                                                                                  \
-    HIP_TRY(hipFuncSetAttribute((const void *)linec2c_h2_ct<N, NCH, T, SG, GN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-    linec2c_h2_ct<N, NCH, T, SG, GN><<<grid, T, shm, ctx->stream>>>(in, o2, nouter, inner, scale, seed)
-    if (gen) { C2C_LAUNCH(1, true); }
-    else if (inverse) { C2C_LAUNCH(1, false); }
-    else { C2C_LAUNCH(-1, false); }
-#undef C2C_LAUNCH
-    LAUNCH_CHECK();
-    return 0;
+    auto launch = [&](auto kernel) {
+        HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        kernel<<<grid, T, shm, ctx->stream>>>(in, o2, nouter, inner, scale, seed);
+        LAUNCH_CHECK();
+        return 0;
+    };
+    if (gen) return launch(linec2c_kernel<N, NCH, T, H2, 1, true>());
+    if (inverse) return launch(linec2c_kernel<N, NCH, T, H2, 1, false>());
+    return launch(linec2c_kernel<N, NCH, T, H2, -1, false>());
 }
 // a strided complex pass of the flat-sky transforms (inner > 1) for the lengths that have a compile-time schedule;
 // gen: inverse pass whose input is generated from the real k-weights `in` (corahip_randomfield_irfftn).  *took = false:
@@ -473,7 +404,7 @@ int flat_c2c_ct(corahip_ctx *ctx, const double *in, double *out, long nouter, in
     int rc;
     if (n == 256 && inner >= 16) rc = launch_linec2c<256, 16, 256>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 512 && inner >= 16) rc = launch_linec2c<512, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else if (n == 1024 && inner >= 16) rc = launch_linec2c_h2<1024, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
+    else if (n == 1024 && inner >= 16) rc = launch_linec2c<1024, 16, 512, true>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 1024 && inner >= 8) rc = launch_linec2c<1024, 8, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 384 && inner >= 16) rc = launch_linec2c<384, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 768 && inner >= 8) rc = launch_linec2c<768, 8, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
@@ -505,13 +436,9 @@ liner2c_ct(const double *in, double2 *out, long nlines) {
     const int tid0 = threadIdx.x;
     const long nitems = (nlines + NCH - 1) / NCH;
     double2 wA, wB, wS, wSstep;     // (wS: e^{-i pi (tid mod N) / N}, its step over T bins)
+    pass_twiddles<N, Q0, R1>(tid0, wA, wB);
     {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
         double s, c;
-        sincospi(2.0 * (double)j0 / (double)N, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
         sincospi((double)(tid0 % N) / (double)N, &s, &c);
         wS = make_double2(c, -s);
         sincospi((double)T / (double)N, &s, &c);
@@ -787,20 +714,13 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
     double2 *lg_l = sm + NCH * BS, *sc_l = lg_l + 257;
     const int tid0 = threadIdx.x;
     const double2 *in2 = reinterpret_cast<const double2 *>(in);
-    const long chunks = (inner + NCH - 1) / NCH;
-    const long ntiles = nouter * chunks;
-    if (GEN) {
-        for (int k = tid0; k < 257; k += T) lg_l[k] = RNG_LOG_TAB[k];
-        for (int k = tid0; k < 256; k += T) sc_l[k] = RNG_SC_TAB[k];
-    }
+    tile_walk<NCH> tiles(inner);
+    const long ntiles = nouter * tiles.chunks;
+    if (GEN) rng_tabs_to_lds(lg_l, sc_l, tid0, T);
     double2 wA, wB, wL;     // e^{2 pi i j0 / P}, e^{2 pi i j1 / (P / R0)}; wL: wA for the last pass' thread -> butterfly map
+    pass_twiddles<P, Q0, R1>(tid0, wA, wB);
     {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
         double s, c;
-        sincospi(2.0 * (double)j0 / (double)P, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
         sincospi(2.0 * (double)((tid0 / NCH) & (Q0 - 1)) / (double)P, &s, &c);
         wL = make_double2(c, s);
     }
@@ -817,25 +737,7 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
     for (int it = 0; it < ITL; it++)
 #pragma unroll
         for (int r = 0; r < R0 / 2; r++) ob[it][r] = chirp[min((tid0 + it * T) / NCH % Q0 + r * Q0, n - 1)];
-    constexpr int GL = 3;
-    const long gmask = (8L << GL) - 1;
-    const bool pair_xcd = (ntiles & gmask) == 0 && (gridDim.x & gmask) == 0;
-    auto remap = [&](long v) {
-        if (!pair_xcd) return v;
-        const long slot = v >> 3, xcd = v & 7;
-        return (((slot >> GL) * 8 + xcd) << GL) + (slot & ((1 << GL) - 1));
-    };
-    struct tile_t {
-        long base;
-        int teff;
-    };
-    auto tile_of = [&](long v) {
-        const long outer = v / chunks, i0 = (v - outer * chunks) * NCH;
-        tile_t t;
-        t.base = outer * n * inner + i0;
-        t.teff = (int)min((long)NCH, inner - i0);
-        return t;
-    };
+    tiles.pair_xcds(ntiles);
     double2 R[U];
     auto prefetch = [&](const tile_t &tl, int tid) {
 #pragma unroll
@@ -848,7 +750,7 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
     };
     long vt = blockIdx.x;
     if (vt >= ntiles) return;
-    tile_t cur = tile_of(remap(vt));
+    tile_t cur = tiles.tile_of(vt, n);
     prefetch(cur, tid0);
     while (true) {
         int tid = tid0;                                   // opaque per item: see ringfft_direct_ct
@@ -863,8 +765,7 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
             double2 v = R[u];
             if (GEN) {
                 const long addr = cur.base + (long)min(j, n - 1) * inner + min(c, cur.teff - 1);
-                const double2 z = philox_boxmuller((uint64_t)addr, seed, lg_l, sc_l);
-                v = make_double2(z.x * v.x, z.y * v.x);
+                v = philox_weighted_pair((uint64_t)addr, seed, v.x, lg_l, sc_l);
             }
             if (inverse) v.y = -v.y;
             // (opaque: the generated and the loaded input must go through the SAME instructions from here on - fused into
@@ -875,7 +776,7 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
             sm[c * BS + fpad(j)] = v;
         }
         const long vnext = vt + gridDim.x;
-        const tile_t nxt = tile_of(remap(min(vnext, ntiles - 1)));
+        const tile_t nxt = tiles.tile_of(min(vnext, ntiles - 1), n);
         prefetch(nxt, tid);
         __syncthreads();
         blu_core<P, NCH, T>(sm, tid, wA, wB, fl);
@@ -936,14 +837,7 @@ lineblu_c2r_ct(const double2 *in, double2 *out, long nlines, int h, double scale
     const int hp = (h >> 1) + 1;
     const long nitems = (nlines + NCH - 1) / NCH;
     double2 wA, wB;
-    {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / 16 - 1);
-        double s, c;
-        sincospi(2.0 * (double)j0 / (double)P, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
+    pass_twiddles<P, Q0, 16>(tid0, wA, wB);
     double2 fl[R2];
 #pragma unroll
     for (int r = 0; r < R2; r++) fl[r] = filt[(size_t)(tid0 % NB) * R2 + r];
@@ -1063,14 +957,7 @@ lineblu_r2c_ct(const double2 *in, double2 *out, long nlines, int h, const double
     const int hp = (h >> 1) + 1;
     const long nitems = (nlines + NCH - 1) / NCH;
     double2 wA, wB;
-    {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / 16 - 1);
-        double s, c;
-        sincospi(2.0 * (double)j0 / (double)P, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
+    pass_twiddles<P, Q0, 16>(tid0, wA, wB);
     double2 fl[R2];
 #pragma unroll
     for (int r = 0; r < R2; r++) fl[r] = filt[(size_t)(tid0 % NB) * R2 + r];

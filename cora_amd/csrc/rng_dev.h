@@ -187,3 +187,17 @@ __device__ static inline double2 philox_boxmuller(uint64_t counter, uint64_t key
     philox4x32_10(counter, key, r);
     return rng_boxmuller_bits(r, lg, sc);
 }
+
+// copies of the two tables in LDS (lg: 257 entries, sc: 256), filled by nthreads threads; readable behind the caller's next barrier
+__device__ static inline void rng_tabs_to_lds(double2 *lg, double2 *sc, int tid, int nthreads) {
+    for (int k = tid; k < 257; k += nthreads) lg[k] = RNG_LOG_TAB[k];
+    for (int k = tid; k < 256; k += nthreads) sc[k] = RNG_SC_TAB[k];
+}
+
+// "generate where committed": kweight (N(0,1) + i N(0,1)) of spectrum element addr, the pair being the Box-Muller outputs
+// of Philox counter addr - what randomfield_draw_kernel writes.  Every kernel that fuses the draw into a transform takes
+// its input from here: the bit-identity of randomfield_irfftn with draw + irfftn rests on this being one expression.
+__device__ static inline double2 philox_weighted_pair(uint64_t addr, uint64_t seed, double kweight, const double2 *lg, const double2 *sc) {
+    const double2 z = philox_boxmuller(addr, seed, lg, sc);
+    return make_double2(z.x * kweight, z.y * kweight);
+}

@@ -200,7 +200,7 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
 
     // per-thread twiddles, fixed for the whole kernel
     double2 wH, wA, wB;     // e^{i pi j0 / N}, e^{2 pi i j0 / N}, e^{2 pi i j1 / (N / R0)}
-    {
+    {   // (pass_twiddles written out: wH shares (double)j0 with wA, and the code the compiler makes of this kernel depends on that)
         const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
         double s, c;
         sincospi((double)j0 / (double)N, &s, &c);
@@ -356,14 +356,7 @@ ringfft_blu_ct(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
     const double invP = 1.0 / (double)P;
 
     double2 wA, wB;     // e^{2 pi i j0 / P}, e^{2 pi i j1 / (P / R0)}
-    {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
-        double s, c;
-        sincospi(2.0 * (double)j0 / (double)P, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
+    pass_twiddles<P, Q0, R1>(tid0, wA, wB);
     auto cell_ptr = [&](int item) {
         const int ring = ring_list[item / ngrp];
         const int ch0 = (item % ngrp) * NCH;
@@ -642,13 +635,9 @@ ringana_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
     double2 wA, wB;         // e^{2 pi i j0 / N}, e^{2 pi i j1 / (N / R0)} (the passes conjugate them)
     double2 wS, wSstep;     // e^{-i pi tid / N} and its step over T cells: the split twiddle
     double2 phS, phSstep;   // e^{-i tid pi / (2 N)} and its step: the phase of the shifted rings
+    pass_twiddles<N, Q0, R1>(tid0, wA, wB);
     {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
         double s, c;
-        sincospi(2.0 * (double)j0 / (double)N, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
         sincospi((double)tid0 / (double)N, &s, &c);
         wS = make_double2(c, -s);
         sincospi((double)T / (double)N, &s, &c);
@@ -873,14 +862,7 @@ ringana_blu_ct(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
     const double invP = 1.0 / (double)P;
 
     double2 wA, wB;     // e^{2 pi i j0 / P}, e^{2 pi i j1 / (P / R0)}
-    {
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
-        double s, c;
-        sincospi(2.0 * (double)j0 / (double)P, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
+    pass_twiddles<P, Q0, R1>(tid0, wA, wB);
     double2 pf[NCH][U];   // z_j, j = tid + u T, of the next item (index clamped; zeroed where j >= h at the commit)
     double2 cbn[U];       // chirp b_j of the same positions
     auto prefetch = [&](int item, int t) {
