@@ -52,6 +52,7 @@ struct corahip_ctx {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;                 // second stream for kernels that run beside those of `stream` (K5 pair)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    int *k5_tickets = nullptr;                     // K5: the item counters of the ticketed belt kernel (8 words, zeroed per call)
     // the l-range pipeline of the numpy-stream draw (drawstream.hip): its generator stream and the ring's events
     unsigned *draw_slot_tab = nullptr;             // K3: (l, m block) of every work slot of 0 .. draw_slot_lmax (draw.hip)
     int draw_slot_lmax = -1;

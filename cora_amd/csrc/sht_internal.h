@@ -475,8 +475,18 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
                 double *maps);
 // K5 with compile-time transform shapes (sht_ringfft_ct.hip): *took = it launched class c (false: the generic kernel
 // has to take it); the return value is the error status only (0, CORAHIP_E* or a hipError_t)
+// cu_limit: CUs the class may fill (its persistent grid is that many workgroups times those of it that fit one CU)
 int sht_ringfft_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c, const double *inter,
-                   int G, int nnu, double *maps, bool *took);
+                   int G, int nnu, double *maps, int cu_limit, bool *took);
+// does class c go to the ticketed belt kernel (ringfft_direct_ct)?  Such a class may be launched more than once per call:
+// every launch draws its items from ctx->k5_tickets, which sht_ringfft zeroes once per call
+bool sht_ringfft_ticketed(const corahip_sht_plan::ring_class &c);
+// estimated cost of one (ring, channel group) item of class c in CU microseconds, with the CU not limited by HBM
+double sht_ringfft_item_weight(const corahip_sht_plan::ring_class &c);
+// zeroes the context's ticket counters on `stream` (allocating them on first use): once per sht_ringfft call, ahead of
+// every launch of a ticketed class
+#define K5_NTICKETS 8
+int sht_k5_tickets(corahip_ctx *ctx, hipStream_t stream);
 // plan time: filters of the 3 * 2^k Bluestein lengths (fills p->d_bfilt3; h_blu3_P / d_blu3_foff / d_bchirp must be set)
 int sht_blu3_tables(corahip_ctx *ctx, corahip_sht_plan *p, int64_t total);
 // creates ctx->stream2 and the fork / join events on first use

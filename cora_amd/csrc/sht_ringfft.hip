@@ -451,6 +451,47 @@ ringana_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
         }
     }
 }
+// One class of K5 on ctx->stream, its persistent grid limited to cu_limit CUs
+static int ringfft_launch_class(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c,
+                                const double *inter, int G, int nnu_valid, double *maps, int cu_limit) {
+    bool took = false;   // compile-time kernel for this class?
+    const int rct = sht_ringfft_ct(ctx, p, c, inter, G, nnu_valid, maps, cu_limit, &took);
+    if (rct) return rct;
+    if (took) return 0;
+    const size_t shm = sizeof(double2) * (size_t)c.nch * c.bstride;
+    const long nitems = (long)c.count * ((nnu_valid + c.nch - 1) / c.nch);
+    const int per_cu = std::max<int>(1, (int)((160 * 1024) / std::max<size_t>(shm, 1)));
+    const int k5_threads = c.threads ? c.threads : K5_THREADS;
+    // (the short classes run narrow workgroups - see the plan - and more of them per CU)
+    dim3 grid((unsigned)std::min<long>(nitems, (long)cu_limit * std::min(per_cu, k5_threads <= 128 ? 8 : 4)));
+#define RINGFFT_LAUNCH(NCH, BLU)                                                                                     \
+    HIP_TRY(hipFuncSetAttribute((const void *)ringfft_kernel<NCH, BLU>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
+                                160 * 1024));                                                                   \
+    ringfft_kernel<NCH, BLU><<<grid, k5_threads, shm, ctx->stream>>>(c.d_list, c.count, p->nside, p->lmax, G, nnu_valid, p->npix,     \
+                                                         p->d_nphi, p->d_start, p->d_phi0, inter, maps, p->d_tw, \
+                                                         p->pmax, p->d_blu_P, p->d_blu_boff, p->d_blu_foff,      \
+                                                         p->d_bchirp, p->d_bfilt, c.bstride, p->d_mcut)
+    if (c.P == 0) {
+        if (c.nch == 4) { RINGFFT_LAUNCH(4, false); }
+        else if (c.nch == 2) { RINGFFT_LAUNCH(2, false); }
+        else { RINGFFT_LAUNCH(1, false); }
+    } else {
+        if (c.nch == 4) { RINGFFT_LAUNCH(4, true); }
+        else if (c.nch == 2) { RINGFFT_LAUNCH(2, true); }
+        else { RINGFFT_LAUNCH(1, true); }
+    }
+#undef RINGFFT_LAUNCH
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// CORAHIP_K5_BELT_WGS, read at every call: unset -> -1 (automatic), 0 -> the alternating schedule, n > 0 -> W = n
+static int k5_belt_wgs_switch() {
+    const char *e = getenv("CORAHIP_K5_BELT_WGS");
+    if (!e || !*e) return -1;
+    return std::max(0, atoi(e));
+}
+
 // K5 over the F_m cells of `inter` for nnu_valid channels -> maps
 int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter, int nnu_chunk_pad, int nnu_valid,
                        double *maps) {
@@ -458,13 +499,78 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
         StageTimer t(ctx, "ringfft");
         const int G = nnu_chunk_pad / 4;
         static const bool class_times = getenv("CORAHIP_K5_TIMES") != nullptr;   // diagnostics: per-class ms on stderr
-        // The class launches alternate between two streams: every class is a persistent grid that fills the chip, so the
-        // two kernels in flight run one after the other EXCEPT for their tails - the workgroups of the next class start on
-        // the CUs the finishing one frees (12 launches, 0.1-0.3 ms of tail each on one stream).  The per-class timing
-        // switch keeps everything on the context's stream.
         const bool two = !class_times && !K5_STAMPS && p->classes.size() > 1;
         hipStream_t const main_stream = ctx->stream;
         StreamRestore restore{ctx, main_stream};   // (ctx->stream is switched per launch below)
+        const int ncu = ctx->num_cu;
+
+        // ---- the belt (the direct class of the ticketed compile-time kernel) and everything else, with their estimated
+        //      costs in CU ms: B where HBM does not limit the belt, C for the cap classes, which are bound per CU anyway
+        const corahip_sht_plan::ring_class *belt = nullptr;
+        std::vector<std::pair<double, const corahip_sht_plan::ring_class *>> side;   // (cost, class)
+        double B = 0.0, C = 0.0;
+        for (const auto &c : p->classes) {
+            const double cost = 1e-3 * sht_ringfft_item_weight(c) * (double)c.count * ((nnu_valid + c.nch - 1) / c.nch);
+            if (!belt && sht_ringfft_ticketed(c)) {
+                belt = &c;
+                B = cost;
+            } else {
+                side.push_back({cost, &c});
+                C += cost;
+            }
+        }
+        if (belt) {
+            const int rct = sht_k5_tickets(ctx, main_stream);   // (ahead of the fork: ordered before every launch of the call)
+            if (rct) return rct;
+        }
+        // ---- W, the CUs of the belt on the main stream; the cap classes run beside it on the other ncu - W.  Both are
+        //      multiples of 8 (workgroups are dealt round-robin over the 8 XCDs), and where the list has 2- / 1-channel
+        //      classes the side grid is a multiple of 16 / 32, which the XCD pairing of their items needs (ct_remap).
+        //      The belt is given slightly LESS than its share: it then outlives the caps and the helper launch behind
+        //      them (same kernel, same tickets) takes the rest on the CUs the caps have left - an error of the weights
+        //      in that direction costs little (cfg 3: 0.2 ms at W = 64 for 80), in the other direction the caps finish
+        //      alone on ncu - W CUs (+1.2 ms at W = 112, +3.6 ms at 128).
+        const int sw = k5_belt_wgs_switch();
+        int W = 0;
+        if (two && belt && !side.empty() && sw != 0 && ncu >= 16 && ncu % 8 == 0) {
+            if (sw > 0) {
+                W = std::min(std::max(8 * ((sw + 4) / 8), 8), ncu - 8);
+            } else if (B >= 0.2 * ncu && C >= 0.2 * ncu) {      // either side under 0.2 ms of the chip: nothing to share
+                int gran = 8;
+                for (const auto &sc : side) gran = std::max(gran, sc.second->nch == 2 ? 16 : (sc.second->nch == 1 ? 32 : 8));
+                if (ncu % gran) gran = 8;
+                const double share = C / (B + C) * ncu;          // the caps' CUs at an even finish
+                int S = gran * (int)std::ceil(share / gran + 0.1);    // (at least a tenth of a step beyond it)
+                S = std::min(std::max(S, gran), ncu - 8);
+                W = ncu - S;
+            }
+        }
+        if (W > 0) {
+            int rc2 = sht_second_stream(ctx);
+            if (rc2) return rc2;
+            HIP_TRY(hipEventRecord(ctx->ev_fork, main_stream));
+            HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+            restore.forked = true;
+            int rc = ringfft_launch_class(ctx, p, *belt, inter, G, nnu_valid, maps, W);
+            if (rc) return rc;
+            ctx->stream = ctx->stream2;
+            std::stable_sort(side.begin(), side.end(), [](const auto &a, const auto &b) { return a.first > b.first; });   // longest first
+            for (const auto &sc : side)
+                if ((rc = ringfft_launch_class(ctx, p, *sc.second, inter, G, nnu_valid, maps, ncu - W))) return rc;
+            // helper: the belt kernel again, on the CUs the caps leave - it exits at once if no tickets are left
+            if ((rc = ringfft_launch_class(ctx, p, *belt, inter, G, nnu_valid, maps, ncu - W))) return rc;
+            ctx->stream = main_stream;
+            HIP_TRY(hipEventRecord(ctx->ev_join, ctx->stream2));
+            HIP_TRY(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
+            restore.forked = false;                 // (joined here: nothing left for the guard)
+            return 0;
+        }
+
+        // ---- the alternating schedule: every class is a persistent grid that fills the chip, launched on two streams in
+        // turn, so the two kernels in flight run one after the other EXCEPT for their tails - the workgroups of the next
+        // class start on the CUs the finishing one frees (12 launches, 0.1-0.3 ms of tail each on one stream).  The
+        // per-class timing switch keeps everything on the context's stream (and, with CORAHIP_K5_BELT_WGS = n, runs
+        // the belt on n CUs: the reduced-width figure the weight table wants).
         if (two) {
             int rc2 = sht_second_stream(ctx);
             if (rc2) return rc2;
@@ -481,40 +587,15 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
                 (void)hipEventCreate(&ce1);
                 (void)hipEventRecord(ce0, ctx->stream);
             }
-            bool took = false;   // compile-time kernel for this class?
-            const int rct = sht_ringfft_ct(ctx, p, c, inter, G, nnu_valid, maps, &took);
-            if (rct) return rct;   // (StreamRestore puts the caller's stream back)
-            const size_t shm = sizeof(double2) * (size_t)c.nch * c.bstride;
-            const long nitems = (long)c.count * ((nnu_valid + c.nch - 1) / c.nch);
-            const int per_cu = std::max<int>(1, (int)((160 * 1024) / std::max<size_t>(shm, 1)));
-            const int k5_threads = c.threads ? c.threads : K5_THREADS;
-            // (the short classes run narrow workgroups - see the plan - and more of them per CU)
-            dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * std::min(per_cu, k5_threads <= 128 ? 8 : 4)));
-#define RINGFFT_LAUNCH(NCH, BLU)                                                                                     \
-    HIP_TRY(hipFuncSetAttribute((const void *)ringfft_kernel<NCH, BLU>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                160 * 1024));                                                                   \
-    ringfft_kernel<NCH, BLU><<<grid, k5_threads, shm, ctx->stream>>>(c.d_list, c.count, p->nside, p->lmax, G, nnu_valid, p->npix,     \
-                                                         p->d_nphi, p->d_start, p->d_phi0, inter, maps, p->d_tw, \
-                                                         p->pmax, p->d_blu_P, p->d_blu_boff, p->d_blu_foff,      \
-                                                         p->d_bchirp, p->d_bfilt, c.bstride, p->d_mcut)
-            if (took) {
-            } else if (c.P == 0) {
-                if (c.nch == 4) { RINGFFT_LAUNCH(4, false); }
-                else if (c.nch == 2) { RINGFFT_LAUNCH(2, false); }
-                else { RINGFFT_LAUNCH(1, false); }
-            } else {
-                if (c.nch == 4) { RINGFFT_LAUNCH(4, true); }
-                else if (c.nch == 2) { RINGFFT_LAUNCH(2, true); }
-                else { RINGFFT_LAUNCH(1, true); }
-            }
-#undef RINGFFT_LAUNCH
-            LAUNCH_CHECK();
+            const int cus = (class_times && sw > 0 && &c == belt) ? std::min(sw, ncu) : ncu;
+            const int rc = ringfft_launch_class(ctx, p, c, inter, G, nnu_valid, maps, cus);
+            if (rc) return rc;   // (StreamRestore puts the caller's stream back)
             if (class_times) {
                 float ms = 0.f;
                 (void)hipEventRecord(ce1, ctx->stream);
                 (void)hipEventSynchronize(ce1);
                 (void)hipEventElapsedTime(&ms, ce0, ce1);
-                fprintf(stderr, "K5 class P=%d (length %d) rings=%d: %.3f ms\n", c.P, c.P3 ? c.P3 : (c.P ? c.P : c.N), c.count, ms);
+                fprintf(stderr, "K5 class P=%d (length %d) rings=%d: %.3f ms on %d CUs\n", c.P, c.P3 ? c.P3 : (c.P ? c.P : c.N), c.count, ms, cus);
                 (void)hipEventDestroy(ce0);
                 (void)hipEventDestroy(ce1);
             }

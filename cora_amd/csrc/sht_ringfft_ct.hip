@@ -177,6 +177,16 @@ __device__ __forceinline__ static int ct_remap(int v, int nitems) {
     return (((slot >> SH) * 8 + xcd) << SH) + (slot & ((1 << SH) - 1));
 }
 
+// The same pairing for the ticketed item loop of ringfft_direct_ct: v = 8 slot + (blockIdx & 7) with the slot drawn from
+// the counter of that XCD label, so the pairing does not depend on the grid size
+template <int NCH>
+__device__ __forceinline__ static int ct_remap_tk(int v, int nitems) {
+    constexpr int SH = NCH == 2 ? 1 : (NCH == 1 ? 2 : 0);
+    if (SH == 0 || (nitems & ((8 << SH) - 1)) != 0) return v;
+    const int slot = v >> 3, xcd = v & 7;
+    return (((slot >> SH) * 8 + xcd) << SH) + (slot & ((1 << SH) - 1));
+}
+
 // ------------------------------------------------------------------------------------
 // direct class: h = N = 2^k (N >= 2048 so that the first-pass stride is a multiple of the 128-element padding period)
 // ------------------------------------------------------------------------------------
@@ -184,7 +194,7 @@ template <int N, int NCH, int MC, int T>
 __global__ void __launch_bounds__(T)
 ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, int G, int nnu, long npix,
                   const int64_t *__restrict__ start_a, const double *__restrict__ phi0_a,
-                  const double *inter, double *maps, const int32_t *__restrict__ mcut) {   // (not __restrict__: see ringfft_blu_ct)
+                  const double *inter, double *maps, const int32_t *__restrict__ mcut, int *tickets) {   // (not __restrict__: see ringfft_blu_ct)
     constexpr int PK = K5_PK_DIRECT;
     constexpr int R0 = Sch<N>::R0, R1 = Sch<N>::R1, R2 = Sch<N>::R2;
     static_assert(R0 == 16 && R1 == 16, "digit map of the fused store assumes 16 x 16 x R2");
@@ -197,6 +207,18 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
     const int L = lmax + 1;
     const int ngrp = (nnu + NCH - 1) / NCH;
     const int nitems = nlist * ngrp;
+
+    // Items are drawn from a device counter (zeroed per call by sht_ringfft), not strided over the grid: a second launch
+    // of this kernel on the same counter - the helper grid behind the cap classes - then takes whatever the first has
+    // not reached, and a workgroup that finds the counter exhausted leaves at once.  Nothing waits on a ticket.
+    // NCH < 4: one counter per XCD label, v = 8 slot + label, so that the items sharing 64-byte cells stay on one L2.
+    constexpr bool PERX = NCH < 4;
+    __shared__ int s_tk[2];
+    int *ctr = tickets + (PERX ? (int)(blockIdx.x & 7) : 0);
+    // (the address is made opaque where it is used: for a uniform address the compiler rewrites the atomic into its
+    //  wave-wide form, whose result is read back right behind the request - a memory round trip inside pass 1)
+    auto vitem_of = [&](int t) { return PERX ? 8 * t + (int)(blockIdx.x & 7) : t; };
+    int tkn = 0;            // (thread 0) ticket requested ahead of where it is published
 
     // per-thread twiddles, fixed for the whole kernel
     double2 wH, wA, wB;     // e^{i pi j0 / N}, e^{2 pi i j0 / N}, e^{2 pi i j1 / (N / R0)}
@@ -228,16 +250,22 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
         sincospi((double)T * phs, &s, &c);
         phstepS = make_double2(c, s);
     }
-    int vitem = blockIdx.x;
-    if (vitem < nitems) fe.prefetch(cell_ptr(ct_remap<NCH>(vitem, nitems)), L, tid0);
+    if (tid0 == 0) {
+        tkn = atomicAdd(ctr, 2);                          // the first two items of this workgroup
+        s_tk[0] = tkn;
+        s_tk[1] = tkn + 1;
+    }
+    __syncthreads();
+    int vitem = vitem_of(__builtin_amdgcn_readfirstlane(s_tk[0]));
+    if (vitem < nitems) fe.prefetch(cell_ptr(ct_remap_tk<NCH>(vitem, nitems)), L, tid0);
     fe.touch();   // (so that the prefetch is known to be complete on BOTH edges into the loop: no wait in the fold)
-    for (; vitem < nitems; vitem += gridDim.x) {
+    while (vitem < nitems) {
         // the thread index is made opaque once per item: otherwise every LDS / pixel address of every pass (all of them
         // functions of tid only) is hoisted out of this loop as a loop invariant, ~60 registers of them spill, and a
         // scratch reload - a vmcnt-ordered load - in the store pass waits for the whole prefetch of the next item
         int tid = tid0;
         asm volatile("" : "+v"(tid));
-        const int item = ct_remap<NCH>(vitem, nitems);
+        const int item = ct_remap_tk<NCH>(vitem, nitems);
         const int ring = ring_list[item / ngrp];
         const int ch0 = (item % ngrp) * NCH;
         const long start = start_a[ring];
@@ -250,9 +278,11 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
             fe.fold(sm, cell_ptr(item), Lr, n, p0, p1, tid);
         }
         // the next item's cells: two passes (~7k cycles) ahead of the store pass, in front of which they are waited for
-        // (unconditional - the last iteration re-reads an item - so that the compiler can COUNT these loads in its
-        //  vmcnt waits; behind an `if` it assumes they may be absent and waits for everything instead)
-        const double *ncell = cell_ptr(ct_remap<NCH>(min(vitem + (int)gridDim.x, nitems - 1), nitems));
+        // (unconditional - with the counter exhausted the current item is read again - so that the compiler can COUNT
+        //  these loads in its vmcnt waits; behind an `if` it assumes they may be absent and waits for everything instead).
+        // Its ticket was published before the barrier at the top of this item (by the previous item's store pass).
+        const int vnext = vitem_of(__builtin_amdgcn_readfirstlane(s_tk[1]));
+        const double *ncell = cell_ptr(ct_remap_tk<NCH>(vnext < nitems ? vnext : vitem, nitems));
         fe.template prefetch<0>(ncell, L, tid);
         __syncthreads();
         // ---- pass 1 with the Hermitian step: butterfly j0 of channel ch reads X_k, k = j0 + r Q0, and the mirror
@@ -296,6 +326,14 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
         }
         __syncthreads();
         ct_pass<PK, N, NCH, BS, Q0, R1, 1, false, T>(sm, wB, tid);
+        // the ticket of the item after the next, requested here and published in the store pass: it is the youngest memory
+        // request of the item (its wait is the wait for the prefetch that is there anyway), in flight across the barrier,
+        // and alive in a register only where nothing else is (held across a pass it was spilled: a vmcnt(0) on the spot)
+        if (tid0 == 0) {
+            auto c = (__attribute__((address_space(1))) int *)ctr;   // (global, not flat: a flat request counts in lgkmcnt too)
+            asm volatile("" : "+v"(c));
+            tkn = __hip_atomic_fetch_add(c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         __syncthreads();
         // ---- last pass (radix R2 on contiguous elements, no twiddles) with the pixel store: butterfly t = 16 k0 + k1
         //      holds the natural indices k0 + 16 k1 + 256 r.  Lane bits: 0-2 = k0 low, 3-5 = k1 low, 6 = k0 high,
@@ -304,6 +342,7 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
             constexpr int TOT = NCH * 256;
             constexpr int IT = (TOT + T - 1) / T;
             fe.touch();
+            if (tid0 == 0) s_tk[1] = tkn;                 // (read behind the barrier at the top of the next item)
 #pragma unroll
             for (int it = 0; it < IT; it++) {
                 const int idx = tid + it * T;
@@ -323,6 +362,7 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
                 }
             }
         }
+        vitem = vnext;
     }
 }
 
@@ -749,23 +789,29 @@ ringana_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
 // ------------------------------------------------------------------------------------
 template <int N, int NCH, int MC, int T>
 static int launch_direct(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_plan *p,
-                         const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps) {
+                         const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps, int cu_limit) {
     constexpr int PK = K5_PK_DIRECT;
     constexpr int BS = fpc(N) + 1 + K5_CH_SKEW;
     const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu + NCH - 1) / NCH);
     const int per_cu = std::max<int>(1, (int)((160 * 1024) / shm));
-    dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
+    dim3 grid((unsigned)std::min<long>(nitems, (long)cu_limit * per_cu));
+    if (!ctx->k5_tickets) {
+        corahip_set_error("ring FFT: the ticket counters of the context are missing");
+        return CORAHIP_ESTATE;
+    }
+    // (the kernel's ticket words are static LDS: the dynamic part is what the class needs, not the whole 160 KB)
+    static_assert(sizeof(double2) * (size_t)NCH * BS + 64 <= 160 * 1024, "channel buffers + ticket words fit the LDS");
     HIP_TRY(hipFuncSetAttribute((const void *)ringfft_direct_ct<N, NCH, MC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
+                                (int)shm));
     ringfft_direct_ct<N, NCH, MC, T><<<grid, T, shm, stream>>>(c.d_list, c.count, p->lmax, G, nnu, p->npix, p->d_start,
-                                                               p->d_phi0, inter, maps, p->d_mcut);
+                                                               p->d_phi0, inter, maps, p->d_mcut, ctx->k5_tickets);
     LAUNCH_CHECK();
     return 0;
 }
 template <int P, int NCH, int MC, int T>
 static int launch_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_plan *p,
-                      const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps,
+                      const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps, int cu_limit,
                       const int64_t *d_foff = nullptr, const double2 *d_filt = nullptr) {
     if (!d_foff) {
         d_foff = p->d_blu_foff;
@@ -776,7 +822,7 @@ static int launch_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_pl
     const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu + NCH - 1) / NCH);
     const int per_cu = std::max<int>(1, (int)((160 * 1024) / shm));
-    dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
+    dim3 grid((unsigned)std::min<long>(nitems, (long)cu_limit * per_cu));
     HIP_TRY(hipFuncSetAttribute((const void *)ringfft_blu_ct<P, NCH, MC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024));
     ringfft_blu_ct<P, NCH, MC, T><<<grid, T, shm, stream>>>(c.d_list, c.count, p->nside, p->lmax, G, nnu, p->npix, p->d_nphi,
@@ -802,28 +848,28 @@ static int launch_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_pl
 // error status only (0 = OK, CORAHIP_E* < 0 or a positive hipError_t): hipErrorInvalidValue is 1, so "launched" must
 // never share the int with the status
 int sht_ringfft_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c, const double *inter,
-                   int G, int nnu, double *maps, bool *took) {
+                   int G, int nnu, double *maps, int cu_limit, bool *took) {
     *took = false;
     int rc = -1;
     hipStream_t st = ctx->stream;
     if (c.P == 0) {
-        if (c.N == 2048) rc = launch_direct<2048, 4, 4, 512>(ctx, st, p, c, inter, G, nnu, maps);
-        else if (c.N == 4096) rc = launch_direct<4096, 2, 8, 512>(ctx, st, p, c, inter, G, nnu, maps);
+        if (c.N == 2048) rc = launch_direct<2048, 4, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
+        else if (c.N == 4096) rc = launch_direct<4096, 2, 8, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
         else return 0;
     } else {
         // P3 = 8192 / 6144: one channel fills the LDS.  Measured at the cfg-5 rank share (128 channels; the generic kernel
         // took 30.6 ms for the two classes): 512 threads (two waves per SIMD, but the radix-32 / 24 butterflies then spill:
         // 268 / 72 bytes) 16.5 / 10.1 ms, 256 threads (one wave per SIMD, no spill) 13.8 / 10.8 ms for P = 8192 / 6144:
         // each takes the faster form.
-        if (c.P3 == 8192) rc = launch_blu<8192, 1, 16, 256>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 6144) rc = launch_blu<6144, 1, 8, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 2560) rc = launch_blu<2560, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 3584) rc = launch_blu<3584, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 3072) rc = launch_blu<3072, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 1536) rc = launch_blu<1536, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P == 4096) rc = launch_blu<4096, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps);
-        else if (c.P == 2048) rc = launch_blu<2048, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps);
-        else if (c.P == 1024) rc = launch_blu<1024, 4, 2, 256>(ctx, st, p, c, inter, G, nnu, maps);   // (256 threads, two workgroups per CU: 0.61 -> 0.54 ms)
+        if (c.P3 == 8192) rc = launch_blu<8192, 1, 16, 256>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 6144) rc = launch_blu<6144, 1, 8, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 2560) rc = launch_blu<2560, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 3584) rc = launch_blu<3584, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 3072) rc = launch_blu<3072, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P3 == 1536) rc = launch_blu<1536, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
+        else if (c.P == 4096) rc = launch_blu<4096, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
+        else if (c.P == 2048) rc = launch_blu<2048, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
+        else if (c.P == 1024) rc = launch_blu<1024, 4, 2, 256>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);   // (256 threads, two workgroups per CU: 0.61 -> 0.54 ms)
         else return 0;
     }
     if (rc) return rc;
@@ -1096,6 +1142,36 @@ int sht_ringana_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sh
 #undef ANA_ARGS
     if (rc) return rc;
     *took = true;
+    return 0;
+}
+
+bool sht_ringfft_ticketed(const corahip_sht_plan::ring_class &c) { return c.P == 0 && (c.N == 2048 || c.N == 4096); }
+
+// CU microseconds per item of each kernel instantiation, for the split of the CUs between the belt and the cap classes
+// (sht_ringfft).  Measured on one MI355X with the per-class diagnostic (CORAHIP_K5_TIMES=1, tools/k5_probe.py): time of
+// the class x CUs it ran on / items, at nside 1024 / lmax 2048 / 256 channels (lengths <= 4096) and at nside 2048 /
+// lmax 4096 / 128 channels (direct 4096, 6144, 8192).  The belt entries are from runs on 96 of the 256 CUs
+// (CORAHIP_K5_BELT_WGS=96 beside CORAHIP_K5_TIMES: 13.55 / 34.65 ms), where HBM does not limit it; on the whole chip
+// an item costs 11.8 / 14.2.  HISTORY.md ("K5: belt and cap classes side by side") has the measurement.
+double sht_ringfft_item_weight(const corahip_sht_plan::ring_class &c) {
+    struct W { int len; double us; };
+    static const W direct[] = {{2048, 9.9}, {4096, 12.7}};
+    static const W blu[] = {{8192, 26.1}, {6144, 20.5}, {4096, 15.0}, {3584, 14.3}, {3072, 13.3}, {2560, 12.4},
+                            {2048, 12.6}, {1536, 10.6}, {1024, 6.8}};
+    if (c.P == 0) {
+        for (const W &w : direct)
+            if (w.len == c.N) return w.us;
+        return 13.0;      // the power-of-two cap rings (run-time kernel, a few items)
+    }
+    const int len = c.P3 ? c.P3 : c.P;
+    for (const W &w : blu)
+        if (w.len == len) return w.us;
+    return len > 4096 ? 26.1 * len / 8192 : 5.7;   // run-time kernel: lengths <= 512 at the plans in use
+}
+
+int sht_k5_tickets(corahip_ctx *ctx, hipStream_t stream) {
+    if (!ctx->k5_tickets) HIP_TRY(hipMalloc((void **)&ctx->k5_tickets, sizeof(int) * K5_NTICKETS));
+    HIP_TRY(hipMemsetAsync(ctx->k5_tickets, 0, sizeof(int) * K5_NTICKETS, stream));
     return 0;
 }
 
