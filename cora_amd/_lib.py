@@ -108,6 +108,13 @@ SIGNATURES = {
     "corahip_der1_alm_prep": (c_int, [c_void_p, c_void_p, PTR, c_int, c_int, c_int, PTR]),
     "corahip_der1_combine": (c_int, [c_void_p, c_void_p, PTR, c_int, c_int, PTR, PTR, c_int, PTR, PTR]),
     "corahip_radial_gradient": (c_int, [c_void_p, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
+    "corahip_slice_mix": (c_int, [c_void_p, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
+    "corahip_slice_diff2": (c_int, [c_void_p, PTR, PTR, PTR, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
+    "corahip_slice_moments_workspace_bytes": (c_int, [c_int, ctypes.c_long, ctypes.POINTER(c_size_t)]),
+    "corahip_slice_moments": (c_int, [c_void_p, PTR, ctypes.c_long, PTR, c_int, ctypes.c_long, c_void_p, c_size_t, PTR,
+                                      PTR]),
+    "corahip_bias_field": (c_int, [c_void_p, PTR, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
+    "corahip_lognormal": (c_int, [c_void_p, PTR, PTR, PTR, c_double, c_int, ctypes.c_long, ctypes.c_long, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -946,6 +953,247 @@ class Context:
         _check(self.lib.corahip_radial_gradient(self.h, self._f64(f), self._f64(cdev),
                                                 None if scale is None else self._f64(scale), int(n), int(npix),
                                                 self._f64(out)))
+        return out
+
+    # -- LSS chain: bias, linear dynamics, Fingers of God, map (csrc/lsschain.hip) -----------------------------------
+    def _rowvec(self, v, n, name):
+        """``[n]`` host array, scalar (broadcast) or device tensor -> device float64 [n]."""
+        torch = _torch()
+        if isinstance(v, torch.Tensor):
+            v = v.to(device=self.device, dtype=torch.float64).reshape(-1)
+            if v.numel() == 1:
+                v = v.expand(n)
+            v = v.contiguous()
+        else:
+            h = np.asarray(v, dtype=np.float64)
+            if h.ndim == 0:
+                h = np.full(n, float(h))
+            v = self.to_device(h.reshape(-1))
+        if v.numel() != n:
+            raise ValueError("Array %s has %d entries, expected %d" % (name, v.numel(), n))
+        return v
+
+    def _field2d(self, f, name):
+        torch = _torch()
+        if not isinstance(f, torch.Tensor) or f.dim() != 2:
+            raise ValueError("%s must be a [n, ncol] device tensor (got shape %r)" % (name, tuple(getattr(f, "shape", ()))))
+        if f.dtype != torch.float64 or not f.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 tensor" % name)
+        return int(f.shape[0]), int(f.shape[1])
+
+    @staticmethod
+    def _overlap(a, abytes, b, bbytes):
+        return a.data_ptr() < b.data_ptr() + bbytes and b.data_ptr() < a.data_ptr() + abytes
+
+    @staticmethod
+    def slice_mix_ranges(K, band_cut=None):
+        """Host side of the skipping rule of ``slice_mix``: ``(K', ranges)`` for a host matrix ``K`` [n, n].
+
+        With ``band_cut`` the entries with ``|K_ij| < band_cut * max_j |K_ij|`` are zeroed in the copy ``K'`` (else
+        ``K'`` is ``K``).  ``ranges`` is int32 [ceil(n / 16), 2]: for each block of 16 output rows the range
+        ``[klo, khi)`` of input slices that holds every non-zero entry of those rows of ``K'``, widened to multiples
+        of the MFMA depth 4 (``khi`` may exceed n by up to 3: the kernel pads with zeros); (0, 0) for an all-zero
+        block."""
+        K = np.asarray(K, dtype=np.float64)
+        if K.ndim != 2 or K.shape[0] != K.shape[1]:
+            raise ValueError("K must be a square matrix (got shape %r)" % (K.shape,))
+        n = K.shape[0]
+        if band_cut is not None:
+            K = np.where(np.abs(K) < float(band_cut) * np.abs(K).max(axis=1, keepdims=True), 0.0, K)
+        nb = (n + 15) // 16
+        ranges = np.zeros((nb, 2), dtype=np.int32)
+        for b in range(nb):
+            cols = np.nonzero((K[16 * b:16 * b + 16] != 0).any(axis=0))[0]
+            if cols.size:
+                ranges[b] = (cols[0] // 4 * 4, (cols[-1] + 4) // 4 * 4)
+        return K, ranges
+
+    def slice_mix(self, K, f, out=None, band_cut=None, skip=True, ranges=None):
+        """``out = K @ f`` for a device field ``f`` [n, ncol] and a matrix ``K`` [n, n] (host array or device tensor),
+        1 <= n <= 4096, with FP64 MFMA.  ``out`` must not overlap ``f`` (ValueError).
+
+        The host passes, per block of 16 output rows, the range of input slices outside which the rows of ``K`` are
+        exactly zero (:meth:`slice_mix_ranges`); the kernel forms no product outside it.  Those terms are exact zeros:
+        for finite ``f`` the result does not depend on the skipping (``skip=False`` passes no ranges and gives the
+        same bits).  A non-finite ``f`` in a skipped slice does not propagate, where a dense product gives NaN.
+
+        ``band_cut``: entries with ``|K_ij| < band_cut * max_j |K_ij|`` are zeroed in a copy of ``K`` first, which
+        narrows the ranges of a banded kernel.  What that drops from element (i, p) is bounded by
+        ``band_cut * max_j |K_ij| * sum_j |f_jp|``.  Default ``None``: exact, like the reference's ``np.matmul``.
+        Two calls on the same inputs return identical bits (no atomics).
+
+        ``ranges``: a device int32 tensor from an earlier ``to_device(slice_mix_ranges(K)[1], np.int32)`` for the same
+        device matrix ``K``: the call then does no host work on ``K`` (repeated products with one matrix)."""
+        torch = _torch()
+        n, ncol = self._field2d(f, "f")
+        if ranges is not None:
+            if not isinstance(K, torch.Tensor) or band_cut is not None or tuple(K.shape) != (n, n):
+                raise ValueError("slice_mix: ranges go with a device matrix K [n, n] and no band_cut")
+            if ranges.dtype != torch.int32 or tuple(ranges.shape) != ((n + 15) // 16, 2) or not ranges.is_contiguous():
+                raise ValueError("slice_mix: ranges must be int32 [ceil(n / 16), 2]")
+            return self._slice_mix_launch(K, f, out, ranges, n, ncol)
+        Kh = K.detach().cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K, dtype=np.float64)
+        if Kh.shape != (n, n):
+            raise ValueError("Array K has the wrong shape (got %r, expected %r)" % (tuple(Kh.shape), (n, n)))
+        if not 1 <= n <= 4096:
+            raise ValueError("slice_mix takes 1 <= n <= 4096 slices (got %d)" % n)
+        Kc, ranges = self.slice_mix_ranges(Kh, band_cut)
+        if isinstance(K, torch.Tensor) and band_cut is None and K.dtype == torch.float64 and K.is_contiguous() \
+                and K.device == self.device:
+            Kd = K
+        else:
+            Kd = self.to_device(Kc)
+        rdev = self.to_device(ranges, dtype=np.int32) if skip else None
+        return self._slice_mix_launch(Kd, f, out, rdev, n, ncol)
+
+    def _slice_mix_launch(self, Kd, f, out, rdev, n, ncol):
+        torch = _torch()
+        if out is None:
+            out = self.empty((n, ncol))
+        if tuple(out.shape) != (n, ncol) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 [%d, %d] tensor" % (n, ncol))
+        if self._overlap(out, n * ncol * 8, f, n * ncol * 8) or self._overlap(out, n * ncol * 8, Kd, n * n * 8):
+            raise ValueError("slice_mix: out overlaps an input")
+        _check(self.lib.corahip_slice_mix(self.h, self._f64(Kd), self._f64(f), None if rdev is None else self._p(rdev),
+                                          n, ncol, self._f64(out)))
+        return out
+
+    @staticmethod
+    def diff2_coefficients(x):
+        """Host tables of ``lssutil.diff2`` (cora/signal/lssutil.py:99-185) for coordinates ``x`` [n], n >= 4:
+        ``(coef [n, 4], first [n])``.  Output row i is ``((c0 w0 + c1 w1) + c2 w2) + c3 w3`` over the input rows
+        ``first[i] .. first[i] + 3`` (``first[i] = min(max(i - 2, 0), n - 4)``, the rule the kernel applies).  Interior
+        rows 2 .. n - 2 hold ``(alpha, beta, -(alpha + beta + gamma), gamma)`` of the reference, rows 0, 1 and n - 1 its
+        one-sided 4-point weights, each from the reference's expression."""
+        x = np.asarray(x, dtype=np.float64)
+        n = x.size
+        if x.ndim != 1 or n < 4:
+            raise ValueError("diff2 needs at least 4 coordinates along the axis (got shape %r)" % (x.shape,))
+        coef = np.zeros((n, 4))
+        for i in range(2, n - 1):
+            dm2 = x[i] - x[i - 2]
+            dm1 = x[i] - x[i - 1]
+            dp1 = x[i + 1] - x[i]
+            alpha = 2 * (dp1 - dm1) / (dm2 * (dm2 + dp1) * (dm2 - dm1))
+            beta = 2 * (dm2 - dp1) / (dm1 * (dm2 - dm1) * (dm1 + dp1))
+            gamma = 2 * (dm2 + dm1) / (dp1 * (dm1 + dp1) * (dm2 + dp1))
+            coef[i] = (alpha, beta, -(alpha + beta + gamma), gamma)
+        dp1, dp2, dp3 = x[1] - x[0], x[2] - x[0], x[3] - x[0]
+        coef[0] = (2 * (dp1 + dp2 + dp3) / (dp1 * dp2 * dp3),
+                   -2 * (dp2 + dp3) / (dp1 * (dp1 - dp2) * (dp1 - dp3)),
+                   2 * (dp1 + dp3) / ((dp1 - dp2) * dp2 * (dp2 - dp3)),
+                   2 * (dp1 + dp2) / ((dp1 - dp3) * dp3 * (-dp2 + dp3)))
+        dm1, dp1, dp2 = x[1] - x[0], x[2] - x[1], x[3] - x[1]
+        coef[1] = (2 * (dp1 + dp2) / (dm1 * (dm1 + dp1) * (dm1 + dp2)),
+                   2 * (dm1 - dp1 - dp2) / (dm1 * dp1 * dp2),
+                   2 * (dm1 - dp2) / (dp1 * (dm1 + dp1) * (dp1 - dp2)),
+                   -2 * (dm1 - dp1) / ((dp1 - dp2) * dp2 * (dm1 + dp2)))
+        dm1, dm2, dm3 = x[-1] - x[-2], x[-1] - x[-3], x[-1] - x[-4]
+        coef[n - 1] = (2 * (dm1 + dm2) / ((dm1 - dm3) * dm3 * (-dm2 + dm3)),
+                       2 * (dm1 + dm3) / ((dm1 - dm2) * dm2 * (dm2 - dm3)),
+                       -2 * (dm2 + dm3) / (dm1 * (dm1 - dm2) * (dm1 - dm3)),
+                       2 * (dm1 + dm2 + dm3) / (dm1 * dm2 * dm3))
+        first = np.clip(np.arange(n) - 2, 0, n - 4)
+        return coef, first
+
+    def slice_diff2(self, f, x, g=None, h=None, s=None, t=None, out=None):
+        """``lssutil.diff2(f, x, axis=0)`` of a device field f [n, ncol], n >= 4, equal to the reference bit for bit
+        (the reference's operation order, no contraction).  With ``g``, ``h`` [n, ncol] and per-row factors ``s``,
+        ``t``: ``out = (h + s[:, None] * g) + d2 * t[:, None]`` in one pass.  ``f=None`` (``x`` unused): ``out = h +
+        s[:, None] * g``.  ``out`` must not overlap ``f``."""
+        if (g is None) != (h is None):
+            raise ValueError("slice_diff2: g and h come together")
+        ref = f if f is not None else g
+        if ref is None:
+            raise ValueError("slice_diff2 needs f or (g, h)")
+        n, ncol = self._field2d(ref, "f" if f is not None else "g")
+        cdev = None
+        if f is not None:
+            coef, _ = self.diff2_coefficients(x)
+            if coef.shape[0] != n:
+                raise ValueError("x has %d entries, f %d rows" % (coef.shape[0], n))
+            cdev = self.to_device(coef)
+        for a, name in ((g, "g"), (h, "h")):
+            if a is not None and self._field2d(a, name) != (n, ncol):
+                raise ValueError("Array %s has the wrong shape (got %r, expected %r)" % (name, tuple(a.shape), (n, ncol)))
+        sd = td = None
+        if g is not None:
+            sd = self._rowvec(s, n, "s")
+            td = self._rowvec(t, n, "t") if f is not None else None
+        if out is None:
+            out = self.empty((n, ncol))
+        if self._field2d(out, "out") != (n, ncol):
+            raise ValueError("out has shape %r, expected %r" % (tuple(out.shape), (n, ncol)))
+        if f is not None and self._overlap(out, n * ncol * 8, f, n * ncol * 8):
+            raise ValueError("slice_diff2: out overlaps f")
+        opt = lambda a: None if a is None else self._f64(a)  # noqa: E731
+        _check(self.lib.corahip_slice_diff2(self.h, opt(f), opt(cdev), opt(g), opt(h), opt(sd), opt(td), n, ncol,
+                                            self._f64(out)))
+        return out
+
+    def slice_moments(self, f, c=None):
+        """``(sum_p (f[i, p] - c[i]), sum_p (f[i, p] - c[i])**2)`` per row of a device field f [n, ncol]; ``f`` may be a
+        view with a row stride larger than ncol (unit column stride), ``c`` device [n] or None (= 0).  Fixed summation
+        order: identical bits from call to call."""
+        torch = _torch()
+        if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.dtype != torch.float64 or f.device != self.device:
+            raise ValueError("slice_moments takes a float64 [n, ncol] device tensor")
+        n, ncol = int(f.shape[0]), int(f.shape[1])
+        ld = int(f.stride(0)) if n > 1 else ncol
+        if n < 1 or ncol < 1 or (ncol > 1 and f.stride(1) != 1) or ld < ncol:
+            raise ValueError("slice_moments: rows must be contiguous, row stride >= ncol")
+        if c is not None:
+            c = self._rowvec(c, n, "c")
+        nbytes = c_size_t()
+        _check(self.lib.corahip_slice_moments_workspace_bytes(n, ncol, ctypes.byref(nbytes)))
+        work = torch.empty(int(nbytes.value) // 8, dtype=torch.float64, device=self.device)
+        sums = self.empty((2, n))
+        _check(self.lib.corahip_slice_moments(self.h, c_void_p(f.data_ptr()), ld, None if c is None else self._f64(c), n,
+                                              ncol, self._p(work), int(nbytes.value), self._f64(sums[0]),
+                                              self._f64(sums[1])))
+        return sums[0], sums[1]
+
+    def bias_field(self, delta, c1, c2=None, m2=None, out=None):
+        """``out = c1[:, None] * delta + c2[:, None] * (delta**2 - m2[:, None])`` (``c2 is None``: exactly ``c1[:, None] *
+        delta``) for a device field [n, ncol]; ``out`` may be ``delta`` itself."""
+        n, ncol = self._field2d(delta, "delta")
+        if (c2 is None) != (m2 is None):
+            raise ValueError("bias_field: c2 and m2 come together")
+        c1 = self._rowvec(c1, n, "c1")
+        if c2 is not None:
+            c2, m2 = self._rowvec(c2, n, "c2"), self._rowvec(m2, n, "m2")
+        if out is None:
+            out = self.empty((n, ncol))
+        if self._field2d(out, "out") != (n, ncol):
+            raise ValueError("out has shape %r, expected %r" % (tuple(out.shape), (n, ncol)))
+        if out.data_ptr() != delta.data_ptr() and self._overlap(out, n * ncol * 8, delta, n * ncol * 8):
+            raise ValueError("bias_field: out partly overlaps delta")
+        _check(self.lib.corahip_bias_field(self.h, self._f64(delta), self._f64(c1), None if c2 is None else self._f64(c2),
+                                           None if m2 is None else self._f64(m2), n, ncol, self._f64(out)))
+        return out
+
+    def lognormal(self, f, half_var, out=None, prefactor=1.0, row_scale=None):
+        """``out = ((exp(f - half_var[:, None]) - 1) * prefactor) * row_scale[:, None]`` for a device field f [n, ncol];
+        ``half_var=None``: no transform (``out = (f * prefactor) * row_scale``).  ``out`` [n, ncol] may be ``f`` itself
+        or a view with a larger row stride, e.g. plane 0 ``m[:, 0]`` of a map ``m`` [n, 4, ncol]."""
+        torch = _torch()
+        n, ncol = self._field2d(f, "f")
+        hv = None if half_var is None else self._rowvec(half_var, n, "half_var")
+        rs = None if row_scale is None else self._rowvec(row_scale, n, "row_scale")
+        if out is None:
+            out = self.empty((n, ncol))
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, ncol) or out.dtype != torch.float64 \
+                or out.device != self.device:
+            raise ValueError("Given output array is incompatible.")
+        ld = int(out.stride(0)) if n > 1 else ncol
+        if (ncol > 1 and out.stride(1) != 1) or ld < ncol:
+            raise ValueError("Given output array is incompatible.")
+        inplace = out.data_ptr() == f.data_ptr() and ld == ncol
+        if not inplace and self._overlap(out, ((n - 1) * ld + ncol) * 8, f, n * ncol * 8):
+            raise ValueError("lognormal: out partly overlaps f")
+        _check(self.lib.corahip_lognormal(self.h, self._f64(f), None if hv is None else self._f64(hv),
+                                          None if rs is None else self._f64(rs), float(prefactor), n, ncol, ld,
+                                          c_void_p(out.data_ptr())))
         return out
 
     # -- n3: xi(r) -> C_l --------------------------------------------------------------

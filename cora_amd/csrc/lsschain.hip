@@ -1,0 +1,509 @@
+// lsschain.hip - the steps of cora/signal/lss.py around the Zel'dovich step, on fields [n, ncol] (row = slice, float64,
+// row-major): Lagrangian bias (GenerateBiasedFieldBase.process, lss.py:556-603), linear dynamics
+// (LinearDynamics.process, :862-918), Fingers of God (FingersOfGod.process, :1162-1220) and the map
+// (BiasedLSSToMap.process, :944-993), with lssutil's diff2 and lognormal_transform.
+//
+//   slice_mix_kernel       out = K f, K [n, n]: FP64 MFMA (v_mfma_f64_16x16x4_f64), M = output slice, N = columns,
+//                          K-dimension = input slice.  A workgroup owns 128 output rows x 128 columns (4 waves of
+//                          64 x 64); for n <= 128 every element of f leaves HBM once and every element of out is
+//                          written once; for larger n the row blocks of a column tile are neighbours in the grid, so the
+//                          re-reads of f are served by the L2.  K comes through LDS from the L2.
+//                          Skipping: per block of 16 output rows the host gives the range [klo, khi) of input slices
+//                          (multiples of the MFMA depth 4) whose K entries are not all exactly zero; MFMAs outside it
+//                          are not issued and chunks of 16 input slices outside the union of the workgroup's ranges
+//                          are not loaded.  Skipped terms are exact zeros: for finite f the result is the same with
+//                          and without skipping, bit for bit (the remaining products are accumulated in the same
+//                          order; adding +0 changes nothing).  A non-finite f in a skipped slice does NOT propagate
+//                          (0 * inf would be NaN in a dense product).  No atomics: the sum order is fixed.
+//   slice_diff2_kernel     lssutil.diff2 along axis 0 from a host table of coefficients [n][4], rows kept in registers
+//                          (every element of f read once), optional fused epilogue (h + s g) + d2 t.
+//   slice_moments_*        per-row sum (f - c), sum (f - c)^2 in a fixed order (block partials, ordered final pass)
+//   bias_field_kernel      c1 f + c2 (f^2 - m2)
+//   lognormal_kernel       (exp(f - hv) - 1) pre rs, into a strided destination
+// Rows may be only 8-byte aligned (odd ncol): the streaming kernels use 16-byte accesses when every row start is
+// 16-byte aligned and 8-byte ones otherwise.  All element offsets are 64-bit.
+#include <type_traits>
+
+#include "common.h"
+#include "glibc_exp.h"
+
+namespace {
+
+constexpr int SM_WAVES = 4;            // waves per workgroup
+constexpr int SM_T = 128, SM_K = 16;   // slice_mix: output tile edge, input slices per LDS chunk
+constexpr int SM_NT = 64 * SM_WAVES;   // threads per workgroup
+constexpr int SM_UT = 16 / SM_WAVES;   // 16-row tiles per wave: a wave owns 16 SM_UT rows x 64 columns
+
+// vec: ncol even and f 16-byte aligned, so that the f tile can be read 16 bytes per lane
+__global__ void __launch_bounds__(SM_NT, SM_WAVES / 2)
+slice_mix_kernel(const double *__restrict__ K, const double *__restrict__ f, const int *__restrict__ rng, int n, long ncol,
+                 int nrb, int vec, double *__restrict__ out) {
+    constexpr int AS = SM_K + 1, BS = SM_T + 4;
+    constexpr int NA = SM_T * SM_K / SM_NT, NB = SM_K * SM_T / SM_NT;
+    __shared__ double As[2][SM_T * AS];
+    __shared__ __attribute__((aligned(16))) double Bs[2][SM_K * BS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ri = lane & 15, kq = lane >> 4;
+    const int rb = (int)(blockIdx.x % (unsigned)nrb);
+    const long cb = (long)(blockIdx.x / (unsigned)nrb);
+    const int row0 = rb * SM_T;
+    const long col0 = cb * SM_T;
+    const int wr = (wave >> 1) * (16 * SM_UT), wc = (wave & 1) * 64;   // the wave's sub-tile
+    const int n4 = (n + 3) & ~3;
+
+    // ranges of the wave's 16-row tiles (wave-uniform) and their union over the workgroup's eight
+    int klo[SM_UT], khi[SM_UT], blo = n4, bhi = 0;
+#pragma unroll
+    for (int t = 0; t < SM_T / 16; t++) {
+        const int r16 = row0 + 16 * t;
+        int lo = 0, hi = 0;
+        if (r16 < n) {
+            lo = rng ? rng[2 * (r16 >> 4)] : 0;
+            hi = rng ? rng[2 * (r16 >> 4) + 1] : n4;
+            lo = max(0, lo) & ~3;
+            hi = min(n4, (hi + 3) & ~3);
+            if (hi > lo) blo = min(blo, lo), bhi = max(bhi, hi);
+        }
+#pragma unroll
+        for (int u = 0; u < SM_UT; u++)
+            if (t == (wr >> 4) + u) klo[u] = lo, khi[u] = hi;
+    }
+#pragma unroll
+    for (int u = 0; u < SM_UT; u++) {
+        klo[u] = __builtin_amdgcn_readfirstlane(klo[u]);
+        khi[u] = __builtin_amdgcn_readfirstlane(khi[u]);
+    }
+    d4_t acc[SM_UT][4];
+#pragma unroll
+    for (int u = 0; u < SM_UT; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) acc[u][v] = (d4_t){0.0, 0.0, 0.0, 0.0};
+
+    // global -> registers -> LDS, split so that the loads of chunk c+1 are in flight while chunk c is multiplied
+    double ra[NA], rb0[NB];
+    auto gload_a = [&](int kc) {
+#pragma unroll
+        for (int u = 0; u < NA; u++) {
+            const int e = tid + SM_NT * u;
+            const int r = e / SM_K, k = e % SM_K;     // K tile: 128 rows x 16 input slices (128-byte runs per row)
+            const int gr = row0 + r;
+            ra[u] = (gr < n && kc + k < n) ? K[(size_t)gr * n + kc + k] : 0.0;
+        }
+    };
+    auto gload_b = [&](double(&rbv)[NB], int kc) {
+        if (vec) {
+#pragma unroll
+            for (int u = 0; u < NB / 2; u++) {
+                const int e = tid + SM_NT * u;
+                const int k = e / (SM_T / 2), c = 2 * (e % (SM_T / 2));     // f tile: 16 input slices x 64 column pairs
+                const long gc = col0 + c;                                   // even, ncol even: the pair is inside or outside
+                double2 x = make_double2(0.0, 0.0);
+                if (kc + k < n && gc < ncol) x = *reinterpret_cast<const double2 *>(f + (size_t)(kc + k) * (size_t)ncol + (size_t)gc);
+                rbv[2 * u] = x.x, rbv[2 * u + 1] = x.y;
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < NB; u++) {
+                const int e = tid + SM_NT * u;
+                const int k = e / SM_T, c = e % SM_T;     // f tile: 16 input slices x 128 columns (coalesced along the columns)
+                const long gc = col0 + c;
+                rbv[u] = (kc + k < n && gc < ncol) ? f[(size_t)(kc + k) * (size_t)ncol + (size_t)gc] : 0.0;
+            }
+        }
+    };
+    auto lstore = [&](int buf, const double(&rbv)[NB]) {
+#pragma unroll
+        for (int u = 0; u < NA; u++) {
+            const int e = tid + SM_NT * u;
+            As[buf][(e / SM_K) * AS + e % SM_K] = ra[u];
+        }
+        if (vec) {
+#pragma unroll
+            for (int u = 0; u < NB / 2; u++) {
+                const int e = tid + SM_NT * u;
+                *reinterpret_cast<double2 *>(&Bs[buf][(e / (SM_T / 2)) * BS + 2 * (e % (SM_T / 2))]) =
+                    make_double2(rbv[2 * u], rbv[2 * u + 1]);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < NB; u++) {
+                const int e = tid + SM_NT * u;
+                Bs[buf][(e / SM_T) * BS + e % SM_T] = rbv[u];
+            }
+        }
+    };
+    const int kbeg = blo / SM_K * SM_K;
+    const int nchunk = bhi > blo ? (bhi - kbeg + SM_K - 1) / SM_K : 0;
+    if (nchunk > 0) {
+        gload_a(kbeg);
+        gload_b(rb0, kbeg);
+        lstore(0, rb0);
+    }
+    __syncthreads();
+    for (int c = 0; c < nchunk; c++) {
+        const int buf = c & 1, kc = kbeg + c * SM_K;
+        if (c + 1 < nchunk) {
+            gload_a(kc + SM_K);
+            gload_b(rb0, kc + SM_K);
+        }
+        const double *as = As[buf], *bs = Bs[buf];
+#pragma unroll
+        for (int ks = 0; ks < SM_K / 4; ks++) {
+            const int k4 = kc + 4 * ks;
+            double b[4];
+#pragma unroll
+            for (int v = 0; v < 4; v++) b[v] = bs[(4 * ks + kq) * BS + wc + 16 * v + ri];
+#pragma unroll
+            for (int u = 0; u < SM_UT; u++) {
+                if (k4 >= klo[u] && k4 < khi[u]) {        // wave-uniform
+                    const double a = as[(wr + 16 * u + ri) * AS + 4 * ks + kq];
+#pragma unroll
+                    for (int v = 0; v < 4; v++) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[v], acc[u][v], 0, 0, 0);
+                }
+            }
+        }
+        if (c + 1 < nchunk) lstore(buf ^ 1, rb0);   // the other buffer was last read before the previous barrier
+        __syncthreads();
+    }
+    // C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
+#pragma unroll
+    for (int u = 0; u < SM_UT; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            const long gc = col0 + wc + 16 * v + ri;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int gr = row0 + wr + 16 * u + kq + 4 * r;
+                if (gr < n && gc < ncol) out[(size_t)gr * (size_t)ncol + (size_t)gc] = acc[u][v][r];
+            }
+        }
+}
+
+template <int V> struct vec_of { typedef double type; };
+template <> struct vec_of<2> { typedef double2 type; };
+
+// every product and sum rounded on its own (the reference's numpy statements), no contraction into FMAs
+__device__ inline double d2_row(double c0, double c1, double c2, double c3, double w0, double w1, double w2, double w3) {
+#pragma clang fp contract(off)
+    return ((c0 * w0 + c1 * w1) + c2 * w2) + c3 * w3;
+}
+__device__ inline double lin_row(double h, double s, double g, double d2, double t, bool vel) {
+#pragma clang fp contract(off)
+    const double a = h + s * g;
+    return vel ? a + d2 * t : a;
+}
+__device__ inline double bias_value(double a, double b, double m, double x, bool second) {
+#pragma clang fp contract(off)
+    return second ? a * x + b * (x * x - m) : a * x;
+}
+
+// lssutil.diff2 along axis 0 (+ optional epilogue).  Output row i uses input rows st .. st + 3, st = clamp(i - 2, 0, n - 4)
+// (rows 0, 1: 0 .. 3; interior rows 2 .. n - 2: i - 2 .. i + 1; row n - 1: n - 4 .. n - 1), with coef[i] = (c0, c1, c2, c3):
+//   d2 = ((c0 w0 + c1 w1) + c2 w2) + c3 w3, every product and sum rounded on its own.
+// The interior rows of the reference are ((alpha f[i-2] + beta f[i-1]) - (alpha + beta + gamma) f[i]) + gamma f[i+1]: the
+// host stores c2 = -(alpha + beta + gamma), and x + (-s) y == x - s y exactly.  A thread walks the rows of its column(s)
+// with the four rows of the window and the next one in registers.
+// f == NULL (needs g, h): no stencil term, out = h + s g.  g, h != NULL: out = (h + s[i] g) + d2 t[i].
+template <int V>
+__global__ void __launch_bounds__(256)
+slice_diff2_kernel(const double *__restrict__ f, const double *__restrict__ coef, const double *g, const double *h,
+                   const double *__restrict__ s, const double *__restrict__ t, int n, long ncol, double *out) {
+    typedef typename vec_of<V>::type vec;
+    const long nv = ncol / V;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < nv; p += (long)gridDim.x * blockDim.x) {
+        const vec *src = reinterpret_cast<const vec *>(f) + p;
+        const vec *gs = reinterpret_cast<const vec *>(g) + p, *hs = reinterpret_cast<const vec *>(h) + p;
+        vec *dst = reinterpret_cast<vec *>(out) + p;
+        vec w0 = {}, w1 = {}, w2 = {}, w3 = {}, nxt = {};
+        int cur = 0;
+        if (f) {
+            w0 = src[0], w1 = src[(size_t)nv], w2 = src[(size_t)2 * nv], w3 = src[(size_t)3 * nv];
+            if (n > 4) nxt = src[(size_t)4 * nv];
+        }
+        for (int i = 0; i < n; i++) {
+            vec r = {};
+            if (f) {
+                const int st = min(max(i - 2, 0), n - 4);
+                if (st > cur) {
+                    w0 = w1, w1 = w2, w2 = w3, w3 = nxt;
+                    cur++;
+                    if (cur + 4 < n) nxt = src[(size_t)(cur + 4) * nv];      // in flight while row i is formed
+                }
+                const double c0 = coef[4 * i], c1 = coef[4 * i + 1], c2 = coef[4 * i + 2], c3 = coef[4 * i + 3];
+                if constexpr (V == 2)
+                    r = make_double2(d2_row(c0, c1, c2, c3, w0.x, w1.x, w2.x, w3.x), d2_row(c0, c1, c2, c3, w0.y, w1.y, w2.y, w3.y));
+                else
+                    r = d2_row(c0, c1, c2, c3, w0, w1, w2, w3);
+            }
+            if (g) {
+                const vec gv = gs[(size_t)i * nv], hv = hs[(size_t)i * nv];
+                const double si = s[i], ti = f ? t[i] : 0.0;
+                if constexpr (V == 2)
+                    r = make_double2(lin_row(hv.x, si, gv.x, r.x, ti, f != nullptr), lin_row(hv.y, si, gv.y, r.y, ti, f != nullptr));
+                else
+                    r = lin_row(hv, si, gv, r, ti, f != nullptr);
+            }
+            dst[(size_t)i * nv] = r;
+        }
+    }
+}
+
+// partial sums of row i over the columns [b per, (b + 1) per): work[(i nb + b) 2 + (0, 1)] = sum (f - c), sum (f - c)^2.
+// Fixed order: a thread adds its strided elements in sequence, lanes fold by shuffles, waves through LDS.
+template <int V>
+__global__ void __launch_bounds__(256)
+slice_moments_partial_kernel(const double *__restrict__ f, long ld, const double *__restrict__ c, int n, long ncol, int nb,
+                             long per, double *__restrict__ work) {
+    typedef typename vec_of<V>::type vec;
+    const int i = (int)(blockIdx.x / (unsigned)nb), b = (int)(blockIdx.x % (unsigned)nb);
+    const long lo = (long)b * per, hi = min(ncol, lo + per);
+    const double ci = c ? c[i] : 0.0;
+    const double *row = f + (size_t)i * (size_t)ld;
+    double s1 = 0.0, s2 = 0.0;
+    {
+#pragma clang fp contract(off)
+        for (long p = lo + (long)threadIdx.x * V; p < hi; p += 256 * V) {
+            if constexpr (V == 2) {
+                const vec x = *reinterpret_cast<const vec *>(row + p);
+                const double dx = x.x - ci, dy = x.y - ci;
+                s1 = s1 + (dx + dy);
+                s2 = s2 + (dx * dx + dy * dy);
+            } else {
+                const double dx = row[p] - ci;
+                s1 = s1 + dx;
+                s2 = s2 + dx * dx;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_down(s1, o, 64);
+        s2 += __shfl_down(s2, o, 64);
+    }
+    __shared__ double red[8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[2 * wave] = s1, red[2 * wave + 1] = s2;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        work[(size_t)blockIdx.x * 2] = ((red[0] + red[2]) + red[4]) + red[6];
+        work[(size_t)blockIdx.x * 2 + 1] = ((red[1] + red[3]) + red[5]) + red[7];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+slice_moments_final_kernel(const double *__restrict__ work, int n, int nb, double *__restrict__ sum1,
+                           double *__restrict__ sum2) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s1 = 0.0, s2 = 0.0;
+    for (int b = 0; b < nb; b++) {
+        s1 += work[((size_t)i * nb + b) * 2];
+        s2 += work[((size_t)i * nb + b) * 2 + 1];
+    }
+    sum1[i] = s1;
+    sum2[i] = s2;
+}
+
+// out = c1[i] f + c2[i] (f f - m2[i]) (c2 == NULL: exactly c1[i] f); the reference's statement order
+// (lss.py:582-592), products and sums rounded one by one
+template <int V>
+__global__ void __launch_bounds__(256)
+bias_field_kernel(const double *f, const double *__restrict__ c1, const double *__restrict__ c2,
+                  const double *__restrict__ m2, int n, long ncol, double *out) {
+    typedef typename vec_of<V>::type vec;
+    const long nv = ncol / V;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < nv; p += (long)gridDim.x * blockDim.x) {
+        const vec *src = reinterpret_cast<const vec *>(f) + p;
+        vec *dst = reinterpret_cast<vec *>(out) + p;
+#pragma unroll 4
+        for (int i = 0; i < n; i++) {
+            const vec x = src[(size_t)i * nv];
+            const double a = c1[i];
+            const double b = c2 ? c2[i] : 0.0, m = c2 ? m2[i] : 0.0;
+            vec r;
+            if constexpr (V == 2)
+                r = make_double2(bias_value(a, b, m, x.x, c2 != nullptr), bias_value(a, b, m, x.y, c2 != nullptr));
+            else
+                r = bias_value(a, b, m, x, c2 != nullptr);
+            dst[(size_t)i * nv] = r;
+        }
+    }
+}
+
+__device__ inline double ln_value(double x, double hv, bool tr, double pre, double rs) {
+#pragma clang fp contract(off)
+    double v = x;
+    if (tr) {
+        const double a = x - hv;
+        // glibc_exp_fma holds for |a| < 512; beyond it (and for NaN) the device's own exp gives the limits
+        v = (fabs(a) < 512.0 ? glibc_exp_fma(a) : exp(a)) - 1.0;
+    }
+    return (v * pre) * rs;
+}
+
+// out[i ld_out + p] = ((exp(f[i ncol + p] - hv[i]) - 1) pre) rs[i]; hv == NULL: no transform (copy), rs == NULL: 1
+template <int V>
+__global__ void __launch_bounds__(256)
+lognormal_kernel(const double *f, const double *__restrict__ hv, const double *__restrict__ rs, double pre, int n,
+                 long ncol, long ld_out, double *out) {
+    typedef typename vec_of<V>::type vec;
+    const long nv = ncol / V, ldv = ld_out / V;
+    for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < nv; p += (long)gridDim.x * blockDim.x) {
+        const vec *src = reinterpret_cast<const vec *>(f) + p;
+        vec *dst = reinterpret_cast<vec *>(out) + p;
+#pragma unroll 2
+        for (int i = 0; i < n; i++) {
+            const vec x = src[(size_t)i * nv];
+            const double hvi = hv ? hv[i] : 0.0, rsi = rs ? rs[i] : 1.0;
+            vec r;
+            if constexpr (V == 2)
+                r = make_double2(ln_value(x.x, hvi, hv != nullptr, pre, rsi), ln_value(x.y, hvi, hv != nullptr, pre, rsi));
+            else
+                r = ln_value(x, hvi, hv != nullptr, pre, rsi);
+            dst[(size_t)i * ldv] = r;
+        }
+    }
+}
+
+inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+inline long stream_blocks(corahip_ctx *ctx, long nv) {
+    long blocks = (nv + 255) / 256;
+    const long cap = (long)ctx->num_cu * 32;
+    return blocks > cap ? cap : blocks;
+}
+
+inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// nb (partials per row) and per (columns per partial, even) of slice_moments
+inline void moments_split(long ncol, int *nb, long *per) {
+    long b = (ncol + 8191) / 8192;
+    if (b > 4096) b = 4096;
+    long pr = (ncol + b - 1) / b;
+    pr = (pr + 1) & ~1L;
+    *nb = (int)((ncol + pr - 1) / pr);
+    *per = pr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int corahip_slice_mix(corahip_ctx *ctx, const double *K, const double *f, const int32_t *ranges, int n, long ncol,
+                      double *out) {
+    ARG_CHECK(ctx && K && f && out && n >= 1 && n <= 4096 && ncol >= 1);
+    ARG_CHECK(((uintptr_t)K & 7) == 0 && ((uintptr_t)f & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    ARG_CHECK(ranges == nullptr || ((uintptr_t)ranges & 3) == 0);
+    const size_t nbytes = (size_t)n * (size_t)ncol * 8;
+    ARG_CHECK(!overlaps(out, nbytes, f, nbytes) && !overlaps(out, nbytes, K, (size_t)n * n * 8));
+    const long nrb = (n + SM_T - 1) / SM_T, ncb = (ncol + SM_T - 1) / SM_T;
+    ARG_CHECK(nrb * ncb <= 0x7fffffffL);
+    StageTimer t(ctx, "slice_mix");
+    const int vec = (ncol & 1) == 0 && al16(f);
+    hipLaunchKernelGGL(slice_mix_kernel, dim3((unsigned)(nrb * ncb)), dim3(SM_NT), 0, ctx->stream, K, f, ranges, n, ncol,
+                       (int)nrb, vec, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_slice_diff2(corahip_ctx *ctx, const double *f, const double *coef, const double *g, const double *h,
+                        const double *s, const double *t, int n, long ncol, double *out) {
+    ARG_CHECK(ctx && out && n >= 1 && ncol >= 1);
+    ARG_CHECK((g == nullptr) == (h == nullptr));
+    ARG_CHECK(f != nullptr || g != nullptr);
+    ARG_CHECK(f == nullptr || (coef != nullptr && n >= 4));
+    ARG_CHECK(g == nullptr || (s != nullptr && (f == nullptr || t != nullptr)));
+    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)g & 7) == 0 && ((uintptr_t)h & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    const size_t nbytes = (size_t)n * (size_t)ncol * 8;
+    ARG_CHECK(f == nullptr || !overlaps(out, nbytes, f, nbytes));
+    StageTimer tm(ctx, "slice_diff2");
+    const bool v2 = (ncol & 1) == 0 && al16(f) && al16(g) && al16(h) && al16(out);
+    const long nv = v2 ? ncol / 2 : ncol;
+    const long blocks = stream_blocks(ctx, nv);
+    if (v2)
+        hipLaunchKernelGGL(slice_diff2_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, coef, g, h, s, t, n,
+                           ncol, out);
+    else
+        hipLaunchKernelGGL(slice_diff2_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, coef, g, h, s, t, n,
+                           ncol, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_slice_moments_workspace_bytes(int n, long ncol, size_t *bytes) {
+    ARG_CHECK(bytes && n >= 1 && ncol >= 1);
+    int nb;
+    long per;
+    moments_split(ncol, &nb, &per);
+    *bytes = (size_t)n * nb * 2 * sizeof(double);
+    return 0;
+}
+
+int corahip_slice_moments(corahip_ctx *ctx, const double *f, long ld, const double *c, int n, long ncol, void *work,
+                          size_t work_bytes, double *sum1, double *sum2) {
+    ARG_CHECK(ctx && f && work && sum1 && sum2 && n >= 1 && ncol >= 1 && ld >= ncol);
+    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)work & 7) == 0);
+    int nb;
+    long per;
+    moments_split(ncol, &nb, &per);
+    ARG_CHECK(work_bytes >= (size_t)n * nb * 2 * sizeof(double));
+    ARG_CHECK((long)n * nb <= 0x7fffffffL);
+    StageTimer t(ctx, "slice_moments");
+    const bool v2 = (ncol & 1) == 0 && (ld & 1) == 0 && al16(f);
+    if (v2)
+        hipLaunchKernelGGL(slice_moments_partial_kernel<2>, dim3((unsigned)((long)n * nb)), dim3(256), 0, ctx->stream, f, ld,
+                           c, n, ncol, nb, per, (double *)work);
+    else
+        hipLaunchKernelGGL(slice_moments_partial_kernel<1>, dim3((unsigned)((long)n * nb)), dim3(256), 0, ctx->stream, f, ld,
+                           c, n, ncol, nb, per, (double *)work);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(slice_moments_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const double *)work, n, nb, sum1, sum2);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_bias_field(corahip_ctx *ctx, const double *f, const double *c1, const double *c2, const double *m2, int n,
+                       long ncol, double *out) {
+    ARG_CHECK(ctx && f && c1 && out && n >= 1 && ncol >= 1);
+    ARG_CHECK((c2 == nullptr) == (m2 == nullptr));
+    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    const size_t nbytes = (size_t)n * (size_t)ncol * 8;
+    ARG_CHECK(out == f || !overlaps(out, nbytes, f, nbytes));
+    StageTimer t(ctx, "bias_field");
+    const bool v2 = (ncol & 1) == 0 && al16(f) && al16(out);
+    const long nv = v2 ? ncol / 2 : ncol;
+    const long blocks = stream_blocks(ctx, nv);
+    if (v2)
+        hipLaunchKernelGGL(bias_field_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, c1, c2, m2, n, ncol, out);
+    else
+        hipLaunchKernelGGL(bias_field_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, c1, c2, m2, n, ncol, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_lognormal(corahip_ctx *ctx, const double *f, const double *hv, const double *rs, double pre, int n, long ncol,
+                      long ld_out, double *out) {
+    ARG_CHECK(ctx && f && out && n >= 1 && ncol >= 1 && ld_out >= ncol);
+    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    // in place (same pointer, same stride) or disjoint
+    ARG_CHECK((out == f && ld_out == ncol) ||
+              !overlaps(out, ((size_t)(n - 1) * (size_t)ld_out + (size_t)ncol) * 8, f, (size_t)n * (size_t)ncol * 8));
+    StageTimer t(ctx, "lognormal");
+    const bool v2 = (ncol & 1) == 0 && (ld_out & 1) == 0 && al16(f) && al16(out);
+    const long nv = v2 ? ncol / 2 : ncol;
+    const long blocks = stream_blocks(ctx, nv);
+    if (v2)
+        hipLaunchKernelGGL(lognormal_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, hv, rs, pre, n, ncol,
+                           ld_out, out);
+    else
+        hipLaunchKernelGGL(lognormal_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, hv, rs, pre, n, ncol,
+                           ld_out, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

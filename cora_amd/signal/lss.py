@@ -7,6 +7,12 @@ iterated analysis, derivative synthesis and radial gradient, csrc/sht_der1.hip),
 numerical content of ``ZeldovichDynamics.process(sph=True)`` (lss.py:777-856) from ``phi, delta`` to the final
 density without leaving the device.
 
+The steps around it (csrc/lsschain.hip): ``biased_field`` (GenerateBiasedFieldBase.process, lss.py:556-603),
+``linear_dynamics`` (LinearDynamics.process, :862-918), ``fingers_of_god`` (FingersOfGod.process, :1162-1220),
+``biased_lss_to_map`` (BiasedLSSToMap.process, :944-993) and their composition ``tracer_map_device``: ``phi, delta``
+in, map out, on the device.  The bias, growth and temperature models of the reference are not part of this package:
+``b1``, ``b2``, ``sigmaP``, ``D``, ``f``, ``T_b`` are per-slice arrays (or scalars) the caller supplies.
+
 The reference's scatter (pmesh_util.c:37, called from pmesh.pyx:_bin_delta) indexes ``out`` with a row stride of 9
 (the number of pixel weights) instead of the map's npix, so mass meant for radial bin ``ri`` lands ri (npix - 9)
 elements early.  This port implements the intended ``out[ri, pix]`` (tests/test_lss_host.py).
@@ -179,3 +185,162 @@ def zeldovich_density(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lm
     res = zeldovich_density_device(ctx.to_device(phi), ctx.to_device(delta), ctx.to_device(delta_bias), chi, D, f,
                                    sigma_chi=sigma_chi, lmax=lmax, niter=niter)
     return ctx.to_host(res)
+
+
+# ------------------------------------------------------------------------------------
+# bias, linear dynamics, Fingers of God, map (cora/signal/lss.py:556-603, 862-918, 1162-1220, 944-993)
+# ------------------------------------------------------------------------------------
+_rows = lssutil.row_values
+
+
+def _check_field(field, name, nmin=1):
+    if len(field.shape) != 2:
+        raise ValueError(f"Array {name} must be [nchi, npix] (got shape {tuple(field.shape)})")
+    n = int(field.shape[0])
+    if n < nmin:
+        raise ValueError(f"{name} needs at least {nmin} slices (got {n})")
+    return n, int(field.shape[1])
+
+
+def biased_field_device(delta, D, b1=None, b2=None, lognormal=False, lightcone=True, out=None):
+    """``GenerateBiasedFieldBase.process`` (cora/signal/lss.py:556-603) on a device tensor ``delta`` [nchi, npix]:
+    ``(D b1)[:, None] delta + (D^2 b2)[:, None] (delta^2 - <delta^2>_slice)``, then the lognormal transform along
+    axis 1 if ``lightcone`` else over the whole field.  ``D``, ``b1``, ``b2``: [nchi] arrays or scalars; a missing
+    ``b1`` or ``b2`` skips that term.  Returns a new device tensor (``out`` if given; it may be ``delta``)."""
+    n, npix = _check_field(delta, "delta")
+    D = _rows(D, n, "D")
+    ctx = _lib.get_context()
+    c1 = np.zeros(n) if b1 is None else D * _rows(b1, n, "b1")
+    if b2 is not None:
+        c2 = D**2 * _rows(b2, n, "b2")
+        _, s2 = ctx.slice_moments(delta)
+        res = ctx.bias_field(delta, c1, c2, s2 / npix, out=out)
+    else:
+        res = ctx.bias_field(delta, c1, out=out)
+    if lognormal:
+        lssutil.lognormal_transform_device(res, out=res, axis=1 if lightcone else None)
+    return res
+
+
+def biased_field(delta, D, b1=None, b2=None, lognormal=False, lightcone=True):
+    """:func:`biased_field_device` for numpy arrays."""
+    delta = np.asarray(delta)
+    n, _ = _check_field(delta, "delta")
+    _rows(D, n, "D")
+    ctx = _lib.get_context()
+    return ctx.to_host(biased_field_device(ctx.to_device(delta), D, b1, b2, lognormal=lognormal, lightcone=lightcone))
+
+
+def linear_dynamics_device(phi, delta, delta_bias, chi, D, f=None, out=None):
+    """``LinearDynamics.process`` (cora/signal/lss.py:862-918) on device tensors [nchi, npix], nchi >= 4:
+    ``(delta_bias + D[:, None] delta) + diff2(phi, chi, axis=0) (-(D f))[:, None]`` in one launch; ``f=None`` is the
+    reference's ``redshift_space=False``: no velocity term.  ``out`` must not overlap ``phi``."""
+    n, npix = _check_field(delta, "delta")
+    _assert_shape(phi, (n, npix), "phi")
+    _assert_shape(delta_bias, (n, npix), "delta_bias")
+    chi_h = np.asarray(_host(chi), dtype=np.float64)
+    _assert_shape(chi_h, (n,), "chi")
+    D = _rows(D, n, "D")
+    if n < 4:
+        raise ValueError("linear_dynamics needs at least 4 slices (got %d)" % n)
+    ctx = _lib.get_context()
+    if f is None:
+        return ctx.slice_diff2(None, None, g=delta, h=delta_bias, s=D, out=out)
+    return ctx.slice_diff2(phi, chi_h, g=delta, h=delta_bias, s=D, t=-(D * _rows(f, n, "f")), out=out)
+
+
+def linear_dynamics(phi, delta, delta_bias, chi, D, f=None):
+    """:func:`linear_dynamics_device` for numpy arrays."""
+    phi, delta, delta_bias = np.asarray(phi), np.asarray(delta), np.asarray(delta_bias)
+    n, npix = _check_field(delta, "delta")
+    _assert_shape(phi, (n, npix), "phi")
+    _assert_shape(delta_bias, (n, npix), "delta_bias")
+    if n < 4:
+        raise ValueError("linear_dynamics needs at least 4 slices (got %d)" % n)
+    ctx = _lib.get_context()
+    return ctx.to_host(linear_dynamics_device(ctx.to_device(phi), ctx.to_device(delta), ctx.to_device(delta_bias), chi, D, f))
+
+
+def _fog_kernel(n, chi, sigmaP, D, alpha_FoG):
+    chi_h = np.asarray(_host(chi), dtype=np.float64)
+    _assert_shape(chi_h, (n,), "chi")
+    sig = alpha_FoG * _rows(sigmaP, n, "sigmaP")
+    Dh = np.full(n, 1.0) if D is None else _rows(D, n, "D")
+    return lssutil.exponential_FoG_kernel(chi_h, sig, Dh)
+
+
+def fingers_of_god_device(field, chi, sigmaP, D=None, alpha_FoG=1.0, band_cut=None):
+    """``FingersOfGod.process`` (cora/signal/lss.py:1162-1220) on a device tensor ``field`` [n, npix] or
+    [n, npol, npix]: ``K @ field.reshape(n, -1)`` with ``K = exponential_FoG_kernel(chi, alpha_FoG sigmaP, D or 1)``.
+    Returns ``field`` itself when ``alpha_FoG == 0``.  ``band_cut``: see :meth:`cora_amd._lib.Context.slice_mix`
+    (default: exact)."""
+    if alpha_FoG == 0.0:
+        return field
+    if len(field.shape) not in (2, 3):
+        raise ValueError(f"Array field must be [n, npix] or [n, npol, npix] (got shape {tuple(field.shape)})")
+    n = int(field.shape[0])
+    K = _fog_kernel(n, chi, sigmaP, D, alpha_FoG)
+    ctx = _lib.get_context()
+    return ctx.slice_mix(K, field.reshape(n, -1), band_cut=band_cut).reshape(field.shape)
+
+
+def fingers_of_god(field, chi, sigmaP, D=None, alpha_FoG=1.0, band_cut=None):
+    """:func:`fingers_of_god_device` for numpy arrays."""
+    if alpha_FoG == 0.0:
+        return field
+    field = np.asarray(field)
+    if field.ndim not in (2, 3):
+        raise ValueError(f"Array field must be [n, npix] or [n, npol, npix] (got shape {field.shape})")
+    _fog_kernel(field.shape[0], chi, sigmaP, D, alpha_FoG)
+    ctx = _lib.get_context()
+    return ctx.to_host(fingers_of_god_device(ctx.to_device(field), chi, sigmaP, D, alpha_FoG, band_cut))
+
+
+def biased_lss_to_map_device(delta, lognormal=False, map_prefactor=1.0, T_b=None, polarisation=True):
+    """``BiasedLSSToMap.process`` (cora/signal/lss.py:944-993) on a device tensor ``delta`` [n, npix]: a map
+    [n, 4 or 1, npix] whose plane 0 is the lognormal transform of ``delta`` along axis 1 (or a copy), times
+    ``map_prefactor``, times ``T_b[:, None]`` (the mean 21 cm temperature per slice, supplied by the caller);
+    the other planes are zero."""
+    import torch
+
+    n, npix = _check_field(delta, "delta")
+    ctx = _lib.get_context()
+    m = torch.zeros((n, 4 if polarisation else 1, npix), dtype=torch.float64, device=delta.device)
+    hv = None
+    if lognormal:
+        _, var = lssutil.slice_moments_device(delta)
+        hv = var * 0.5
+    ctx.lognormal(delta, hv, out=m[:, 0], prefactor=map_prefactor, row_scale=None if T_b is None else _rows(T_b, n, "T_b"))
+    return m
+
+
+def biased_lss_to_map(delta, lognormal=False, map_prefactor=1.0, T_b=None, polarisation=True):
+    """:func:`biased_lss_to_map_device` for numpy arrays."""
+    delta = np.asarray(delta)
+    _check_field(delta, "delta")
+    ctx = _lib.get_context()
+    return ctx.to_host(biased_lss_to_map_device(ctx.to_device(delta), lognormal, map_prefactor, T_b, polarisation))
+
+
+def tracer_map_device(phi, delta, chi, D, f, b1, b2=None, sigmaP=None, dynamics="zeldovich", lognormal=False,
+                      lightcone=True, redshift_space=True, fog_D=None, alpha_FoG=1.0, band_cut=None,
+                      map_lognormal=False, map_prefactor=1.0, T_b=None, polarisation=True, sigma_chi=None, lmax=None,
+                      niter=3):
+    """``phi, delta`` [nchi, npix] (device, from ``mkfullsky_device``) -> tracer map [nchi, 4 or 1, npix] on the device:
+    :func:`biased_field_device` -> :func:`zeldovich_density_device` (``dynamics="zeldovich"``) or
+    :func:`linear_dynamics_device` (``"linear"``) -> :func:`fingers_of_god_device` (skipped when ``sigmaP`` is None)
+    -> :func:`biased_lss_to_map_device`.  A composition only: every number comes from those four calls, with the
+    arguments passed through (``redshift_space=False`` passes ``f=None`` to the dynamics; ``fog_D`` is the growth factor
+    the FoG kernel divides out and re-applies, None = 1)."""
+    if dynamics not in ("zeldovich", "linear"):
+        raise ValueError("dynamics must be 'zeldovich' or 'linear' (got %r)" % (dynamics,))
+    fd = f if redshift_space else None
+    bias = biased_field_device(delta, D, b1, b2, lognormal=lognormal, lightcone=lightcone)
+    if dynamics == "zeldovich":
+        final = zeldovich_density_device(phi, delta, bias, chi, D, fd, sigma_chi=sigma_chi, lmax=lmax, niter=niter)
+    else:
+        final = linear_dynamics_device(phi, delta, bias, chi, D, fd)
+    del bias
+    if sigmaP is not None:
+        final = fingers_of_god_device(final, chi, sigmaP, fog_D, alpha_FoG, band_cut)
+    return biased_lss_to_map_device(final, map_lognormal, map_prefactor, T_b, polarisation)

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 6      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient */
+#define CORAHIP_ABI_MINOR 7      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -521,6 +521,41 @@ int corahip_der1_combine(corahip_ctx *ctx, corahip_sht_plan *plan, const double 
                          const double *s_theta, const double *s_phi, int phi_extra, double *out_theta, double *out_phi);
 int corahip_radial_gradient(corahip_ctx *ctx, const double *f, const double *x_coef, const double *s_r, int n, long npix,
                             double *out);
+
+/* ---- large-scale structure: bias, linear dynamics, Fingers of God, map (csrc/lsschain.hip) ------------------
+ * The steps of cora/signal/lss.py around the Zel'dovich step (GenerateBiasedFieldBase.process :556-603,
+ * LinearDynamics.process :862-918, FingersOfGod.process :1162-1220, BiasedLSSToMap.process :944-993) and the lssutil
+ * functions they call.  All fields are row-major [n, ncol] float64 on the device, row = slice; rows need only 8-byte
+ * alignment (ncol may be odd).  Every function returns CORAHIP_EINVAL on arguments it cannot take.
+ * slice_mix:  out = K f for K [n, n], 1 <= n <= 4096, ncol >= 1, with FP64 MFMA; out must overlap neither f nor K.
+ *            ranges: NULL, or device int32 [ceil(n / 16)][2]: for output rows 16 b .. 16 b + 15 the input slices
+ *            [klo, khi) outside which every K entry of those rows is exactly zero (the kernel widens them to
+ *            multiples of 4 and clips them to the matrix); products outside are not formed.  For finite f the result is
+ *            the same, bit for bit, as with ranges NULL; a non-finite f in a skipped slice does not propagate.
+ *            No atomics: two calls on the same inputs give identical bits.
+ * slice_diff2: lssutil.diff2 along axis 0, n >= 4: d2[i] = ((c0 w0 + c1 w1) + c2 w2) + c3 w3 with
+ *            (c0 .. c3) = coef[i] (device [n][4]) and w0 .. w3 = rows st .. st + 3 of f, st = min(max(i - 2, 0), n - 4);
+ *            every product and sum is rounded on its own.  g, h (both or neither, [n, ncol]) with device [n] factors
+ *            s, t: out = (h + s[i] g) + d2 t[i]; f NULL (then g, h, s required, any n >= 1): out = h + s[i] g.
+ *            out must not overlap f; it may be g or h.
+ * slice_moments: sum1[i] = sum_p (f[i ld + p] - c[i]), sum2[i] = sum_p (f[i ld + p] - c[i])^2 over p < ncol; ld >= ncol the
+ *            row stride, c device [n] or NULL (= 0).  Block partials in work (slice_moments_workspace_bytes), then
+ *            one ordered pass: no atomics, identical bits from call to call.
+ * bias_field: out = c1[i] f + c2[i] (f f - m2[i]); c2, m2 both NULL: exactly c1[i] f.  out == f allowed.
+ * lognormal: out[i ld_out + p] = ((exp(f[i ncol + p] - hv[i]) - 1) pre) rs[i], exp as glibc's (then - 1, not expm1);
+ *            hv NULL: no transform (out = (f pre) rs), rs NULL: 1.  ld_out >= ncol (plane 0 of a [n, 4, ncol] map:
+ *            ld_out = 4 ncol); in place (out == f, ld_out == ncol) allowed, any other overlap is not.            */
+int corahip_slice_mix(corahip_ctx *ctx, const double *K, const double *f, const int32_t *ranges, int n, long ncol,
+                      double *out);
+int corahip_slice_diff2(corahip_ctx *ctx, const double *f, const double *coef, const double *g, const double *h,
+                        const double *s, const double *t, int n, long ncol, double *out);
+int corahip_slice_moments_workspace_bytes(int n, long ncol, size_t *bytes);
+int corahip_slice_moments(corahip_ctx *ctx, const double *f, long ld, const double *c, int n, long ncol, void *work,
+                          size_t work_bytes, double *sum1, double *sum2);
+int corahip_bias_field(corahip_ctx *ctx, const double *f, const double *c1, const double *c2, const double *m2, int n,
+                       long ncol, double *out);
+int corahip_lognormal(corahip_ctx *ctx, const double *f, const double *hv, const double *rs, double pre, int n, long ncol,
+                      long ld_out, double *out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
