@@ -7,6 +7,7 @@ entry points raise (loudly) instead of computing something else.
 """
 import ctypes
 import os
+import weakref
 
 import numpy as np
 
@@ -129,6 +130,8 @@ class CoraHipError(RuntimeError):
     status = 0
 
 
+CORAHIP_ESTATE = -3          # include/corahip.h: an object used in the wrong state (e.g. a second draw session on a context)
+
 _lib = None
 
 
@@ -220,13 +223,86 @@ def _rng_struct(rng):
         return r, None
     if rng[0] != "legacy" or rng[1]["bit_generator"] != "MT19937":
         raise ValueError("numpy stream on the device: ('pcg64', state, inc) or ('legacy', MT19937 state dict)")
-    ms = _MtState()
-    key = np.ascontiguousarray(rng[1]["state"]["key"], dtype=np.uint32)
-    ctypes.memmove(ms.key, key.ctypes.data, 624 * 4)
-    ms.pos, ms.has_gauss, ms.gauss = int(rng[1]["state"]["pos"]), int(rng[1]["has_gauss"]), float(rng[1]["gauss"])
+    ms = _mt_struct(rng[1])
     r.kind = 3
     r.legacy = ctypes.pointer(ms)
     return r, ms
+
+
+def _mt_struct(state):
+    """``get_state(legacy=False)`` of a legacy generator on MT19937 -> corahip_mt_state."""
+    if state["bit_generator"] != "MT19937":
+        raise ValueError("legacy stream on the device: MT19937 only")
+    ms = _MtState()
+    key = np.ascontiguousarray(state["state"]["key"], dtype=np.uint32)
+    ctypes.memmove(ms.key, key.ctypes.data, 624 * 4)
+    ms.pos, ms.has_gauss, ms.gauss = int(state["state"]["pos"]), int(state["has_gauss"]), float(state["gauss"])
+    return ms
+
+
+def _mt_dict(ms):
+    """corahip_mt_state -> the dict ``set_state`` takes."""
+    return {"bit_generator": "MT19937", "state": {"key": np.frombuffer(ms.key, dtype=np.uint32).copy(), "pos": int(ms.pos)},
+            "has_gauss": int(ms.has_gauss), "gauss": float(ms.gauss)}
+
+
+class DrawSession:
+    """One draw with numpy's own stream on a context: ``corahip_draw_alm_numpy_prepare`` (here) -> :meth:`run` (``_run``:
+    K3 against the factors) -> :meth:`finish` (``_end``: the one read-back).  The session holds what the library reads
+    until then (the ``corahip_rng`` struct, the MT state it points to, the tensors of the run) and is the one place that
+    ends the C session: ``_end`` is called exactly once - by ``finish``, by :meth:`abort`, by ``run`` when it raises, or
+    by the finalizer of a session that was dropped - and a session that did not run whole leaves the generator untouched."""
+
+    def __init__(self, ctx, rng, lmax, F, ring_bytes=0):
+        self.rng_struct, self.mt_state = _rng_struct(rng)
+        self.shape, self.state, self.keep = (int(lmax), int(F)), "prepared", []
+        pend = c_void_p()
+        _check(ctx.lib.corahip_draw_alm_numpy_prepare(ctx.h, ctypes.byref(self.rng_struct), int(lmax), int(F), int(ring_bytes),
+                                                      ctypes.byref(pend)))
+        self.ctx, self.pending = ctx, pend
+        # (the callback keeps the struct and the MT state alive, not the session; nothing is ended at interpreter exit)
+        self._end = weakref.finalize(self, lambda r, ms: ctx.lib.corahip_draw_alm_numpy_end(ctx.h, pend, ctypes.byref(r)),
+                                     self.rng_struct, self.mt_state)
+        self._end.atexit = False
+
+    def run(self, T, info, lmax, F, nu0=0, nnu=None, out=None, rows=False, chunks=None):
+        """K3 of every range against ``T`` (arguments as :meth:`Context.draw_alm_numpy`); returns the a_lm.  Whatever is
+        raised here - a shape that does not fit, the allocation of the a_lm, a status of the library - ends the session."""
+        ctx = self.ctx
+        try:
+            assert self.state == "prepared" and self.shape == (int(lmax), int(F)), "the prepared session is for another shape"
+            if chunks is not None:
+                rows, nu0, nnu = True, chunks[0][0], sum(c[1] for c in chunks)
+            nnu = F if nnu is None else nnu
+            assert tuple(T.shape) == ((lmax + 1, nnu, F) if rows else (lmax + 1, F, F)), T.shape
+            alm = ctx._alm_out(lmax, nnu, out)
+            cs = _chanset(chunks if chunks is not None and len(chunks) > 1 else [(nu0, nnu)])
+            _check(ctx.lib.corahip_draw_alm_numpy_run(ctx.h, self.pending, ctx._f64(T), 1 if rows else 0, ctx._p0(info),
+                                                      ctypes.byref(cs), ctx._f64(alm)))
+        except BaseException:
+            self.state = "ended"
+            self._end()
+            raise
+        self.state, self.keep = "ran", [T, info, alm]           # (alive until the queue has been waited for)
+        return alm
+
+    def finish(self):
+        """``corahip_draw_alm_numpy_end`` behind a run: waits for the queue; returns the generator's state after - the
+        PCG64 state as a python int, or the legacy state dict ``set_state`` takes."""
+        assert self.state == "ran", self.state
+        self.state = "ended"
+        rc = self._end()
+        self.keep = []
+        _check(rc)
+        if self.mt_state is not None:
+            return _mt_dict(self.mt_state)
+        return (int(self.rng_struct.state[0]) << 64) | int(self.rng_struct.state[1])
+
+    def abort(self):
+        """Give up a session that has not finished (generator untouched); harmless on one that has ended."""
+        if self._end.alive:
+            self.state, self.keep = "ended", []
+            _check(self._end())
 
 
 class Context:
@@ -295,6 +371,13 @@ class Context:
         torch = _torch()
         assert t.dtype == torch.float64 and t.device == self.device
         return self._p(t)
+
+    def _p0(self, t):
+        return self._p(t) if t is not None else None
+
+    def _alm_out(self, lmax, nnu, out=None):
+        """``out``, or a fresh a_lm buffer in the device layout [nalm, ceil(nnu / 4), 2, 4]."""
+        return out if out is not None else self.empty(((lmax + 1) * (lmax + 2) // 2, (nnu + 3) // 4, 2, 4))
 
     # -- host delivery ------------------------------------------------------------------
     _PINNED_MIN_BYTES = 1 << 24     # below this a pageable copy is as fast as pinning a buffer
@@ -476,63 +559,33 @@ class Context:
         """The next ``n`` values of numpy's LEGACY stream (``np.random.standard_normal`` / ``RandomState``: MT19937 + polar
         method) from ``state`` = ``get_state(legacy=False)``, generated on the device; returns (g, state after) with the
         state as a dict ``set_state`` takes."""
-        import numpy as np
-
-        class MtState(ctypes.Structure):
-            _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_int32), ("has_gauss", ctypes.c_int32),
-                        ("gauss", c_double)]
-
-        if state["bit_generator"] != "MT19937":
-            raise ValueError("legacy stream on the device: MT19937 only")
-        ms = MtState()
-        key = np.ascontiguousarray(state["state"]["key"], dtype=np.uint32)
-        ctypes.memmove(ms.key, key.ctypes.data, 624 * 4)
-        ms.pos, ms.has_gauss, ms.gauss = int(state["state"]["pos"]), int(state["has_gauss"]), float(state["gauss"])
+        ms = _mt_struct(state)
         g = out if out is not None else self.empty((n,))
         assert g.numel() >= n
         _check(self.lib.corahip_normals_mt19937_legacy(self.h, ctypes.byref(ms), int(n), self._f64(g)))
-        new = {"bit_generator": "MT19937", "state": {"key": np.frombuffer(ms.key, dtype=np.uint32).copy(), "pos": int(ms.pos)},
-               "has_gauss": int(ms.has_gauss), "gauss": float(ms.gauss)}
-        return g, new
+        return g, _mt_dict(ms)
 
     def draw_alm(self, T, info, g, lmax, F, nu0=0, nnu=None, out=None):
         nnu = F if nnu is None else nnu
-        nalm = (lmax + 1) * (lmax + 2) // 2
-        G = (nnu + 3) // 4
-        alm = out if out is not None else self.empty((nalm, G, 2, 4))
-        _check(self.lib.corahip_draw_alm(self.h, self._f64(T), self._p(info) if info is not None else None,
+        alm = self._alm_out(lmax, nnu, out)
+        _check(self.lib.corahip_draw_alm(self.h, self._f64(T), self._p0(info),
                                          self._f64(g), lmax, F, nu0, nnu, self._f64(alm)))
         return alm
 
     def draw_alm_rows(self, T_rows, info, g, lmax, F, nu0, nnu, out=None):
         """draw_alm with T_rows [lmax+1, nnu, F] = rows nu0..nu0+nnu-1 of every factor."""
         assert tuple(T_rows.shape) == (lmax + 1, nnu, F), T_rows.shape
-        nalm = (lmax + 1) * (lmax + 2) // 2
-        G = (nnu + 3) // 4
-        alm = out if out is not None else self.empty((nalm, G, 2, 4))
-        _check(self.lib.corahip_draw_alm_rows(self.h, self._f64(T_rows), self._p(info) if info is not None else None,
+        alm = self._alm_out(lmax, nnu, out)
+        _check(self.lib.corahip_draw_alm_rows(self.h, self._f64(T_rows), self._p0(info),
                                               self._f64(g), lmax, F, nu0, nnu, self._f64(alm)))
         return alm
 
     def draw_alm_numpy_prepare(self, rng, lmax, F, ring_bytes=0):
         """``corahip_draw_alm_numpy_prepare``: the generator's part of :meth:`draw_alm_numpy` - its count / jump passes and
         the first two ranges of normals - enqueued on the library's generator stream NOW, so that it runs beside
-        whatever the caller enqueues next (the kernels that make the factors).  Returns the handle ``draw_alm_numpy``
-        takes as ``prepared``; ``handle.abort()`` gives the session up (generator untouched)."""
-        r, ms = _rng_struct(rng)
-        pend = c_void_p()
-        _check(self.lib.corahip_draw_alm_numpy_prepare(self.h, ctypes.byref(r), int(lmax), int(F), int(ring_bytes), ctypes.byref(pend)))
-        ctx = self
-
-        class Prepared:
-            rng_struct, mt_state, pending, shape, live = r, ms, pend, (int(lmax), int(F)), True
-
-            def abort(self):
-                if self.live:
-                    self.live = False
-                    _check(ctx.lib.corahip_draw_alm_numpy_end(ctx.h, self.pending, ctypes.byref(self.rng_struct)))
-
-        return Prepared()
+        whatever the caller enqueues next (the kernels that make the factors).  Returns the :class:`DrawSession`
+        ``draw_alm_numpy`` takes as ``prepared``; its ``abort()`` gives the session up (generator untouched)."""
+        return DrawSession(self, rng, lmax, F, ring_bytes)
 
     def draw_alm_numpy(self, T, info, rng, lmax, F, nu0=0, nnu=None, out=None, rows=False, ring_bytes=0, defer=False,
                        chunks=None, prepared=None):
@@ -543,70 +596,24 @@ class Context:
         everything is enqueued, nothing waited for; ``finish()`` (``corahip_draw_alm_numpy_end``: the one read-back)
         returns the state after and is called once the caller has enqueued what follows (the synthesis).
         ``chunks``: [(first, count), (first, count)] - the two chunks of a folded frequency shard (row-block T in local
-        channel order) instead of ``nu0`` / ``nnu``.  ``prepared``: the handle of :meth:`draw_alm_numpy_prepare` (``rng``
-        is then ignored: the session carries the generator)."""
-        import numpy as np
-
-        if chunks is not None:
-            rows, nu0, nnu = True, chunks[0][0], sum(c[1] for c in chunks)
-        nnu = F if nnu is None else nnu
-        assert tuple(T.shape) == ((lmax + 1, nnu, F) if rows else (lmax + 1, F, F)), T.shape
-        nalm = (lmax + 1) * (lmax + 2) // 2
-        alm = out if out is not None else self.empty((nalm, (nnu + 3) // 4, 2, 4))
-        if prepared is not None:
-            # the generator's passes were enqueued earlier (draw_alm_numpy_prepare): K3 against the factors now
-            assert prepared.live and prepared.shape == (int(lmax), int(F)), "the prepared session is for another shape"
-            r, ms, pend = prepared.rng_struct, prepared.mt_state, prepared.pending
-            cs = _chanset(chunks if chunks is not None and len(chunks) > 1 else [(nu0, nnu)])
-            prepared.live = False
-            try:
-                _check(self.lib.corahip_draw_alm_numpy_run(self.h, pend, self._f64(T), 1 if rows else 0,
-                                                           self._p(info) if info is not None else None, ctypes.byref(cs), self._f64(alm)))
-            except CoraHipError:
-                self.lib.corahip_draw_alm_numpy_end(self.h, pend, ctypes.byref(r))       # (frees the session)
-                raise
-        else:
-            r, ms = _rng_struct(rng)
-            pend = c_void_p()
-            if chunks is not None and len(chunks) > 1:
-                cs = _chanset(chunks)
-                _check(self.lib.corahip_draw_alm_numpy_begin_set(self.h, self._f64(T), self._p(info) if info is not None else None,
-                                                                 ctypes.byref(r), lmax, F, ctypes.byref(cs), self._f64(alm),
-                                                                 int(ring_bytes), ctypes.byref(pend)))
-            else:
-                _check(self.lib.corahip_draw_alm_numpy_begin(self.h, self._f64(T), 1 if rows else 0,
-                                                             self._p(info) if info is not None else None, ctypes.byref(r), lmax,
-                                                             F, nu0, nnu, self._f64(alm), int(ring_bytes), ctypes.byref(pend)))
-        keep = [T, info, alm]           # (alive until the queue has been waited for)
-
-        def finish():
-            _check(self.lib.corahip_draw_alm_numpy_end(self.h, pend, ctypes.byref(r)))
-            keep.clear()
-            if ms is not None:
-                return {"bit_generator": "MT19937", "state": {"key": np.frombuffer(ms.key, dtype=np.uint32).copy(), "pos": int(ms.pos)},
-                        "has_gauss": int(ms.has_gauss), "gauss": float(ms.gauss)}
-            return (int(r.state[0]) << 64) | int(r.state[1])
-
-        if defer:
-            return alm, finish
-        return alm, finish()
+        channel order) instead of ``nu0`` / ``nnu``.  ``prepared``: the session of :meth:`draw_alm_numpy_prepare` (``rng``
+        and ``ring_bytes`` are then ignored: the session carries the generator); without it the session is made here."""
+        session = prepared if prepared is not None else self.draw_alm_numpy_prepare(rng, lmax, F, ring_bytes)
+        alm = session.run(T, info, lmax, F, nu0=nu0, nnu=nnu, out=out, rows=rows, chunks=chunks)
+        return (alm, session.finish) if defer else (alm, session.finish())
 
     def draw_alm_philox(self, T, info, seed, lmax, F, nu0=0, nnu=None, out=None):
         nnu = F if nnu is None else nnu
-        nalm = (lmax + 1) * (lmax + 2) // 2
-        G = (nnu + 3) // 4
-        alm = out if out is not None else self.empty((nalm, G, 2, 4))
-        _check(self.lib.corahip_draw_alm_philox(self.h, self._f64(T), self._p(info) if info is not None else None,
+        alm = self._alm_out(lmax, nnu, out)
+        _check(self.lib.corahip_draw_alm_philox(self.h, self._f64(T), self._p0(info),
                                                 c_u64(int(seed) & (2**64 - 1)), lmax, F, nu0, nnu, self._f64(alm)))
         return alm
 
     def draw_alm_philox_rows(self, T_rows, info, seed, lmax, F, nu0, nnu, out=None):
         """draw_alm_philox with T_rows [lmax+1, nnu, F] = rows nu0..nu0+nnu-1 of every factor."""
         assert tuple(T_rows.shape) == (lmax + 1, nnu, F), T_rows.shape
-        nalm = (lmax + 1) * (lmax + 2) // 2
-        G = (nnu + 3) // 4
-        alm = out if out is not None else self.empty((nalm, G, 2, 4))
-        _check(self.lib.corahip_draw_alm_philox_rows(self.h, self._f64(T_rows), self._p(info) if info is not None else None,
+        alm = self._alm_out(lmax, nnu, out)
+        _check(self.lib.corahip_draw_alm_philox_rows(self.h, self._f64(T_rows), self._p0(info),
                                                      c_u64(int(seed) & (2**64 - 1)), lmax, F, nu0, nnu, self._f64(alm)))
         return alm
 
@@ -615,10 +622,9 @@ class Context:
         chunks of a folded frequency shard; T_rows [lmax+1, sum(count), F] in local channel order."""
         nnu = sum(int(c[1]) for c in chunks)
         assert tuple(T_rows.shape) == (lmax + 1, nnu, F), T_rows.shape
-        nalm = (lmax + 1) * (lmax + 2) // 2
-        alm = out if out is not None else self.empty((nalm, (nnu + 3) // 4, 2, 4))
+        alm = self._alm_out(lmax, nnu, out)
         cs = _chanset(chunks)
-        _check(self.lib.corahip_draw_alm_philox_rows_set(self.h, self._f64(T_rows), self._p(info) if info is not None else None,
+        _check(self.lib.corahip_draw_alm_philox_rows_set(self.h, self._f64(T_rows), self._p0(info),
                                                          c_u64(int(seed) & (2**64 - 1)), lmax, F, ctypes.byref(cs),
                                                          self._f64(alm)))
         return alm
@@ -654,7 +660,7 @@ class Context:
         assert packed.dtype == torch.complex128
         nnu, nalm = packed.shape
         assert nalm == (lmax + 1) * (lmax + 2) // 2
-        alm = self.empty((nalm, (nnu + 3) // 4, 2, 4))
+        alm = self._alm_out(lmax, nnu)
         _check(self.lib.corahip_alm_packed_to_dev(self.h, self._p(packed), lmax, nnu, self._f64(alm)))
         return alm
 
@@ -715,34 +721,16 @@ class Context:
         nnu = F if nnu is None else nnu
         plan = self.sht_plan(nside, lmax)
 
-        class MtState(ctypes.Structure):
-            _fields_ = [("key", ctypes.c_uint32 * 624), ("pos", ctypes.c_int32), ("has_gauss", ctypes.c_int32),
-                        ("gauss", c_double)]
-
-        class Rng(ctypes.Structure):
-            _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("stream", c_void_p), ("seed", c_u64),
-                        ("state", c_u64 * 2), ("inc", c_u64 * 2), ("legacy", ctypes.POINTER(MtState))]
-
-        r = Rng()
-        M = 2**64 - 1
         kind = {"stream": 0, "philox": 1, "pcg64": 2, "legacy": 3}[rng[0]]
-        ms = None
-        if kind == 3:        # ("legacy", np.random.get_state(legacy=False)): returns the state dict after the draws
-            import numpy as np
-
-            ms = MtState()
-            key = np.ascontiguousarray(rng[1]["state"]["key"], dtype=np.uint32)
-            ctypes.memmove(ms.key, key.ctypes.data, 624 * 4)
-            ms.pos, ms.has_gauss, ms.gauss = int(rng[1]["state"]["pos"]), int(rng[1]["has_gauss"]), float(rng[1]["gauss"])
-            r.legacy = ctypes.pointer(ms)
-        r.kind = kind
-        if kind == 0:
-            r.stream = self._f64(rng[1])
-        elif kind == 1:
-            r.seed = int(rng[1]) & M
-        elif kind == 2:
-            r.state[0], r.state[1] = (int(rng[1]) >> 64) & M, int(rng[1]) & M
-            r.inc[0], r.inc[1] = (int(rng[2]) >> 64) & M, int(rng[2]) & M
+        if kind >= 2:        # ("legacy", np.random.get_state(legacy=False)): returns the state dict after the draws
+            r, ms = _rng_struct(rng)
+        else:
+            r, ms = _Rng(), None
+            r.kind = kind
+            if kind == 0:
+                r.stream = self._f64(rng[1])
+            else:
+                r.seed = int(rng[1]) & (2**64 - 1)
         b = c_size_t()
         _check(self.lib.corahip_mkfullsky_workspace_bytes(plan, F, nu0, nnu, kind, 1 if alms else 0, ctypes.byref(b)))
         need = int(b.value) if workspace_bytes is None else int(workspace_bytes)
@@ -756,10 +744,7 @@ class Context:
         _check(self.lib.corahip_mkfullsky(self.h, plan, self._f64(C), F, ctypes.byref(r), nu0, nnu, 1 if alms else 0,
                                           c_void_p(out.data_ptr()), self._p(ws), need))
         if kind == 3:
-            import numpy as np
-
-            return out, {"bit_generator": "MT19937", "state": {"key": np.frombuffer(ms.key, dtype=np.uint32).copy(), "pos": int(ms.pos)},
-                         "has_gauss": int(ms.has_gauss), "gauss": float(ms.gauss)}
+            return out, _mt_dict(ms)
         return out, ((int(r.state[0]) << 64) | int(r.state[1])) if kind == 2 else None
 
     def map2alm_workspace_bytes(self, plan, nnu):

@@ -13,6 +13,8 @@ HIP kernels behind ``libcorahip.so``:
 
 ``mkconstrained`` (cora/core/skysim.py:139-201) is built on the analysis kernels (K5^T, K4^T).
 """
+import weakref
+
 import numpy as np
 import scipy.integrate as si
 
@@ -234,20 +236,46 @@ def stream_normals(ctx, numz, maxl, rng):
 
 
 class _PreparedStream:
-    """A numpy stream whose device generator has been started ahead of the factors (:func:`prepare_numpy_stream`): holds
-    the generator's lock until the draw's ``finish()`` - or :meth:`abort` - has run."""
+    """A numpy stream whose device generator has been started ahead of the factors (:func:`prepare_numpy_stream`): the one
+    owner of the generator's lock AND the draw session (``_lib.DrawSession``), from here to :meth:`finish` or
+    :meth:`abort` - or to the finalizer of an object that was dropped without either.  The lock is released exactly
+    once, and only here."""
 
-    def __init__(self, rng, legacy, lock, state, handle):
-        self.rng, self.legacy, self.lock, self.state, self.handle = rng, legacy, lock, state, handle
+    def __init__(self, rng, legacy, lock, state, session):
+        """``lock``: held by the caller, handed over here; ``state``: the PCG64 bit generator's state dict read under it."""
+        self.rng, self.legacy, self.state, self.session = rng, legacy, state, session
+        self._close = weakref.finalize(self, self._end, session, lock)            # (runs once, whoever calls it first)
+
+    @staticmethod
+    def _end(session, lock):
+        try:
+            session.abort()                                # (nothing to do behind a finish or a failed run)
+        finally:
+            lock.release()
+
+    def draw(self, T, info, maxl, numz, **kw):
+        """K3 against the factors (keywords of ``DrawSession.run``); a failure gives the session up."""
+        try:
+            return self.session.run(T, info, maxl, numz, **kw)
+        except BaseException:
+            self.abort()
+            raise
+
+    def finish(self):
+        """Waits for the draw, leaves the generator where numpy would leave it and releases its lock."""
+        try:
+            after = self.session.finish()
+            if self.legacy is not None:
+                self.legacy[1](after)
+            else:
+                self.state["state"]["state"] = after
+                self.rng.bit_generator.state = self.state  # (has_uint32 / uinteger untouched, as standard_normal leaves them)
+        finally:
+            self._close()
 
     def abort(self):
-        """Give the session up (the factors could not be made): the generator is left as it was."""
-        try:
-            self.handle.abort()
-        finally:
-            if self.lock is not None:
-                self.lock.release()
-                self.lock = None
+        """Give the session up (the factors could not be made): the generator is left as it was.  Idempotent."""
+        self._close()
 
 
 def prepare_numpy_stream(ctx, rng, maxl, numz):
@@ -256,13 +284,13 @@ def prepare_numpy_stream(ctx, rng, maxl, numz):
     MT19937 stream, and the first two ranges of normals) then run BESIDE the kernels the caller enqueues next - the
     C_l integration and the factorisation (the stream is a function of the generator alone: the reference draws it inside
     ``mkfullsky``, cora/util/nputil.py:121-125, but nothing it draws depends on the covariance).  Returns the object
-    ``draw_numpy_stream(..., prepared=...)`` takes, or None for a generator that is consumed on the host.  The
-    generator's lock is held from here to the end of the draw."""
+    ``draw_numpy_stream(..., prepared=...)`` takes, or None where the draw takes the host stream: a generator that is
+    consumed on the host, or a set-up refused as a STATE error (``CORAHIP_ESTATE``: a session still pending on the
+    context) - lock released, generator untouched.  Otherwise the generator's lock is held from here to the end of the draw."""
     legacy = _legacy_state_of(rng)
-    pcg = legacy is None and _is_pcg64_generator(rng)
-    if legacy is None and not pcg:
+    if legacy is None and not _is_pcg64_generator(rng):
         return None
-    lock = legacy[2] if legacy is not None else rng.bit_generator.lock
+    lock = legacy[2] if legacy is not None else rng.bit_generator.lock       # the lock numpy's own draws hold
     lock.acquire()
     try:
         if legacy is not None:
@@ -271,11 +299,13 @@ def prepare_numpy_stream(ctx, rng, maxl, numz):
         else:
             st = rng.bit_generator.state
             spec = ("pcg64", int(st["state"]["state"]), int(st["state"]["inc"]))
-        handle = ctx.draw_alm_numpy_prepare(spec, maxl, numz)
-    except BaseException:
+        session = ctx.draw_alm_numpy_prepare(spec, maxl, numz)
+    except BaseException as e:
         lock.release()
+        if isinstance(e, _lib.CoraHipError) and e.status == _lib.CORAHIP_ESTATE:
+            return None                                    # (the only status that is a reason to take the host stream)
         raise
-    return _PreparedStream(rng, legacy, lock, st, handle)
+    return _PreparedStream(rng, legacy, lock, st, session)
 
 
 def draw_numpy_stream(ctx, T, info, rng, maxl, numz, nu0=0, nnu=None, out=None, rows=False, defer=False, chunks=None,
@@ -324,65 +354,17 @@ def draw_numpy_stream(ctx, T, info, rng, maxl, numz, nu0=0, nnu=None, out=None, 
             return ctx.draw_alm_rows(T, info, g, maxl, numz, nu0, nnu, out=out)
         return ctx.draw_alm(T, info, g, maxl, numz, nu0=nu0, nnu=nnu, out=out)
 
-    def done(alm, finish=lambda: None):
-        if defer:
-            return alm, finish
-        finish()
-        return alm
-
-    if prepared is not None:
-        # the generator was started ahead of the factors (prepare_numpy_stream): its lock is held, K3 runs against T now
-        legacy, lock, st = prepared.legacy, prepared.lock, prepared.state
-        if legacy is not None:
-            get_state, set_state, _ = legacy
-        else:
-            bg = prepared.rng.bit_generator
-        prepared.lock = None                               # (released by finish() below, or here on failure)
-        try:
-            alm, fin = ctx.draw_alm_numpy(T, info, None, maxl, numz, nu0=nu0, nnu=nnu, out=out, rows=rows, defer=True,
-                                          chunks=chunks, prepared=prepared.handle)
-        except BaseException:
-            lock.release()
-            raise
+    if prepared is None:
+        prepared = prepare_numpy_stream(ctx, rng, maxl, numz)
+    if prepared is None:
+        alm, finish = host_path(), lambda: None
     else:
-        legacy = _legacy_state_of(rng)
-        pcg = legacy is None and _is_pcg64_generator(rng)
-        if legacy is None and not pcg:
-            return done(host_path())
-        if legacy is not None:
-            get_state, set_state, lock = legacy
-        else:
-            bg = rng.bit_generator
-            lock = bg.lock                                     # the lock numpy's own draws hold
-        lock.acquire()
-        try:
-            if legacy is not None:
-                spec = ("legacy", get_state(legacy=False))
-            else:
-                st = bg.state
-                spec = ("pcg64", int(st["state"]["state"]), int(st["state"]["inc"]))
-            alm, fin = ctx.draw_alm_numpy(T, info, spec, maxl, numz, nu0=nu0, nnu=nnu, out=out, rows=rows, defer=True, chunks=chunks)
-        except _lib.CoraHipError as e:
-            lock.release()
-            if e.status != -3:                                 # only CORAHIP_ESTATE is a reason to take the host stream
-                raise
-            return done(host_path())
-        except BaseException:
-            lock.release()
-            raise
-
-    def finish():
-        try:
-            after = fin()
-            if legacy is not None:
-                set_state(after)
-            else:
-                st["state"]["state"] = after
-                bg.state = st                              # (has_uint32 / uinteger untouched, as standard_normal leaves them)
-        finally:
-            lock.release()
-
-    return done(alm, finish)
+        # the generator runs (started here, or ahead of the factors by the caller): its lock is held, K3 runs against T now
+        alm, finish = prepared.draw(T, info, maxl, numz, nu0=nu0, nnu=nnu, out=out, rows=rows, chunks=chunks), prepared.finish
+    if defer:
+        return alm, finish
+    finish()
+    return alm
 
 
 def factor_device(corr):
@@ -412,6 +394,8 @@ def mkfullsky_device(corr, nside, alms=False, rng=None, factors=None, nu_range=N
     if factors is None:
         numz = corr.shape[1]
         if corr.shape[2] != numz:
+            if prep is not None:
+                prep.abort()
             raise Exception("Correlation matrix is incorrect shape.")
         if prep is None and not isinstance(rng, DeviceRNG):
             # numpy's stream does not depend on the covariance: its generator passes start here, beside the factorisation

@@ -48,11 +48,14 @@ struct corahip_draw_pending {
     unsigned long long slot_elems = 0;
     double *ring = nullptr;
     int lmax = 0, F = 0, emitted = 0;
-    bool ran = false;
+    // PREPARED -> RUNNING (given to corahip_draw_alm_numpy_run) -> RAN (everything is enqueued).  A run that fails stays
+    // RUNNING: it cannot be repeated, and _end treats it as a session that never ran
+    enum { PREPARED, RUNNING, RAN } state = PREPARED;
 };
 
+// ONE rule of ownership: corahip_draw_alm_numpy_prepare frees a session it could not set up (no handle exists yet); once it has
+// returned one, corahip_draw_alm_numpy_end frees it and nothing else does - whatever became of the run in between
 static void pending_free(corahip_draw_pending *p) {
-    if (!p) return;
     if (p->zs) zig_stream_free(p->zs);
     if (p->ms) mt_stream_free(p->ms);
     delete p;
@@ -65,16 +68,12 @@ static void pending_free(corahip_draw_pending *p) {
             corahip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
             (void)hipStreamSynchronize(B);                                                                   \
             (void)hipStreamSynchronize(A);                                                                   \
-            if (own) {                                                                                       \
-                ctx->draw_pending = nullptr;                                                                 \
-                pending_free(pd);                                                                            \
-            }                                                                                                \
             return (int)_e;                                                                                  \
         }                                                                                                    \
     } while (0)
 
 // emit range r into its ring slot on the generator stream (behind the draw of the range that held the slot before)
-static int emit_range(corahip_ctx *ctx, corahip_draw_pending *pd, int r, bool own) {
+static int emit_range(corahip_ctx *ctx, corahip_draw_pending *pd, int r) {
     hipStream_t A = ctx->stream, B = ctx->gen_stream;
     hipEvent_t ev_emit[2] = {ctx->ev_ring[1], ctx->ev_ring[2]}, ev_drawn[2] = {ctx->ev_ring[3], ctx->ev_ring[4]};
     const int sl = r & 1;
@@ -86,13 +85,40 @@ static int emit_range(corahip_ctx *ctx, corahip_draw_pending *pd, int r, bool ow
     return 0;
 }
 
+// the launches of corahip_draw_alm_numpy_prepare, all on the generator stream
+static int prepare_enqueue(corahip_ctx *ctx, const corahip_rng *rng, corahip_draw_pending *pd) {
+    hipStream_t A = ctx->stream, B = ctx->gen_stream;
+    const int nr = (int)pd->bounds.size() - 1;
+    const int64_t n = (int64_t)pd->bounds[nr];
+    // The generator stream never starts before the context's stream has reached this call (the ring and the generator
+    // tables may still be read by a draw queued there: a caller that pipelines realisations without synchronising)
+    DS_TRY(hipEventRecord(ctx->ev_ring[0], A));
+    DS_TRY(hipStreamWaitEvent(B, ctx->ev_ring[0], 0));
+    int rc;
+    if (rng->kind == CORAHIP_RNG_PCG64) rc = zig_stream_prepare(ctx, B, rng->state, rng->inc, n, pd->bounds, &pd->zs);
+    else {
+        corahip_mt_state st0 = *rng->legacy;       // (prepare reads it; the caller's copy is rewritten by _end only)
+        rc = mt_stream_prepare(ctx, B, &st0, n, pd->bounds, &pd->ms);
+    }
+    // both ring slots are free: the first two ranges are emitted right away (they too run beside whatever the caller
+    // enqueues on the context's stream before it hands the factors over)
+    for (int r = 0; r < std::min(nr, 2) && !rc; r++) {
+        rc = emit_range(ctx, pd, r);
+        if (!rc) pd->emitted = r + 1;
+    }
+    if (rc) (void)hipStreamSynchronize(B);
+    return rc;
+}
+
+extern "C" {
+
 // The generator's part of a draw that does not depend on the factors: ranges, ring, the generator's own prepare passes
 // (count + scan / jump tree + count) and the emit passes of the first two ranges (both ring slots are free) - all on the
 // generator stream.  A caller that issues this BEFORE the launches that make the factors (K1, K2) lets the generator run
 // beside them; the stream is a function of the generator alone (cora/util/nputil.py:121-125 draws it inside mkfullsky,
 // but nothing it draws depends on the covariance).
-static int draw_numpy_prepare(corahip_ctx *ctx, const corahip_rng *rng, int lmax, int F, size_t ring_bytes,
-                              corahip_draw_pending **pending) {
+int corahip_draw_alm_numpy_prepare(corahip_ctx *ctx, const corahip_rng *rng, int lmax, int F, size_t ring_bytes,
+                                   corahip_draw_pending **pending) {
     ARG_CHECK(ctx != nullptr && rng != nullptr && pending != nullptr);
     ARG_CHECK(lmax >= 0 && F >= 1);
     ARG_CHECK(rng->kind == CORAHIP_RNG_PCG64 || rng->kind == CORAHIP_RNG_MT19937);
@@ -141,31 +167,12 @@ static int draw_numpy_prepare(corahip_ctx *ctx, const corahip_rng *rng, int lmax
         pd->l_first.push_back(lmax + 1);
     }
     const int nr = (int)pd->bounds.size() - 1;
-    const int64_t n = (int64_t)total;
-    if ((rc = corahip_ctx_scratch(ctx, 7, sizeof(double) * (nr > 1 ? 2 : 1) * (size_t)pd->slot_elems, (void **)&pd->ring))) {
-        pending_free(pd);
-        return rc;
+    rc = corahip_ctx_scratch(ctx, 7, sizeof(double) * (nr > 1 ? 2 : 1) * (size_t)pd->slot_elems, (void **)&pd->ring);
+    if (!rc) {
+        ctx->draw_pending = pd;
+        rc = prepare_enqueue(ctx, rng, pd);
     }
-    hipStream_t A = ctx->stream, B = ctx->gen_stream;
-    const bool own = true;
-    // The generator stream never starts before the context's stream has reached this call (the ring and the generator
-    // tables may still be read by a draw queued there: a caller that pipelines realisations without synchronising)
-    ctx->draw_pending = pd;
-    DS_TRY(hipEventRecord(ctx->ev_ring[0], A));
-    DS_TRY(hipStreamWaitEvent(B, ctx->ev_ring[0], 0));
-    if (rng->kind == CORAHIP_RNG_PCG64) rc = zig_stream_prepare(ctx, B, rng->state, rng->inc, n, pd->bounds, &pd->zs);
-    else {
-        corahip_mt_state st0 = *rng->legacy;       // (prepare reads it; the caller's copy is rewritten by _end only)
-        rc = mt_stream_prepare(ctx, B, &st0, n, pd->bounds, &pd->ms);
-    }
-    // both ring slots are free: the first two ranges are emitted right away (they too run beside whatever the caller
-    // enqueues on the context's stream before it hands the factors over)
-    for (int r = 0; r < std::min(nr, 2) && !rc; r++) {
-        rc = emit_range(ctx, pd, r, own);
-        if (!rc) pd->emitted = r + 1;
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(B);
+    if (rc) {                                      // the one free outside _end: no handle has been returned
         ctx->draw_pending = nullptr;
         pending_free(pd);
         return rc;
@@ -174,23 +181,24 @@ static int draw_numpy_prepare(corahip_ctx *ctx, const corahip_rng *rng, int lmax
     return 0;
 }
 
-// K3 of every range against the factors, on the context's stream, the remaining emit passes on the generator stream
-static int draw_numpy_run(corahip_ctx *ctx, corahip_draw_pending *pd, const double *T, int rows, const int32_t *info,
-                          const corahip_chanset *set, double *alm_dev, bool own) {
+// K3 of every range against the factors, on the context's stream, the remaining emit passes on the generator stream.  A
+// failure leaves the session to the caller: corahip_draw_alm_numpy_end frees it
+int corahip_draw_alm_numpy_run(corahip_ctx *ctx, corahip_draw_pending *pd, const double *T, int rows, const int32_t *info,
+                               const corahip_chanset *set, double *alm_dev) {
     ARG_CHECK(ctx != nullptr && pd != nullptr && T != nullptr && alm_dev != nullptr && set != nullptr);
-    ARG_CHECK(ctx->draw_pending == pd && !pd->ran);
+    ARG_CHECK(ctx->draw_pending == pd && pd->state == corahip_draw_pending::PREPARED);
     hipStream_t A = ctx->stream, B = ctx->gen_stream;
     hipEvent_t ev_emit[2] = {ctx->ev_ring[1], ctx->ev_ring[2]}, ev_drawn[2] = {ctx->ev_ring[3], ctx->ev_ring[4]};
     const int nr = (int)pd->bounds.size() - 1;
     int rc = 0;
-    pd->ran = true;
+    pd->state = corahip_draw_pending::RUNNING;
     {
         StageTimer t(ctx, "draw");
         for (int r = 0; r < nr && !rc; r++) {
             const int sl = r & 1;
             double *slot = pd->ring + (size_t)sl * pd->slot_elems;
             if (r >= pd->emitted) {
-                rc = emit_range(ctx, pd, r, own);
+                rc = emit_range(ctx, pd, r);
                 if (rc) break;
                 pd->emitted = r + 1;
             }
@@ -204,70 +212,24 @@ static int draw_numpy_run(corahip_ctx *ctx, corahip_draw_pending *pd, const doub
     if (rc) {
         (void)hipStreamSynchronize(B);
         (void)hipStreamSynchronize(A);
-        if (own) {
-            ctx->draw_pending = nullptr;
-            pending_free(pd);
-        }
         return rc;
     }
     // (the last draw waited for the last emit: everything of the generator stream is behind the context stream's tail)
+    pd->state = corahip_draw_pending::RAN;
     return 0;
 }
 #undef DS_TRY
 
-static int draw_numpy_begin(corahip_ctx *ctx, const double *T, int rows, const int32_t *info, const corahip_rng *rng, int lmax,
-                            int F, const corahip_chanset *set, double *alm_dev, size_t ring_bytes,
-                            corahip_draw_pending **pending) {
-    ARG_CHECK(ctx != nullptr && T != nullptr && rng != nullptr && alm_dev != nullptr && pending != nullptr && set != nullptr);
-    corahip_draw_pending *pd = nullptr;
-    int rc = draw_numpy_prepare(ctx, rng, lmax, F, ring_bytes, &pd);
-    if (rc) return rc;
-    *pending = nullptr;
-    if ((rc = draw_numpy_run(ctx, pd, T, rows, info, set, alm_dev, true))) return rc;
-    *pending = pd;
-    return 0;
-}
-
-extern "C" {
-
-int corahip_draw_alm_numpy_begin(corahip_ctx *ctx, const double *T, int rows, const int32_t *info, const corahip_rng *rng,
-                                 int lmax, int F, int nu0, int nnu, double *alm_dev, size_t ring_bytes,
-                                 corahip_draw_pending **pending) {
-    ARG_CHECK(nu0 >= 0 && nnu >= 1 && nu0 + nnu <= F);
-    const corahip_chanset set = {1, nnu, {nu0, 0}};
-    return draw_numpy_begin(ctx, T, rows, info, rng, lmax, F, &set, alm_dev, ring_bytes, pending);
-}
-
-int corahip_draw_alm_numpy_begin_set(corahip_ctx *ctx, const double *T_rows, const int32_t *info, const corahip_rng *rng,
-                                     int lmax, int F, const corahip_chanset *set, double *alm_dev, size_t ring_bytes,
-                                     corahip_draw_pending **pending) {
-    return draw_numpy_begin(ctx, T_rows, 1, info, rng, lmax, F, set, alm_dev, ring_bytes, pending);
-}
-
-int corahip_draw_alm_numpy_prepare(corahip_ctx *ctx, const corahip_rng *rng, int lmax, int F, size_t ring_bytes,
-                                   corahip_draw_pending **pending) {
-    return draw_numpy_prepare(ctx, rng, lmax, F, ring_bytes, pending);
-}
-
-int corahip_draw_alm_numpy_run(corahip_ctx *ctx, corahip_draw_pending *pending, const double *T, int rows, const int32_t *info,
-                               const corahip_chanset *set, double *alm_dev) {
-    ARG_CHECK(set != nullptr && pending != nullptr);
-    // (a failure leaves the session to the caller: corahip_draw_alm_numpy_end frees it)
-    return draw_numpy_run(ctx, pending, T, rows, info, set, alm_dev, false);
-}
-
 int corahip_draw_alm_numpy_end(corahip_ctx *ctx, corahip_draw_pending *pd, corahip_rng *rng) {
     ARG_CHECK(ctx != nullptr && pd != nullptr && rng != nullptr);
     ARG_CHECK(ctx->draw_pending == pd);
-    int rc;
-    if (!pd->ran) {
-        // a prepared session that is given up (the factors could not be made): nothing was drawn, the generator stays
+    int rc = 0;
+    if (pd->state != corahip_draw_pending::RAN) {
+        // a session that is given up (the factors could not be made) or whose run failed: whatever was enqueued is waited
+        // for, nothing of it is used, the generator stays as it was
         (void)hipStreamSynchronize(ctx->gen_stream);
-        ctx->draw_pending = nullptr;
-        pending_free(pd);
-        return 0;
-    }
-    if (pd->zs) {
+        (void)hipStreamSynchronize(ctx->stream);
+    } else if (pd->zs) {
         uint64_t n_raw = 0, after[2];
         rc = zig_stream_finish(ctx, ctx->stream, pd->zs, &n_raw);
         if (!rc) rc = corahip_pcg64_advance(rng->state, rng->inc, n_raw, after);
@@ -282,6 +244,35 @@ int corahip_draw_alm_numpy_end(corahip_ctx *ctx, corahip_draw_pending *pd, corah
     ctx->draw_pending = nullptr;
     pending_free(pd);
     return rc;
+}
+
+// _prepare + _run; a session whose run failed is ended here (_end's given-up branch: `rng` is neither read nor written)
+static int draw_numpy_begin(corahip_ctx *ctx, const double *T, int rows, const int32_t *info, const corahip_rng *rng, int lmax,
+                            int F, const corahip_chanset *set, double *alm_dev, size_t ring_bytes,
+                            corahip_draw_pending **pending) {
+    ARG_CHECK(ctx != nullptr && T != nullptr && rng != nullptr && alm_dev != nullptr && pending != nullptr && set != nullptr);
+    int rc = corahip_draw_alm_numpy_prepare(ctx, rng, lmax, F, ring_bytes, pending);
+    if (rc) return rc;
+    if ((rc = corahip_draw_alm_numpy_run(ctx, *pending, T, rows, info, set, alm_dev))) {
+        corahip_rng unused = *rng;
+        (void)corahip_draw_alm_numpy_end(ctx, *pending, &unused);
+        *pending = nullptr;
+    }
+    return rc;
+}
+
+int corahip_draw_alm_numpy_begin(corahip_ctx *ctx, const double *T, int rows, const int32_t *info, const corahip_rng *rng,
+                                 int lmax, int F, int nu0, int nnu, double *alm_dev, size_t ring_bytes,
+                                 corahip_draw_pending **pending) {
+    ARG_CHECK(nu0 >= 0 && nnu >= 1 && nu0 + nnu <= F);
+    const corahip_chanset set = {1, nnu, {nu0, 0}};
+    return draw_numpy_begin(ctx, T, rows, info, rng, lmax, F, &set, alm_dev, ring_bytes, pending);
+}
+
+int corahip_draw_alm_numpy_begin_set(corahip_ctx *ctx, const double *T_rows, const int32_t *info, const corahip_rng *rng,
+                                     int lmax, int F, const corahip_chanset *set, double *alm_dev, size_t ring_bytes,
+                                     corahip_draw_pending **pending) {
+    return draw_numpy_begin(ctx, T_rows, 1, info, rng, lmax, F, set, alm_dev, ring_bytes, pending);
 }
 
 int corahip_draw_alm_numpy(corahip_ctx *ctx, const double *T, int rows, const int32_t *info, corahip_rng *rng, int lmax, int F,

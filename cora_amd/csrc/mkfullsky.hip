@@ -79,12 +79,11 @@ int corahip_mkfullsky(corahip_ctx *ctx, const corahip_sht_plan *plan, const doub
     const bool numpy_stream = rng->kind == CORAHIP_RNG_PCG64 || rng->kind == CORAHIP_RNG_MT19937;
     if (numpy_stream && (rc = corahip_draw_alm_numpy_prepare(ctx, rng, lmax, F, 0, &pending))) return rc;
     // skysim.py:115-119: C_l + I max(diag) 1e-14 -> Cholesky, eigen root where that fails (nputil.py:51-101, threshold 1e-16)
-    if ((rc = corahip_factor_batched(ctx, C, L, F, 1e-14, 1e-16, T, info))) {
-        if (pending) (void)corahip_draw_alm_numpy_end(ctx, pending, rng);     // (given up: the generator stays as it was)
-        return rc;
-    }
+    rc = corahip_factor_batched(ctx, C, L, F, 1e-14, 1e-16, T, info);
     // skysim.py:120-121
-    if (rng->kind == CORAHIP_RNG_PHILOX) {
+    if (rc) {
+        // (no factors: nothing is drawn)
+    } else if (rng->kind == CORAHIP_RNG_PHILOX) {
         rc = corahip_draw_alm_philox(ctx, T, info, rng->seed, lmax, F, nu0, nnu, alm);
     } else if (rng->kind == CORAHIP_RNG_STREAM) {
         rc = corahip_draw_alm(ctx, T, info, rng->stream, lmax, F, nu0, nnu, alm);
@@ -95,15 +94,22 @@ int corahip_mkfullsky(corahip_ctx *ctx, const corahip_sht_plan *plan, const doub
         const corahip_chanset set = {1, nnu, {nu0, 0}};
         rc = corahip_draw_alm_numpy_run(ctx, pending, T, 0, info, &set, alm);
     }
-    if (rc) {
-        if (pending) (void)corahip_draw_alm_numpy_end(ctx, pending, rng);     // (frees the session)
-        return rc;
-    }
     // skysim.py:123-130
-    if (alms) rc = corahip_alm_dev_to_square(ctx, alm, lmax, nnu, out);
-    else rc = corahip_alm2map(ctx, plan, alm, nnu, out, ws + lo.off_sht, workspace_bytes - lo.off_sht);
+    if (!rc) {
+        rc = alms ? corahip_alm_dev_to_square(ctx, alm, lmax, nnu, out)
+                  : corahip_alm2map(ctx, plan, alm, nnu, out, ws + lo.off_sht, workspace_bytes - lo.off_sht);
+    }
+    // the one exit of a session: _end frees it whatever happened above, and writes the generator back only when the
+    // run was enqueued whole (factors that could not be made, a failed run: the generator stays as it was).  An error
+    // return leaves the caller's generator as it was: behind a failed synthesis the state is read back into a copy
     if (pending) {
-        const int rc2 = corahip_draw_alm_numpy_end(ctx, pending, rng);
+        corahip_rng copy = *rng;
+        corahip_mt_state mt_copy;
+        if (rc && rng->legacy) {
+            mt_copy = *rng->legacy;
+            copy.legacy = &mt_copy;
+        }
+        const int rc2 = corahip_draw_alm_numpy_end(ctx, pending, rc ? &copy : rng);
         if (!rc) rc = rc2;
     }
     return rc;

@@ -294,8 +294,12 @@ int corahip_draw_alm_numpy_end(corahip_ctx *ctx, corahip_draw_pending *pending, 
  * factorisation) lets the generator run beside them (the stream is a function of the generator alone; the reference draws
  * it inside mkfullsky, cora/util/nputil.py:121-125, but nothing it draws depends on the covariance).  _run enqueues K3 of
  * every range against the factors (T full [L, F, F] with rows = 0 - `set` then names one block - or the row block of the
- * set's channels with rows = 1) and the remaining emit passes; _end as above.  A prepared session that is given up
- * (no _run) is freed by _end, which then leaves host_rng untouched.  _begin = _prepare + _run. */
+ * set's channels with rows = 1) and the remaining emit passes; _end as above.  _begin = _prepare + _run.
+ * Ownership: once _prepare has returned a session, _end and nothing else frees it - exactly one _end per session,
+ * whatever _run returned.  A session that is given up (no _run) or whose _run failed (it cannot be run again) is ended the
+ * same way: _end waits for both streams, frees it, returns 0 and leaves host_rng untouched.  _begin and
+ * corahip_draw_alm_numpy end a session whose run failed themselves.  Every error return of these entry points leaves
+ * host_rng as it was on entry. */
 int corahip_draw_alm_numpy_prepare(corahip_ctx *ctx, const corahip_rng *host_rng, int lmax, int F, size_t ring_bytes,
                                    corahip_draw_pending **pending);
 int corahip_draw_alm_numpy_run(corahip_ctx *ctx, corahip_draw_pending *pending, const double *T, int rows, const int32_t *info,

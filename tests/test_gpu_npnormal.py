@@ -512,3 +512,190 @@ def test_getsky_and_mkfullsky_start_the_generator_first(ctx, monkeypatch):
     m2 = skysim.mkfullsky(cl, 16, rng=np.random.default_rng(3))
     mean = np.asarray(sky.mean_nu(nu), dtype=np.float64) * np.ones(nu.shape)
     assert np.abs(m1 - mean[:, None] - m2).max() <= 1e-9 * np.abs(m2).max()
+
+
+# ------------------------------------------------------------------ who ends a draw session: every failure path
+_SESSION_SHAPE = (72, 150, 8, 32)                 # F, lmax, nu0, nnu
+_BAD_CHUNKS = [(0, 6), (8, 6)]                    # python takes two equal chunks; chan_of (draw.hip) wants whole cells of 4
+_session_cache = {}
+
+
+def _session_fresh(kind):
+    if kind == "pcg64":
+        g = np.random.default_rng(99)
+        g.standard_normal(5)
+        return g
+    rs = np.random.RandomState(98)
+    rs.standard_normal(3)                         # (an odd count: a cached value in front)
+    return rs
+
+
+def _session_case(ctx, kind):
+    """(T, info, reference a_lm of ``_session_fresh(kind)``): made once per kind, never written to."""
+    from cora_amd.core import skysim
+
+    F, lmax, nu0, nnu = _SESSION_SHAPE
+    if "factors" not in _session_cache:
+        _session_cache["factors"] = _factors(ctx, F, lmax, 4711)
+    Td, infod = _session_cache["factors"]
+    if kind not in _session_cache:
+        _session_cache[kind] = skysim.draw_numpy_stream(ctx, Td, infod, _session_fresh(kind), lmax, F, nu0=nu0, nnu=nnu).clone()
+    return Td, infod, _session_cache[kind]
+
+
+def _lock_of(rng):
+    from cora_amd.core import skysim
+
+    return rng.bit_generator.lock if isinstance(rng, np.random.Generator) else skysim._legacy_state_of(rng)[2]
+
+
+def _assert_nothing_lingers(ctx, kind, rng, twin):
+    """After a session that failed or was given up: the generator's lock is free, the generator is where its untouched
+    twin is, and the context takes the next draw (no CORAHIP_ESTATE left behind) with the reference's result."""
+    import torch
+
+    from cora_amd.core import skysim
+
+    F, lmax, nu0, nnu = _SESSION_SHAPE
+    Td, infod, ref = _session_case(ctx, kind)
+    lock = _lock_of(rng)
+    assert lock.acquire(False)
+    lock.release()
+    assert np.array_equal(rng.standard_normal(6), twin.standard_normal(6))
+    again = skysim.draw_numpy_stream(ctx, Td, infod, _session_fresh(kind), lmax, F, nu0=nu0, nnu=nnu)
+    assert torch.equal(again, ref)
+
+
+@pytest.mark.parametrize("kind", ["pcg64", "legacy"])
+def test_session_failure_before_run_ends_the_session(ctx, kind):
+    """A prepared session handed a T of the wrong shape: the refusal comes before corahip_draw_alm_numpy_run."""
+    from cora_amd.core import skysim
+
+    F, lmax, nu0, nnu = _SESSION_SHAPE
+    Td, infod, _ = _session_case(ctx, kind)
+    rng, twin = _session_fresh(kind), _session_fresh(kind)
+    prep = skysim.prepare_numpy_stream(ctx, rng, lmax, F)
+    assert prep is not None
+    with pytest.raises(AssertionError):
+        skysim.draw_numpy_stream(ctx, Td[:, :5, :].contiguous(), infod, rng, lmax, F, nu0=nu0, nnu=nnu, prepared=prep)
+    _assert_nothing_lingers(ctx, kind, rng, twin)
+
+
+@pytest.mark.parametrize("ahead", [True, False])
+@pytest.mark.parametrize("kind", ["pcg64", "legacy"])
+def test_session_failure_inside_run_ends_the_session(ctx, kind, ahead):
+    """corahip_draw_alm_numpy_run refuses the channel set of the first range (CORAHIP_EINVAL from chan_of: chunks of 6
+    channels are no whole a_lm cells): the session is marked running, nothing of K3 has been launched."""
+    from cora_amd import _lib
+    from cora_amd.core import skysim
+
+    F, lmax, _, _ = _SESSION_SHAPE
+    Td, infod, _ = _session_case(ctx, kind)
+    rng, twin = _session_fresh(kind), _session_fresh(kind)
+    prep = skysim.prepare_numpy_stream(ctx, rng, lmax, F) if ahead else None
+    with pytest.raises(_lib.CoraHipError) as e:
+        skysim.draw_numpy_stream(ctx, Td[:, :12, :].contiguous(), infod, rng, lmax, F, chunks=_BAD_CHUNKS, prepared=prep)
+    assert e.value.status == -1
+    _assert_nothing_lingers(ctx, kind, rng, twin)
+
+
+@pytest.mark.parametrize("kind", ["pcg64", "legacy"])
+def test_only_end_frees_a_session_and_a_failed_run_leaves_the_generator(ctx, kind):
+    """The C rule by raw ctypes: _prepare, a _run that fails (and cannot be repeated), ONE _end - which returns 0 and
+    leaves corahip_rng and the MT state byte for byte as they were.  The same failure through _begin_set, which ends
+    its session itself, and a refusal of the one-call corahip_draw_alm_numpy (one block of channels: its refusals come
+    before a session exists) leave them unchanged too."""
+    import ctypes
+
+    from cora_amd import _lib
+
+    F, lmax, nu0, nnu = _SESSION_SHAPE
+    Td, infod, _ = _session_case(ctx, kind)
+    rng, twin = _session_fresh(kind), _session_fresh(kind)
+    if kind == "pcg64":
+        st = rng.bit_generator.state["state"]
+        spec = ("pcg64", st["state"], st["inc"])
+    else:
+        spec = ("legacy", rng.get_state(legacy=False))
+    r, ms = _lib._rng_struct(spec)
+    before = (bytes(r), None if ms is None else bytes(ms))
+
+    def unchanged():
+        return (bytes(r), None if ms is None else bytes(ms)) == before
+
+    lib, EINVAL = ctx.lib, -1
+    Trows = Td[:, :12, :].contiguous()
+    alm = ctx.empty(((lmax + 1) * (lmax + 2) // 2, 3, 2, 4))
+    bad, good = _lib._chanset(_BAD_CHUNKS), _lib._chanset([(0, 12)])
+    pend = ctypes.c_void_p()
+    assert lib.corahip_draw_alm_numpy_prepare(ctx.h, ctypes.byref(r), lmax, F, 0, ctypes.byref(pend)) == 0
+    assert pend.value is not None
+    run = lambda cs: lib.corahip_draw_alm_numpy_run(ctx.h, pend, ctx._f64(Trows), 1, ctx._p(infod), ctypes.byref(cs), ctx._f64(alm))
+    assert run(bad) == EINVAL
+    assert run(good) == EINVAL                                     # a failed run is not repeated on the same session
+    assert lib.corahip_draw_alm_numpy_end(ctx.h, pend, ctypes.byref(r)) == 0
+    assert unchanged()
+    pend2 = ctypes.c_void_p()
+    assert lib.corahip_draw_alm_numpy_begin_set(ctx.h, ctx._f64(Trows), ctx._p(infod), ctypes.byref(r), lmax, F, ctypes.byref(bad),
+                                                ctx._f64(alm), 0, ctypes.byref(pend2)) == EINVAL
+    assert pend2.value is None and unchanged()
+    assert lib.corahip_draw_alm_numpy(ctx.h, ctx._f64(Td), 0, ctx._p(infod), ctypes.byref(r), lmax, F, F - 4, 8, ctx._f64(alm), 0) == EINVAL
+    assert unchanged()
+    _assert_nothing_lingers(ctx, kind, rng, twin)
+
+
+@pytest.mark.parametrize("kind", ["pcg64", "legacy"])
+def test_mkfullsky_device_shape_error_gives_a_held_session_up(ctx, kind):
+    from cora_amd.core import skysim
+
+    F, lmax, _, _ = _SESSION_SHAPE
+    rng, twin = _session_fresh(kind), _session_fresh(kind)
+    prep = skysim.prepare_numpy_stream(ctx, rng, lmax, F)
+    assert prep is not None
+    with pytest.raises(Exception, match="Correlation matrix is incorrect shape."):
+        skysim.mkfullsky_device(np.zeros((lmax + 1, F, F + 1)), 16, rng=rng, prepared=prep)
+    _assert_nothing_lingers(ctx, kind, rng, twin)
+
+
+@pytest.mark.parametrize("kind", ["pcg64", "legacy"])
+def test_a_second_generator_takes_the_host_stream_while_a_session_is_held(ctx, kind):
+    """CORAHIP_ESTATE at prepare is no error of the caller: prepare_numpy_stream returns None and draw_numpy_stream draws
+    from the host stream - the a_lm and the generator of the reference's own loop."""
+    import torch
+
+    from cora_amd.core import skysim
+
+    F, lmax, nu0, nnu = _SESSION_SHAPE
+    Td, infod, _ = _session_case(ctx, kind)
+    rng, twin = _session_fresh(kind), _session_fresh(kind)
+    held = skysim.prepare_numpy_stream(ctx, rng, lmax, F)
+    assert held is not None
+
+    def second():
+        return np.random.default_rng(7) if kind == "pcg64" else np.random.RandomState(7)
+
+    other, other_twin = second(), second()
+    assert skysim.prepare_numpy_stream(ctx, other, lmax, F) is None
+    assert _lock_of(other).acquire(False)
+    _lock_of(other).release()
+    alm = skysim.draw_numpy_stream(ctx, Td, infod, other, lmax, F, nu0=nu0, nnu=nnu)
+    host = ctx.draw_alm(Td, infod, skysim._upload_host_normals(ctx, F, lmax, other_twin), lmax, F, nu0=nu0, nnu=nnu)
+    assert torch.equal(alm, host)
+    assert np.array_equal(other.standard_normal(6), other_twin.standard_normal(6))
+    held.abort()
+    _assert_nothing_lingers(ctx, kind, rng, twin)
+
+
+@pytest.mark.parametrize("kind", ["pcg64", "legacy"])
+def test_a_dropped_prepared_stream_ends_its_session(ctx, kind):
+    import gc
+
+    from cora_amd.core import skysim
+
+    F, lmax, _, _ = _SESSION_SHAPE
+    rng, twin = _session_fresh(kind), _session_fresh(kind)
+    prep = skysim.prepare_numpy_stream(ctx, rng, lmax, F)
+    assert prep is not None
+    del prep
+    gc.collect()
+    _assert_nothing_lingers(ctx, kind, rng, twin)

@@ -8,6 +8,15 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _free_port():
+    """A rendezvous port that nothing holds now - a fixed number can be another process's, or an outgoing connection's."""
+    import socket
+
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        return sk.getsockname()[1]
+
+
 def test_shard_plan_covers_everything():
     from cora_amd.parallel import shard_plan
 
@@ -47,7 +56,7 @@ def test_allgather_factors_gloo_world2():
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29500 + os.getpid() % 2000
+    port = _free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -95,7 +104,7 @@ def test_all_to_all_exchanges_gloo_world2():
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 31500 + os.getpid() % 2000
+    port = _free_port()
     procs = [ctx.Process(target=_worker_a2a, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
@@ -136,7 +145,7 @@ def test_allgather_channels_gloo(world):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 33500 + os.getpid() % 2000 + world
+    port = _free_port()
     procs = [ctx.Process(target=_worker_chan, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -207,7 +216,7 @@ def test_folded_factor_row_exchange_gloo(world):
 
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 35500 + os.getpid() % 2000 + world
+    port = _free_port()
     procs = [ctx.Process(target=_worker_fold, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -251,7 +260,7 @@ def test_a_hung_exchange_exits_nonzero_and_names_its_stage(capfd):
     import torch.multiprocessing as mp
 
     ctx = mp.get_context("spawn")
-    port = 31500 + os.getpid() % 2000
+    port = _free_port()
     procs = [ctx.Process(target=_worker_hang, args=(r, 2, port)) for r in range(2)]
     for p in procs:
         p.start()
