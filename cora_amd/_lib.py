@@ -116,6 +116,7 @@ SIGNATURES = {
                                       PTR]),
     "corahip_bias_field": (c_int, [c_void_p, PTR, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
     "corahip_lognormal": (c_int, [c_void_p, PTR, PTR, PTR, c_double, c_int, ctypes.c_long, ctypes.c_long, PTR]),
+    "corahip_alm_cross_spectra": (c_int, [c_void_p, PTR, c_int, PTR, c_int, c_int, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -663,6 +664,34 @@ class Context:
         alm = self._alm_out(lmax, nnu)
         _check(self.lib.corahip_alm_packed_to_dev(self.h, self._p(packed), lmax, nnu, self._f64(alm)))
         return alm
+
+    def alm_cross_spectra(self, alm_a, nx, lmax, alm_b=None, ny=None, out=None):
+        """The multi-frequency spectrum of a_lm in the device layout, ``[lmax + 1, nx, ny]`` (clarray's layout):
+        ``out[l, i, j] = sum_m c_m (Re a_i Re b_j + Im a_i Im b_j) / (2l + 1)``, ``c_0 = 1``, ``c_{m>0} = 2`` - healpy's
+        ``alm2cl`` for every pair of channels, one FP64 MFMA Gram product per l (``corahip_alm_cross_spectra``).
+
+        ``alm_a`` [nalm, ceil(nx / 4), 2, 4] as ``map2alm`` and ``draw_alm*`` return it; ``alm_b`` (with ``ny``) a second
+        operand of the same lmax, ``None`` (or ``alm_a`` itself): the symmetric case, whose result equals its transpose
+        bit for bit.  Padding channels never reach the result.  Two calls return identical bits."""
+        nalm = (lmax + 1) * (lmax + 2) // 2
+        nx = int(nx)
+        if tuple(alm_a.shape) != (nalm, (nx + 3) // 4, 2, 4):
+            raise ValueError("alm_a must be [nalm, ceil(nx / 4), 2, 4] (got %r)" % (tuple(alm_a.shape),))
+        if alm_b is None:
+            if ny is not None and int(ny) != nx:
+                raise ValueError("ny goes with a second operand")
+            ny = nx
+        else:
+            ny = nx if ny is None else int(ny)
+            if tuple(alm_b.shape) != (nalm, (ny + 3) // 4, 2, 4):
+                raise ValueError("alm_b must be [nalm, ceil(ny / 4), 2, 4] (got %r)" % (tuple(alm_b.shape),))
+        if out is None:
+            out = self.empty((lmax + 1, nx, ny))
+        if tuple(out.shape) != (lmax + 1, nx, ny):
+            raise ValueError("Given output array is incompatible.")
+        _check(self.lib.corahip_alm_cross_spectra(self.h, self._f64(alm_a), nx, None if alm_b is None else self._f64(alm_b),
+                                                  ny, int(lmax), self._f64(out)))
+        return out
 
     # -- K4/K5 ------------------------------------------------------------------------
     # truncation exponent of the Legendre sums used by plans made without an explicit one (0 = the library's

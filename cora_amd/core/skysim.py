@@ -508,6 +508,43 @@ def mkfullsky_stream(corr, nside, rngs, alms=False, factors=None):
         yield pending[0].numpy()
 
 
+def clarray_from_maps(maps, lmax=None, niter=None, use_weights=None):
+    """Measure :math:`\\hat C_l(z, z')` from a stack of maps: the inverse of :func:`mkfullsky`.  An extension - the
+    reference has no counterpart; it is ``healpy.anafast`` of every pair of maps, in :func:`clarray`'s layout.
+
+    ``C[l, i, j] = sum_m a_i(l,m) conj(a_j(l,m)) / (2l + 1)`` over all m, from the a_lm of
+    ``hputil.map2alm_device(maps, nside, lmax, use_weights, niter)`` (defaults as there), by one FP64 MFMA Gram product
+    per l on the device (``Context.alm_cross_spectra``).  The result is symmetric in (i, j) bit for bit.
+
+    On maps made by :func:`mkfullsky` the expectation is not ``C_l`` but ``C_l (2l + 1/2) / (2l + 1)``:
+    ``mkfullsky`` (like the reference) draws a complex ``a_l0`` of which the synthesis keeps the real part, half the
+    variance.  This function does not correct for it.
+
+    Parameters
+    ----------
+    maps : np.ndarray or device tensor (numz, npix)
+    lmax : integer, optional
+        Default ``3 nside - 1``.
+
+    Returns
+    -------
+    cl : (lmax+1, numz, numz), a numpy array for host maps and a device tensor for device maps
+    """
+    import torch
+
+    from ..util import hputil
+
+    if isinstance(maps, torch.Tensor):
+        return hputil.cross_spectra_device(maps, lmax=lmax, use_weights=use_weights, niter=niter)
+    ctx = _lib.get_context()
+    maps = np.ascontiguousarray(maps, dtype=np.float64)
+    if maps.ndim != 2:
+        raise ValueError("maps must be [numz, npix]")
+    cl = hputil.cross_spectra_device(torch.from_numpy(maps).to(ctx.device), lmax=lmax, use_weights=use_weights,
+                                     niter=niter)
+    return cl.cpu().numpy()
+
+
 def mkconstrained(corr, constraints, nside):
     """Maps satisfying given constraints on some frequency slices, built from the lowest eigenmodes
     (cora/core/skysim.py:139-205).

@@ -1,0 +1,191 @@
+// spectra.hip - the multi-frequency angular power spectrum of a_lm in the device layout: per multipole l the Gram matrix
+// of the channels,
+//   out[l, i, j] = (1 / (2l+1)) sum_{m=0..l} c_m (Re a_i Re b_j + Im a_i Im b_j),   c_0 = 1, c_{m>0} = 2
+// (healpy's alm2cl; Im a_l0 enters as stored).  The transpose of K3 (draw.hip): there a_l = T_l g_l, here a_l a_l^H.
+//
+//   cross_spectra_kernel   FP64 MFMA (v_mfma_f64_16x16x4_f64), M = channels of a, N = channels of b, K-dimension = the
+//                          2 (l+1) real and imaginary values of one l (one MFMA takes (Re, Im) of two m).  A workgroup of
+//                          4 waves owns a tile of 128 x 128 outputs of one l (a wave 64 x 64); 16 x 16 blocks beyond nx
+//                          or ny are not multiplied.  Every (l, m) element of an operand is one contiguous row of 8 G
+//                          doubles [G][2][4]; the 128 channels of a tile are 256 contiguous doubles of it, staged as they
+//                          are: 16-byte loads (128 lanes cover the 2 KiB of a row), 16-byte LDS stores, CS_KM rows of m
+//                          per chunk, LDS and registers double-buffered so that the loads of chunk c+1 are in flight
+//                          while chunk c is multiplied.  LDS pitch 256 doubles, no padding: a fragment read
+//                          (ds_read_b64) of lanes 0-31 = (16 channels) x (Re, Im) covers 32 consecutive doubles = all 64
+//                          banks once, lanes 32-63 the same in the next row (tools/lds_bank_sim.py spectra).
+//                          c_m: the chunks run over m = 1 .. l first, then every accumulator is doubled (exact), then one
+//                          last MFMA adds m = 0 - no operand is scaled, so the symmetric case needs one staged operand on
+//                          diagonal tiles.  1 / (2l+1): one correctly rounded division per output in the epilogue.
+//                          Rounding: the 2 (l+1) products of an output are added in a fixed order by FMAs, + 1 division.
+//                          Symmetric case (b = a): only tiles on or below the diagonal; an off-diagonal tile writes its
+//                          mirror from the same accumulators; on a diagonal tile [i, j] and [j, i] are the commuted
+//                          products a_i a_j, a_j a_i added in the same order (the 64 x 64 block above the diagonal is
+//                          not computed but mirrored from the one below) - the result is bitwise symmetric.
+//                          No atomics, no split of K: the sum order is fixed, repeat calls return identical bits.
+//                          Work per item grows as l + 1: the grid runs over l in descending order.
+//                          Padding channels (4 G > n) are staged like the others; they only ever reach rows / columns
+//                          >= n of the MFMA result, which are not stored.  Groups beyond G are staged as zeros.
+// All element offsets are 64-bit (nalm * 8 G exceeds 2^31 at 256 channels, lmax 2048).
+#include "common.h"
+
+namespace {
+
+constexpr int CS_WAVES = 4;
+constexpr int CS_NT = 64 * CS_WAVES;    // threads per workgroup
+constexpr int CS_T = 128;               // output tile edge (channels)
+constexpr int CS_KM = 8;                // rows of m per LDS chunk (4 MFMA steps)
+constexpr int CS_P = 2 * CS_T;          // doubles of a staged row: 32 groups x [2][4]
+constexpr int CS_NV = CS_KM * CS_P / 2 / CS_NT;   // 16-byte loads per thread, operand and chunk
+
+__global__ void __launch_bounds__(CS_NT, 2)
+cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double *__restrict__ B, int ny, int Gb, int lmax,
+                     int sym, int nty, int ntiles, double *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double As[2][CS_KM * CS_P];
+    __shared__ __attribute__((aligned(16))) double Bs[2][CS_KM * CS_P];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ri = lane & 15, kq = lane >> 4;
+    const int l = lmax - (int)(blockIdx.x / (unsigned)ntiles);      // descending l
+    int t = (int)(blockIdx.x % (unsigned)ntiles), ti, tj;
+    if (sym) {
+        ti = 0;
+        while (t > ti) t -= ++ti;       // tiles (ti, tj <= ti) in row order
+        tj = t;
+    } else {
+        ti = t / nty, tj = t % nty;
+    }
+    const bool diag = sym && ti == tj;
+    const int row0 = ti * CS_T, col0 = tj * CS_T;
+    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;          // the wave's sub-tile
+    const bool active = !(diag && wr < wc);                         // above the diagonal: mirrored from (wc, wr)
+    const bool mirror = sym && (!diag || wr > wc);
+
+    d4_t acc[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) acc[u][v] = (d4_t){0.0, 0.0, 0.0, 0.0};
+    int msk = 0;                                                    // 16-blocks inside the operands: bits 0-3 rows, 4-7 columns
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        if (active && row0 + wr + 16 * u < nx) msk |= 1 << u;
+        if (col0 + wc + 16 * u < ny) msk |= 16 << u;
+    }
+    msk = __builtin_amdgcn_readfirstlane(msk);                      // (wave-uniform)
+    bool ua[4], va[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) ua[u] = (msk >> u) & 1, va[u] = (msk >> (4 + u)) & 1;
+
+    // chunk c < nch holds m = 1 + c CS_KM + r (r = row of the chunk), chunk nch holds m = 0 in row 0; other rows zero
+    const int nch = (l + CS_KM - 1) / CS_KM, ntot = nch + 1;
+    const int sr = tid >> 7, sq = 2 * (tid & 127);                  // staging: row (+ 2 u), double offset in the row
+    double2 ra[CS_NV], rb[CS_NV];
+    auto gload = [&](double2(&rv)[CS_NV], const double *__restrict__ X, int G, int x0, int c) {
+        const int d = 2 * x0 + sq;                                  // offset in the (l, m) row of 8 G doubles
+#pragma unroll
+        for (int u = 0; u < CS_NV; u++) {
+            const int r = sr + 2 * u;
+            const int m = c < nch ? 1 + c * CS_KM + r : (r == 0 ? 0 : l + 1);
+            double2 x = make_double2(0.0, 0.0);
+            if (m <= l && d < 8 * G)
+                x = *reinterpret_cast<const double2 *>(X + ((size_t)alm_idx(l, m, lmax) * (size_t)G * 8 + (size_t)d));
+            rv[u] = x;
+        }
+    };
+    auto lstore = [&](double *S, const double2(&rv)[CS_NV]) {
+#pragma unroll
+        for (int u = 0; u < CS_NV; u++) *reinterpret_cast<double2 *>(&S[(sr + 2 * u) * CS_P + sq]) = rv[u];
+    };
+    gload(ra, A, Ga, row0, 0);
+    lstore(As[0], ra);
+    if (!diag) {
+        gload(rb, B, Gb, col0, 0);
+        lstore(Bs[0], rb);
+    }
+    __syncthreads();
+    // fragment position of channel c of the tile, value (Re, Im) = kq & 1: 8 (c / 4) + 4 (kq & 1) + c % 4
+    const int fo = 8 * (ri >> 2) + 4 * (kq & 1) + (ri & 3) + (kq >> 1) * CS_P;
+    for (int c = 0; c < ntot; c++) {
+        const int buf = c & 1;
+        if (c + 1 < ntot) {
+            gload(ra, A, Ga, row0, c + 1);
+            if (!diag) gload(rb, B, Gb, col0, c + 1);
+        }
+        const double *as = As[buf], *bs = diag ? As[buf] : Bs[buf];
+        if (c == nch) {                                             // c_m = 2 of everything added so far
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int v = 0; v < 4; v++) acc[u][v] = acc[u][v] * 2.0;
+        }
+        auto step = [&](int ks) {
+            double a[4], b[4];
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                a[v] = as[2 * ks * CS_P + 2 * (wr + 16 * v) + fo];
+                b[v] = bs[2 * ks * CS_P + 2 * (wc + 16 * v) + fo];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+#pragma unroll
+                for (int v = 0; v < 4; v++)
+                    if (ua[u] && va[v]) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[v], acc[u][v], 0, 0, 0);
+        };
+        const int nks = c == nch ? 1 : CS_KM / 2;                   // m = 0: one step (row 1 of that chunk is zero)
+        for (int ks = 0; ks < nks; ks++) step(ks);                  // (not unrolled: 4 steps of fragments do not fit beside 128 accumulators)
+        if (c + 1 < ntot) {                                         // the other buffer was last read before the previous barrier
+            lstore(As[buf ^ 1], ra);
+            if (!diag) lstore(Bs[buf ^ 1], rb);
+        }
+        __syncthreads();
+    }
+    // C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
+    const double dl = (double)(2 * l + 1);
+    double *ol = out + (size_t)l * (size_t)nx * (size_t)ny;
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) {
+            if (!(ua[u] && va[v])) continue;
+            const int gc = col0 + wc + 16 * v + ri;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int gr = row0 + wr + 16 * u + kq + 4 * r;
+                if (gr < nx && gc < ny) {
+                    const double x = acc[u][v][r] / dl;
+                    ol[(size_t)gr * (size_t)ny + (size_t)gc] = x;
+                    if (mirror) ol[(size_t)gc * (size_t)ny + (size_t)gr] = x;
+                }
+            }
+        }
+}
+
+inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+}  // namespace
+
+extern "C" {
+
+int corahip_alm_cross_spectra(corahip_ctx *ctx, const double *alm_a, int nx, const double *alm_b, int ny, int lmax,
+                              double *out) {
+    ARG_CHECK(ctx && alm_a && out && nx >= 1 && ny >= 1 && lmax >= 0);
+    const bool sym = alm_b == nullptr || alm_b == alm_a;
+    ARG_CHECK(!sym || ny == nx);
+    ARG_CHECK(((uintptr_t)alm_a & 15) == 0 && ((uintptr_t)alm_b & 15) == 0 && ((uintptr_t)out & 7) == 0);
+    const int Ga = (nx + 3) / 4, Gb = (ny + 3) / 4;
+    const size_t nalm = (size_t)nalm_of(lmax), obytes = (size_t)(lmax + 1) * (size_t)nx * (size_t)ny * 8;
+    ARG_CHECK(!overlaps(out, obytes, alm_a, nalm * Ga * 64));
+    ARG_CHECK(sym || !overlaps(out, obytes, alm_b, nalm * Gb * 64));
+    const long ntx = (nx + CS_T - 1) / CS_T, nty = (ny + CS_T - 1) / CS_T;
+    const long ntiles = sym ? ntx * (ntx + 1) / 2 : ntx * nty;
+    ARG_CHECK(ntiles * (lmax + 1) <= 0x7fffffffL);
+    StageTimer t(ctx, "alm_cross_spectra");
+    hipLaunchKernelGGL(cross_spectra_kernel, dim3((unsigned)(ntiles * (lmax + 1))), dim3(CS_NT), 0, ctx->stream, alm_a, nx, Ga,
+                       sym ? alm_a : alm_b, ny, Gb, lmax, sym ? 1 : 0, (int)nty, (int)ntiles, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -3,7 +3,8 @@
 ``exponential_FoG_kernel`` (:518-589), ``lognormal_transform`` (:592-627); the last four with the kernels of
 csrc/lsschain.hip.  The angular derivatives come from the derivative
 synthesis (csrc/sht_der1.hip), the radial one from ``radial_gradient_kernel``; everything stays on the device in
-the ``_device`` forms."""
+the ``_device`` forms.  The estimators ``pk_flat`` (:293-376), ``corrfunc`` (:379-443), ``ang_correlation`` (:446-464) and
+``transfer`` (:467-488) are read off the all-pairs spectra of the slices (csrc/spectra.hip)."""
 import numpy as np
 
 from .. import _lib
@@ -299,3 +300,190 @@ def lognormal_transform(field, out=None, axis=None):
     res = lognormal_transform_device(ctx.to_device(field), axis=axis)
     out[...] = ctx.to_host(res)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# estimators (cora/signal/lssutil.py:293-488): all of them are read off the Gram matrix of the slices' a_lm per l,
+# S_l[j, k] = sum_m a_j(l,m) conj(a_k(l,m)) / (2l + 1)  (hputil.cross_spectra_device, csrc/spectra.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def invert_no_zero(x):
+    """``1 / x`` where ``x != 0``, else 0 (what the reference takes from ``caput.algorithms.invert_no_zero``)."""
+    x = np.asarray(x, dtype=np.float64)
+    out = np.zeros_like(x)
+    np.divide(1.0, x, out=out, where=x != 0)
+    return out
+
+
+def _pk_axes(chi, lmax, nkpar=None):
+    """``(kpar, kperp, scale, Wk)`` of :func:`pk_flat` for shell distances ``chi``: the shells are ``dx = ptp(chi) /
+    (N - 1)`` apart and span ``L = N dx`` (the range plus one channel width), ``kpar = 2 pi n / L`` for the
+    ``N // 2 + 1`` modes of a real transform, ``kperp = l / mean(chi)``, ``scale = L mean(chi)^2`` and the window of a
+    shell of width dx, ``Wk = sinc(kpar dx / 2 pi)`` (numpy's sinc)."""
+    chi = np.asarray(chi, dtype=np.float64)
+    N = len(chi)
+    chi_mean = chi.mean()
+    dx = np.ptp(chi) / (N - 1)
+    L = N * dx
+    n = np.arange(N // 2 + 1 if nkpar is None else nkpar)
+    kpar = 2 * np.pi * n / L
+    kperp = np.arange(lmax + 1) / chi_mean
+    return kpar, kperp, L * chi_mean**2, np.sinc(kpar * dx / (2 * np.pi))
+
+
+def _pk_contract(S):
+    """``[L, N, N]`` Gram matrices (torch tensor, any device) -> ``[N // 2 + 1, L]``:
+    ``out[n, l] = (1 / N^2) sum_jk cos(2 pi n (j - k) / N) S[l, j, k]``.
+
+    This is ``sum_m |a^n_lm|^2 / (2l + 1)`` over both signs of m for ``a^n = rfft(a^j, axis=j)[n] / N``: the analysis
+    is linear, so the transform along the slices commutes with it, and ``|sum_j w_nj a^j|^2`` summed over +-m keeps
+    only the real part ``cos`` of ``w_nj conj(w_nk)``.  The phases are reduced exactly (``n (j - k) mod N`` in
+    integers); the small contraction is a torch matmul."""
+    import torch
+
+    L, N = int(S.shape[0]), int(S.shape[1])
+    if tuple(S.shape) != (L, N, N):
+        raise ValueError("S must be [L, N, N]")
+    n = np.arange(N // 2 + 1)[:, None, None]
+    d = np.arange(N)[None, :, None] - np.arange(N)[None, None, :]
+    W = np.cos(2 * np.pi * ((n * d) % N) / N) / float(N * N)
+    W = torch.from_numpy(W.reshape(N // 2 + 1, N * N)).to(S.device)
+    return torch.matmul(W, S.reshape(L, N * N).t())
+
+
+def pk_flat_device(maps, chi, maps2=None, lmax=None, window=True):
+    """:func:`pk_flat` on device maps ``[N, npix]`` (float64); ``chi`` a host array.  Returns ``(pk, kpar, kperp)``
+    with ``pk`` a device tensor ``[N // 2 + 1, lmax + 1]`` and the axes host arrays."""
+    import torch
+
+    if maps2 is not None and tuple(maps.shape) != tuple(maps2.shape):
+        raise ValueError(
+            f"Shape of maps2 ({tuple(maps2.shape)}) is not compatible with maps ({tuple(maps.shape)})"
+        )
+    chi = np.asarray(chi, dtype=np.float64)
+    nmaps, nside = check_maps(maps, chi, xname="chi", nmin=2)
+    lmax = 3 * nside if lmax is None else int(lmax)
+    S = hputil.cross_spectra_device(maps, maps2, lmax=lmax)       # hputil._weight / _iter: sphtrans_complex's analysis
+    kpar, kperp, scale, Wk = _pk_axes(chi, lmax)
+    pk = _pk_contract(S)
+    fac = np.full(kpar.shape, scale) / (Wk**2 if window else 1.0)
+    pk = pk * torch.from_numpy(fac).to(pk.device)[:, None]
+    return pk, kpar, kperp
+
+
+def pk_flat(maps, chi, maps2=None, lmax=None, window=True):
+    """Estimate a 2D kpar, kperp power spectrum from a set of spherical maps (cora/signal/lssutil.py:293-376).
+
+    Flat-sky, thin-shell approximation: the angular transform stands for the k_perp direction and the shells are
+    taken as equally spaced.  The reference transforms along the shells first and then analyses every complex
+    Fourier map; here the slices are analysed once and the Fourier sum is taken on their Gram matrix
+    (:func:`_pk_contract`), which is the same number by linearity of the analysis
+    (``hputil.map2alm_device`` with the ``_weight`` / ``_iter`` the reference configures for ``sphtrans_complex``).
+
+    Parameters
+    ----------
+    maps : np.ndarray[N, npix]
+        The Healpix maps at each distance.
+    chi : np.ndarray[N]
+        The distance to each shell in comoving Mpc/h.
+    maps2 : np.ndarray[N, npix], optional
+        A second set of maps: the cross-power spectrum is calculated instead.
+    lmax : int, optional
+        Maximum l to use (sets the maximum k_perp); default ``3 nside``, the reference's.
+    window : bool, optional
+        Undo the effective window function caused by the finite shell width.
+
+    Returns
+    -------
+    pk : np.ndarray[N // 2 + 1, lmax + 1]
+        The 2D power spectrum as k_par, k_perp.
+    k_par, k_perp : np.ndarray
+        The wavenumber along each axis.
+    """
+    import torch
+
+    maps = np.asarray(maps)
+    if maps2 is not None:
+        maps2 = np.asarray(maps2)
+        if maps.shape != maps2.shape:
+            raise ValueError(
+                f"Shape of maps2 ({maps2.shape}) is not compatible with maps ({maps.shape})"
+            )
+    check_maps(maps, np.asarray(chi), xname="chi", nmin=2)
+    ctx = _lib.get_context()
+    dev = torch.from_numpy(np.ascontiguousarray(maps, dtype=np.float64)).to(ctx.device)
+    dev2 = None if maps2 is None else torch.from_numpy(np.ascontiguousarray(maps2, dtype=np.float64)).to(ctx.device)
+    pk, kpar, kperp = pk_flat_device(dev, chi, dev2, lmax=lmax, window=window)
+    return pk.cpu().numpy(), kpar, kperp
+
+
+def _corrfunc_bin(clxx, chi, lmax, rmax, numr):
+    """The host part of :func:`corrfunc`: spectra ``[n (n + 1) / 2, lmax + 1]`` in healpy's pair order -> ``(cf, r)``."""
+    from .corrfunc import legendre_array
+
+    chi = np.asarray(chi, dtype=np.float64)
+    i, j = hputil.spectra_pair_order(len(chi))
+    # spectrum k belongs to maps (i_k, j_k), at distances (chi[i_k], chi[j_k]): the reference's loop `for i: for j in
+    # range(i, nx): (chi[j - i], chi[j])` runs in row order, and its (j - i, j) is what turns that into the diagonal order
+    r1, r2 = chi[i][:, None], chi[j][:, None]
+    mu = np.cos(np.linspace(0, np.pi, 2048))
+    Pl = legendre_array(lmax, mu) * ((2 * np.arange(lmax + 1)[:, None] + 1) / (4 * np.pi))
+    ctheta = np.dot(clxx, Pl)
+    rc = ((r1 - r2) ** 2 + 2 * r1 * r2 * (1 - mu[None, :])) ** 0.5
+    rbins = np.linspace(0, rmax, numr + 1)
+    ind = np.digitize(rc.ravel(), rbins)
+    norm = np.bincount(ind, minlength=numr + 2)
+    csum = np.bincount(ind, weights=ctheta.ravel(), minlength=numr + 2)
+    return (csum * invert_no_zero(norm))[1:-1].copy(), 0.5 * (rbins[1:] + rbins[:-1])
+
+
+def corrfunc(maps, chi, lmax=None, rmax=1e3, numr=1024):
+    """Estimate a 1D correlation function from a set of spherical maps (cora/signal/lssutil.py:379-443).
+
+    The spectra of all pairs of slices (``hputil.anafast``, one Gram product on the device) are turned into angular
+    correlations on 2048 angles by a Legendre sum and binned in the separation of the two shell points.
+
+    Parameters
+    ----------
+    maps : np.ndarray[N, npix]
+        The Healpix maps at each distance.
+    chi : np.ndarray[N]
+        The distance to each shell in comoving Mpc/h.
+    lmax : int, optional
+        Maximum l of the intermediate spectra (default ``3 nside - 1``, ``anafast``'s).
+    rmax : float, optional
+        The maximum r to bin up to.
+    numr : int, optional
+        The number of r bins.
+
+    Returns
+    -------
+    cr : np.ndarray[numr]
+        The 1D correlation function.
+    r : np.ndarray[numr]
+        The centres of the bins.
+    """
+    maps = np.asarray(maps)
+    _, nside = check_maps(maps, np.asarray(chi), xname="chi")
+    lmax = 3 * nside - 1 if lmax is None else int(lmax)
+    clxx = hputil.anafast(maps, pol=False, lmax=lmax)
+    return _corrfunc_bin(clxx, chi, lmax, rmax, numr)
+
+
+def _pair_spectra(x, y):
+    """(cl_xx, cl_yy, cl_xy) of two maps from one 2-map call (``anafast``'s defaults)."""
+    cl = hputil.anafast(np.stack([np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)]), pol=False)
+    return cl[0], cl[1], cl[2]
+
+
+def ang_correlation(x, y):
+    """The angular correlation ``r_l = C_l^xy / sqrt(C_l^xx C_l^yy)`` between two Healpix maps
+    (cora/signal/lssutil.py:446-464)."""
+    cl_xx, cl_yy, cl_xy = _pair_spectra(x, y)
+    return cl_xy / (cl_xx * cl_yy) ** 0.5
+
+
+def transfer(x, y):
+    """The angular transfer function ``T_l = C_l^xy / C_l^yy``: the amount of the power in ``x`` that comes from the
+    reference field ``y`` (cora/signal/lssutil.py:467-488)."""
+    _, cl_yy, cl_xy = _pair_spectra(x, y)
+    return cl_xy / cl_yy

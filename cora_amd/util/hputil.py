@@ -512,3 +512,72 @@ def alm2map_der1(alm, nside):
     dth, dph = ctx.alm2map_der1(dev, nside, lmax, 1)
     out[1], out[2] = dth[0].cpu().numpy(), dph[0].cpu().numpy()
     return out
+
+
+# ------------------------------------------------------------------------------------
+# spectra of maps: healpy.anafast for every pair of a stack at once (csrc/spectra.hip)
+# ------------------------------------------------------------------------------------
+def spectra_pair_order(n):
+    """Index arrays ``(i, j)`` of the ``n (n + 1) / 2`` spectra of ``n`` maps in healpy's order: the diagonals one after
+    the other, (0,0), (1,1), ..., (0,1), (1,2), ..., (0,2), ... (``healpy.anafast`` / ``alm2cl`` of several maps)."""
+    n = int(n)
+    i = np.concatenate([np.arange(n - d) for d in range(n)]) if n > 0 else np.zeros(0, dtype=np.int64)
+    j = np.concatenate([np.arange(d, n) for d in range(n)]) if n > 0 else np.zeros(0, dtype=np.int64)
+    return i.astype(np.int64), j.astype(np.int64)
+
+
+def _npix2nside(npix):
+    nside = int(round(np.sqrt(int(npix) / 12.0)))
+    if nside < 1 or 12 * nside * nside != int(npix):
+        raise ValueError("Wrong pixel number (it is not 12*nside**2)")   # healpy.npix2nside
+    return nside
+
+
+def cross_spectra_device(maps, maps2=None, lmax=None, use_weights=None, niter=None):
+    """Device maps [n, npix] (and ``maps2`` [n2, npix]) -> device ``[lmax + 1, n, n2]``: the spectrum
+    ``C_l[i, j] = sum_m a_i(l,m) conj(b_j(l,m)) / (2l + 1)`` of every pair (``maps2=None``: of ``maps`` with itself,
+    bitwise symmetric).  :func:`map2alm_device` (``use_weights``, ``niter`` as there) followed by
+    ``Context.alm_cross_spectra``; the a_lm never leave the device.  Default ``lmax = 3 nside - 1``."""
+    ctx = _lib.get_context()
+    if maps.dim() != 2 or (maps2 is not None and (maps2.dim() != 2 or maps2.shape[1] != maps.shape[1])):
+        raise ValueError("maps must be [n, npix] (and maps2 [n2, npix] of the same nside)")
+    nside = _npix2nside(maps.shape[1])
+    lmax = 3 * nside - 1 if lmax is None else int(lmax)
+    n = int(maps.shape[0])
+    alm = map2alm_device(maps.contiguous(), nside, lmax, use_weights=use_weights, niter=niter)
+    if maps2 is None:
+        return ctx.alm_cross_spectra(alm, n, lmax)
+    n2 = int(maps2.shape[0])
+    alm2 = map2alm_device(maps2.contiguous(), nside, lmax, use_weights=use_weights, niter=niter)
+    return ctx.alm_cross_spectra(alm, n, lmax, alm_b=alm2, ny=n2)
+
+
+def anafast(map1, map2=None, lmax=None, iter=3, use_weights=False, pol=False):
+    """``healpy.anafast`` for temperature maps, with healpy's shapes and defaults (``iter=3``, ``use_weights=False``,
+    ``lmax = 3 nside - 1``): one map -> ``[lmax + 1]``; maps ``[n, npix]`` -> ``[n (n + 1) / 2, lmax + 1]`` in the
+    order of :func:`spectra_pair_order`; with ``map2`` (same shape) the cross spectra only, entry (i, j) from map i of
+    ``map1`` and map j of ``map2``.  All pairs come from one call of the Gram kernel (:func:`cross_spectra_device`).
+    ``pol=True`` on more than one map (healpy: T, Q, U) is not implemented."""
+    import torch
+
+    map1 = np.asarray(map1, dtype=np.float64)
+    single = map1.ndim == 1
+    if pol and not single:
+        raise NotImplementedError("anafast: polarised (spin-2) spectra are not implemented; pass pol=False")
+    m1 = np.ascontiguousarray(map1.reshape(1, -1) if single else map1)
+    if m1.ndim != 2:
+        raise ValueError("anafast takes one map or maps [n, npix]")
+    ctx = _lib.get_context()
+    d2 = None
+    if map2 is not None:
+        m2 = np.asarray(map2, dtype=np.float64)
+        m2 = np.ascontiguousarray(m2.reshape(1, -1) if m2.ndim == 1 else m2)
+        if m2.shape != m1.shape:
+            raise ValueError("anafast: map2 must have the shape of map1")
+        d2 = torch.from_numpy(m2).to(ctx.device)
+    cl = cross_spectra_device(torch.from_numpy(m1).to(ctx.device), d2, lmax=lmax, use_weights=use_weights, niter=iter)
+    cl = cl.cpu().numpy()
+    if single:
+        return cl[:, 0, 0].copy()
+    i, j = spectra_pair_order(m1.shape[0])
+    return np.ascontiguousarray(cl[:, i, j].T)

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 7      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal */
+#define CORAHIP_ABI_MINOR 8      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -560,6 +560,20 @@ int corahip_bias_field(corahip_ctx *ctx, const double *f, const double *c1, cons
                        long ncol, double *out);
 int corahip_lognormal(corahip_ctx *ctx, const double *f, const double *hv, const double *rs, double pre, int n, long ncol,
                       long ld_out, double *out);
+
+/* ---- spectra of a_lm (csrc/spectra.hip): the multi-frequency angular power spectrum, healpy's alm2cl for every pair ----
+ * out[l, i, j] = (1 / (2l+1)) sum_{m=0..l} c_m (Re a_i(l,m) Re b_j(l,m) + Im a_i(l,m) Im b_j(l,m)), c_0 = 1, c_{m>0} = 2
+ * (Im a_l0 enters as stored), out [lmax+1, nx, ny] row-major - clarray's layout, what mkfullsky takes.
+ *   alm_a, alm_b  device a_lm layout [nalm][nnu_pad/4][2][4] of nx resp. ny channels, 16-byte aligned, with
+ *                 nnu_pad = the channel count rounded up to a multiple of 4: what draw_alm* write and what
+ *                 Context.map2alm / hputil.map2alm_device return (a raw corahip_map2alm buffer pads to 8 and has that
+ *                 shape for n mod 8 in {0, 5, 6, 7}).  Padding channels are never read into out, whatever they hold.
+ *   alm_b         NULL or == alm_a: the symmetric case (ny == nx); out is then bitwise symmetric in (i, j).
+ * One FP64 MFMA Gram product per l; no atomics, no workspace: identical bits from call to call.  Per output the
+ * 2 (l+1) products are added by FMAs in a fixed order (the m > 0 terms, doubled exactly, then m = 0), then one division.
+ * out must overlap neither operand.  nx, ny >= 1, lmax >= 0. */
+int corahip_alm_cross_spectra(corahip_ctx *ctx, const double *alm_a, int nx, const double *alm_b, int ny, int lmax,
+                              double *out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,

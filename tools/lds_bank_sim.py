@@ -2,6 +2,8 @@
 """Lane-group simulation of ds_read_b128 / ds_write_b128 bank conflicts (MI355X_MICROARCH.md, LDS table) for the
 FFT pass patterns of sht_ringfft.hip (k5) and flatsky.hip (r4), and a hill-climb over XOR-linear slot swizzles.
     python tools/lds_bank_sim.py k5|r4 [restarts]
+    python tools/lds_bank_sim.py spectra     fragment reads (ds_read_b64) and staging stores (ds_write_b128) of
+                                             cross_spectra_kernel (spectra.hip) for a few row pitches
 Cost units: read cycles + write cycles relative to conflict-free (2.0 = perfect for a read+write pass)."""
 import numpy as np, itertools, sys
 RG = [list(range(0,4))+list(range(12,16))+list(range(20,28)), list(range(4,12))+list(range(16,20))+list(range(28,32))]
@@ -88,8 +90,39 @@ def total(patterns, f, verbose=False):
         tot += c
     return tot
 
+def dword_cost(addr, groups, nbanks, width):
+    """addr [64] byte addresses of one wave instruction moving `width` dwords per lane; lanes of a group that touch
+    one bank at different addresses serialise.  Returns LDS cycles / conflict-free cycles."""
+    cyc = 0
+    for grp in groups:
+        per_bank = {}
+        for lane in grp:
+            for w in range(width):
+                d = addr[lane] // 4 + w
+                per_bank.setdefault(d % nbanks, set()).add(d)
+        cyc += max(len(v) for v in per_bank.values())
+    return cyc / len(groups)
+
+def spectra_report():
+    """cross_spectra_kernel: a staged row holds the 128 channels of a tile as [32 groups][Re, Im][4] doubles, rows `pitch`
+    doubles apart.  Fragment read: lane (ri, kq) takes channel 16 t + ri, value kq & 1, row 2 ks + (kq >> 1)."""
+    lanes = np.arange(64)
+    ri, kq = lanes & 15, lanes >> 4
+    b64 = [list(range(0, 32)), list(range(32, 64))]
+    b128 = [list(range(8 * k, 8 * k + 8)) for k in range(8)]
+    for pitch in (256, 258, 260, 264):
+        worst_r = max(dword_cost(8 * ((2 * ks + (kq >> 1)) * pitch + 2 * 16 * t + 8 * (ri >> 2) + 4 * (kq & 1) + (ri & 3)),
+                                 b64, 64, 2) for ks in range(4) for t in range(8))
+        # staging store of wave w: thread tid = 64 w + lane, row (tid >> 7) + 2 u, 16 bytes at double 2 (tid & 127)
+        worst_w = max(dword_cost(8 * ((((64 * w + lanes) >> 7) + 2 * u) * pitch + 2 * ((64 * w + lanes) & 127)), b128, 32, 4)
+                      for w in range(4) for u in range(4))
+        print("pitch %d doubles: fragment read %.2f x, staging store %.2f x conflict-free" % (pitch, worst_r, worst_w))
+
 if __name__ == "__main__":
     which = sys.argv[1]
+    if which == "spectra":
+        spectra_report()
+        sys.exit(0)
     if which == "k5":
         pats = []
         for N in (4096, 2048, 1024, 512, 256): pats += k5_passes(N)
