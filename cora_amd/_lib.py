@@ -117,6 +117,10 @@ SIGNATURES = {
     "corahip_bias_field": (c_int, [c_void_p, PTR, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
     "corahip_lognormal": (c_int, [c_void_p, PTR, PTR, PTR, c_double, c_int, ctypes.c_long, ctypes.c_long, PTR]),
     "corahip_alm_cross_spectra": (c_int, [c_void_p, PTR, c_int, PTR, c_int, c_int, PTR]),
+    "corahip_healpix_interp_weights": (c_int, [c_void_p, c_int, PTR, PTR, ctypes.c_long, PTR, PTR]),
+    "corahip_healpix_interp_val": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, PTR, PTR, ctypes.c_long, PTR]),
+    "corahip_healpix_rotate_maps": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, ctypes.POINTER(c_double), PTR]),
+    "corahip_za_density_grid": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -1338,6 +1342,82 @@ class Context:
         _check(self.lib.corahip_za_density_sph(self.h, self._f64(psi), self._f64(delta_bias), self._f64(delta_m),
                                                self._f64(chi), int(nchi), nside, float(sigma_ang), float(sigma_chi),
                                                self._f64(out)))
+        return out
+
+    # -- HEALPix bilinear interpolation (csrc/hpinterp.hip) -----------------------------------
+    @staticmethod
+    def _nside_of(npix):
+        nside = int(round((int(npix) / 12.0) ** 0.5))
+        if nside < 1 or 12 * nside * nside != int(npix):
+            raise ValueError("Wrong pixel number (it is not 12*nside**2)")
+        return nside
+
+    def _directions(self, theta, phi):
+        torch = _torch()
+        if theta.dim() != 1 or tuple(phi.shape) != tuple(theta.shape):
+            raise ValueError("theta and phi must be 1-d device tensors of one length")
+        if theta.dtype != torch.float64 or phi.dtype != torch.float64:
+            raise ValueError("theta and phi must be float64")
+        if theta.device != self.device or phi.device != self.device:
+            raise ValueError("theta and phi must be on %s" % (self.device,))
+        return theta.contiguous(), phi.contiguous(), int(theta.shape[0])
+
+    def _map_stack(self, maps):
+        torch = _torch()
+        if maps.dim() != 2 or maps.dtype != torch.float64 or not maps.is_contiguous() or maps.shape[0] < 1:
+            raise ValueError("maps must be a contiguous float64 device tensor [n, npix], n >= 1")
+        if maps.device != self.device:
+            raise ValueError("maps must be on %s" % (self.device,))
+        return int(maps.shape[0]), self._nside_of(maps.shape[1])
+
+    def healpix_interp_weights(self, nside, theta, phi):
+        """``healpy.get_interp_weights(nside, theta, phi)`` (RING) for 1-d float64 device tensors: ``(pix [4, n] int64,
+        weights [4, n])`` on the device, the upper ring's two pixels first."""
+        torch = _torch()
+        theta, phi, n = self._directions(theta, phi)
+        pix = torch.empty((4, n), dtype=torch.int64, device=self.device)
+        w = self.empty((4, n))
+        _check(self.lib.corahip_healpix_interp_weights(self.h, int(nside), self._f64(theta), self._f64(phi), n,
+                                                       self._p(pix), self._f64(w)))
+        return pix, w
+
+    def healpix_interp_val(self, maps, theta, phi, out=None):
+        """maps [nmap, npix] sampled at the directions -> [nmap, n]; weights once per direction, all maps in one launch."""
+        nmap, nside = self._map_stack(maps)
+        theta, phi, n = self._directions(theta, phi)
+        if out is None:
+            out = self.empty((nmap, n))
+        elif (tuple(out.shape) != (nmap, n) or not out.is_contiguous() or out.dtype != maps.dtype
+              or out.device != self.device):
+            raise ValueError("out must be a contiguous float64 [%d, %d] tensor on %s" % (nmap, n, self.device))
+        _check(self.lib.corahip_healpix_interp_val(self.h, self._f64(maps), nmap, nside, self._f64(theta), self._f64(phi),
+                                                   n, self._f64(out)))
+        return out
+
+    def healpix_rotate_maps(self, maps, R, out=None):
+        """``out[m, p] = interp(maps[m], R n_p)`` for the centre ``n_p`` of every pixel (R: host 3 x 3); ``out`` must not
+        overlap ``maps`` (ValueError)."""
+        nmap, nside = self._map_stack(maps)
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.shape != (3, 3):
+            raise ValueError("R must be a 3 x 3 matrix (got shape %r)" % (R.shape,))
+        if out is None:
+            out = self.empty(tuple(maps.shape))
+        elif (tuple(out.shape) != tuple(maps.shape) or not out.is_contiguous() or out.dtype != maps.dtype
+              or out.device != self.device):
+            raise ValueError("out must be a contiguous float64 tensor of the shape of maps on %s" % (self.device,))
+        nbytes = maps.numel() * 8
+        if self._overlap(out, nbytes, maps, nbytes):
+            raise ValueError("healpix_rotate_maps: out overlaps maps")
+        _check(self.lib.corahip_healpix_rotate_maps(self.h, self._f64(maps), nmap, nside,
+                                                    R.ctypes.data_as(ctypes.POINTER(c_double)), self._f64(out)))
+        return out
+
+    def za_density_grid(self, psi, delta_bias, chi, out):
+        """Zel'dovich grid assignment into ``out`` [nchi, npix] (added to, then minus 1); shapes checked by the caller."""
+        nchi, npix = delta_bias.shape
+        _check(self.lib.corahip_za_density_grid(self.h, self._f64(psi), self._f64(delta_bias), self._f64(chi), int(nchi),
+                                                self._nside_of(npix), self._f64(out)))
         return out
 
     def sht_rings(self, nside, lmax):

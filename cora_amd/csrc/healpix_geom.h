@@ -1,0 +1,128 @@
+// healpix_geom.h - HEALPix RING geometry shared by pmesh.hip and hpinterp.hip: the pixel-centre arithmetic of
+// cora_amd/util/hputil.py (pix2ang, ang2pix), repeated operation for operation so that the host oracles and the
+// kernels pick the same pixels; no contraction into FMAs there.  Restated from the published HEALPix algorithm
+// (Gorski et al. 2005).
+#pragma once
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+
+struct Geom {
+    long nside, npix, ncap;
+};
+
+inline Geom make_geom(int nside) {
+    Geom g;
+    g.nside = nside;
+    g.npix = 12L * nside * nside;
+    g.ncap = 2L * nside * (nside - 1);
+    return g;
+}
+
+__device__ inline long isqrt_l(long v) {
+    long r = (long)sqrt((double)v);
+    while (r * r > v) --r;
+    while ((r + 1) * (r + 1) <= v) ++r;
+    return r;
+}
+
+__device__ inline long floordiv_l(long a, long b) {
+    long q = a / b;
+    return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
+}
+__device__ inline long floormod_l(long a, long b) { return a - floordiv_l(a, b) * b; }
+
+// numpy's float remainder (npy_divmod): fmod, moved to the sign of the divisor
+__device__ inline double np_mod(double a, double b) {
+    double m = fmod(a, b);
+    if (m != 0.0) {
+        if ((b < 0.0) != (m < 0.0)) m += b;
+    } else {
+        m = copysign(0.0, b);
+    }
+    return m;
+}
+
+// z and phi of a pixel centre: the arithmetic of hputil.pix2ang, in the same order
+__device__ inline void pix2zphi(const Geom &g, long ipix, double &z, double &phi) {
+#pragma clang fp contract(off)
+    const long ns = g.nside;
+    const double dn = (double)ns;
+    if (ipix < g.ncap || ipix >= g.npix - g.ncap) {
+        const bool south = ipix >= g.ncap;
+        long p = south ? g.npix - 1 - ipix : ipix;
+        long i = (1 + isqrt_l(1 + 2 * p)) >> 1;     // ring (1-based) holding 2 i (i - 1) .. 2 i (i + 1) - 1
+        long j = p - 2 * i * (i - 1);
+        double zc = 1.0 - (double)i * (double)i / (3.0 * dn * dn);
+        double pc = ((double)j + 0.5) * M_PI / (2.0 * (double)i);
+        z = south ? -zc : zc;
+        phi = south ? 2.0 * M_PI - pc : pc;
+    } else {
+        long pb = ipix - g.ncap;
+        long i = pb / (4 * ns) + ns;
+        long j = pb % (4 * ns);
+        long s = (i - ns + 1) & 1;
+        z = 4.0 / 3.0 - 2.0 * (double)i / (3.0 * dn);
+        phi = ((double)j + 0.5 * (double)s) * M_PI / (2.0 * dn);
+    }
+}
+
+// healpy.pix2vec: (sin theta cos phi, sin theta sin phi, z) with sin theta = sqrt((1 - z)(1 + z))
+__device__ inline void pix2vec(const Geom &g, long ipix, double v[3]) {
+#pragma clang fp contract(off)
+    double z, phi;
+    pix2zphi(g, ipix, z, phi);
+    double st = sqrt((1.0 - z) * (1.0 + z));
+    double s, c;
+    sincos(phi, &s, &c);
+    v[0] = st * c;
+    v[1] = st * s;
+    v[2] = z;
+}
+
+// RING ang2pix: the arithmetic of hputil.ang2pix, in the same order
+__device__ inline long ang2pix(const Geom &g, double theta, double phi) {
+#pragma clang fp contract(off)
+    const long ns = g.nside;
+    const double dn = (double)ns;
+    double z = cos(theta);
+    double za = fabs(z);
+    double tt = np_mod(phi, 2.0 * M_PI) / (M_PI / 2.0);
+    if (za <= 2.0 / 3.0) {
+        double t1 = dn * (0.5 + tt);
+        double t2 = dn * z * 0.75;
+        long jp = (long)floor(t1 - t2);
+        long jm = (long)floor(t1 + t2);
+        long ir = ns + 1 + jp - jm;
+        long kshift = 1 - (ir & 1);
+        long ip = floormod_l(floordiv_l(jp + jm - ns + kshift + 1, 2), 4 * ns);
+        return g.ncap + (ir - 1) * 4 * ns + ip;
+    }
+    double tp = tt - floor(tt);
+    double tmp = dn * sqrt(3.0 * (1.0 - za));
+    long jp = (long)floor(tp * tmp);
+    long jm = (long)floor((1.0 - tp) * tmp);
+    long irc = jp + jm + 1;
+    long ipc = floormod_l((long)floor(tt * (double)irc), 4 * irc);
+    return z > 0 ? 2 * irc * (irc - 1) + ipc : g.npix - 2 * irc * (irc + 1) + ipc;
+}
+
+// pmesh.calculate_positions for one particle: theta outside [0, pi] is reflected and phi gains pi, then phi mod 2 pi
+__device__ inline void displaced_position(double thp, double php, double dth, double dph, double &th, double &ph) {
+#pragma clang fp contract(off)
+    th = thp + dth;
+    ph = php + dph;
+    if (th > M_PI || th < 0.0) {
+        th = M_PI - np_mod(th, M_PI);
+        ph = ph + M_PI;
+    }
+    ph = np_mod(ph, 2.0 * M_PI);
+}
+
+__global__ __launch_bounds__(256) void minus_one_kernel(double *__restrict__ out, long n) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] -= 1.0;
+}
+
+}  // namespace

@@ -4,16 +4,15 @@
 // Geometry: RING ang2pix / pix2vec / ang2vec and get_all_neighbours restated from the published HEALPix
 // algorithm (Gorski et al. 2005; ring -> (x, y, face), step within or across base faces, back to ring).  The
 // z / phi of a pixel centre and ang2pix repeat, operation for operation, cora_amd/util/hputil.py (pix2ang,
-// ang2pix) so that the host oracle and the kernel pick the same pixels; no contraction into FMAs there.
+// ang2pix) so that the host oracle and the kernel pick the same pixels; no contraction into FMAs there
+// (healpix_geom.h, shared with hpinterp.hip).
 //
 // Deposit: one workgroup owns a 16 x 16 block of one base face (RING pixels of those (x, y)) and 8 slices.  Its
 // particles add into an LDS f64 tile of that block with a 4-pixel halo and 3 radial bins of halo on each side
 // (ds_add_f64); a target outside the tile (another face, farther away) goes straight to a global f64 atomic add.  The
 // tile is flushed once with global atomic adds of its non-zero cells.  Sums therefore depend on arrival order: repeated
 // calls agree to rounding, not bit for bit.
-#include "common.h"
-
-#include <cmath>
+#include "healpix_geom.h"
 
 namespace {
 
@@ -43,36 +42,8 @@ __constant__ int8_t c_nb_swap[9][3] = {{0, 0, 3}, {0, 0, 6}, {0, 0, 0}, {0, 0, 5
 __constant__ int8_t c_nb_dx[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
 __constant__ int8_t c_nb_dy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
 
-struct Geom {
-    long nside, npix, ncap;
-};
-
 __device__ inline int face_jrll(int f) { return (f >> 2) + 2; }
 __device__ inline int face_jpll(int f) { return 2 * (f & 3) + ((f >> 2) == 1 ? 0 : 1); }
-
-__device__ inline long isqrt_l(long v) {
-    long r = (long)sqrt((double)v);
-    while (r * r > v) --r;
-    while ((r + 1) * (r + 1) <= v) ++r;
-    return r;
-}
-
-__device__ inline long floordiv_l(long a, long b) {
-    long q = a / b;
-    return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
-}
-__device__ inline long floormod_l(long a, long b) { return a - floordiv_l(a, b) * b; }
-
-// numpy's float remainder (npy_divmod): fmod, moved to the sign of the divisor
-__device__ inline double np_mod(double a, double b) {
-    double m = fmod(a, b);
-    if (m != 0.0) {
-        if ((b < 0.0) != (m < 0.0)) m += b;
-    } else {
-        m = copysign(0.0, b);
-    }
-    return m;
-}
 
 __device__ void ring2xyf(const Geom &g, long pix, int &ix, int &iy, int &face) {
     const long ns = g.nside, nl2 = 2 * ns;
@@ -172,70 +143,6 @@ __device__ void neighbours_xyf(const Geom &g, int ix, int iy, int face, int nx[8
     }
 }
 
-// z and phi of a pixel centre: the arithmetic of hputil.pix2ang, in the same order
-__device__ void pix2zphi(const Geom &g, long ipix, double &z, double &phi) {
-#pragma clang fp contract(off)
-    const long ns = g.nside;
-    const double dn = (double)ns;
-    if (ipix < g.ncap || ipix >= g.npix - g.ncap) {
-        const bool south = ipix >= g.ncap;
-        long p = south ? g.npix - 1 - ipix : ipix;
-        long i = (1 + isqrt_l(1 + 2 * p)) >> 1;     // ring (1-based) holding 2 i (i - 1) .. 2 i (i + 1) - 1
-        long j = p - 2 * i * (i - 1);
-        double zc = 1.0 - (double)i * (double)i / (3.0 * dn * dn);
-        double pc = ((double)j + 0.5) * M_PI / (2.0 * (double)i);
-        z = south ? -zc : zc;
-        phi = south ? 2.0 * M_PI - pc : pc;
-    } else {
-        long pb = ipix - g.ncap;
-        long i = pb / (4 * ns) + ns;
-        long j = pb % (4 * ns);
-        long s = (i - ns + 1) & 1;
-        z = 4.0 / 3.0 - 2.0 * (double)i / (3.0 * dn);
-        phi = ((double)j + 0.5 * (double)s) * M_PI / (2.0 * dn);
-    }
-}
-
-// healpy.pix2vec: (sin theta cos phi, sin theta sin phi, z) with sin theta = sqrt((1 - z)(1 + z))
-__device__ void pix2vec(const Geom &g, long ipix, double v[3]) {
-#pragma clang fp contract(off)
-    double z, phi;
-    pix2zphi(g, ipix, z, phi);
-    double st = sqrt((1.0 - z) * (1.0 + z));
-    double s, c;
-    sincos(phi, &s, &c);
-    v[0] = st * c;
-    v[1] = st * s;
-    v[2] = z;
-}
-
-// RING ang2pix: the arithmetic of hputil.ang2pix, in the same order
-__device__ long ang2pix(const Geom &g, double theta, double phi) {
-#pragma clang fp contract(off)
-    const long ns = g.nside;
-    const double dn = (double)ns;
-    double z = cos(theta);
-    double za = fabs(z);
-    double tt = np_mod(phi, 2.0 * M_PI) / (M_PI / 2.0);
-    if (za <= 2.0 / 3.0) {
-        double t1 = dn * (0.5 + tt);
-        double t2 = dn * z * 0.75;
-        long jp = (long)floor(t1 - t2);
-        long jm = (long)floor(t1 + t2);
-        long ir = ns + 1 + jp - jm;
-        long kshift = 1 - (ir & 1);
-        long ip = floormod_l(floordiv_l(jp + jm - ns + kshift + 1, 2), 4 * ns);
-        return g.ncap + (ir - 1) * 4 * ns + ip;
-    }
-    double tp = tt - floor(tt);
-    double tmp = dn * sqrt(3.0 * (1.0 - za));
-    long jp = (long)floor(tp * tmp);
-    long jm = (long)floor((1.0 - tp) * tmp);
-    long irc = jp + jm + 1;
-    long ipc = floormod_l((long)floor(tt * (double)irc), 4 * irc);
-    return z > 0 ? 2 * irc * (irc - 1) + ipc : g.npix - 2 * irc * (irc + 1) + ipc;
-}
-
 __global__ __launch_bounds__(256) void neighbours_kernel(Geom g, int32_t *__restrict__ out) {
     for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < g.npix; p += (long)gridDim.x * blockDim.x) {
         int ix, iy, f;
@@ -284,12 +191,8 @@ __global__ __launch_bounds__(256) void za_sph_kernel(Geom g, const double *__res
             sc = pow(sc, -1.0 / 3.0);
 
             // pmesh.calculate_positions
-            double th = thp + dth, ph = php + dph;
-            if (th > M_PI || th < 0.0) {
-                th = M_PI - np_mod(th, M_PI);
-                ph = ph + M_PI;
-            }
-            ph = np_mod(ph, 2.0 * M_PI);
+            double th, ph;
+            displaced_position(thp, php, dth, dph, th, ph);
             const double nchi_pos = chi[ii] + dr;
 
             // angular weights over the pixel of the new position and its 8 neighbours (pmesh._pixel_weights).
@@ -371,18 +274,6 @@ __global__ __launch_bounds__(256) void za_sph_kernel(Geom g, const double *__res
         if (b < 0 || b >= nchi || gx < 0 || gy < 0 || gx >= g.nside || gy >= g.nside) continue;
         atomicAdd(&out[(long)b * npix + xyf2ring(g, gx, gy, face)], v);
     }
-}
-
-__global__ __launch_bounds__(256) void minus_one_kernel(double *__restrict__ out, long n) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] -= 1.0;
-}
-
-Geom make_geom(int nside) {
-    Geom g;
-    g.nside = nside;
-    g.npix = 12L * nside * nside;
-    g.ncap = 2L * nside * (nside - 1);
-    return g;
 }
 
 }  // namespace

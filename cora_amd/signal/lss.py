@@ -7,6 +7,10 @@ iterated analysis, derivative synthesis and radial gradient, csrc/sht_der1.hip),
 numerical content of ``ZeldovichDynamics.process(sph=True)`` (lss.py:777-856) from ``phi, delta`` to the final
 density without leaving the device.
 
+``za_density_grid`` (lss.py:996-1096) is the grid form behind ``ZeldovichDynamics(sph=False)``: the same particles,
+their mass shared among the 4 bilinear-interpolation pixels of the new direction x 2 radial bins (csrc/hpinterp.hip);
+``sph=False`` of ``zeldovich_density`` / ``tracer_map_device`` routes there.
+
 The steps around it (csrc/lsschain.hip): ``biased_field`` (GenerateBiasedFieldBase.process, lss.py:556-603),
 ``linear_dynamics`` (LinearDynamics.process, :862-918), ``fingers_of_god`` (FingersOfGod.process, :1162-1220),
 ``biased_lss_to_map`` (BiasedLSSToMap.process, :944-993) and their composition ``tracer_map_device``: ``phi, delta``
@@ -15,7 +19,8 @@ in, map out, on the device.  The bias, growth and temperature models of the refe
 
 The reference's scatter (pmesh_util.c:37, called from pmesh.pyx:_bin_delta) indexes ``out`` with a row stride of 9
 (the number of pixel weights) instead of the map's npix, so mass meant for radial bin ``ri`` lands ri (npix - 9)
-elements early.  This port implements the intended ``out[ri, pix]`` (tests/test_lss_host.py).
+elements early.  This port implements the intended ``out[ri, pix]`` (tests/test_lss_host.py).  The same
+holds for the grid form, where that stride is 4 (the number of interpolation pixels).
 """
 import numpy as np
 
@@ -26,7 +31,7 @@ from . import lssutil
 _assert_shape = lssutil.assert_shape
 
 
-def _check(psi, delta_bias, delta_m, chi, out):
+def _check(psi, delta_bias, delta_m, chi, out, min_slices=3, name="za_density_sph"):
     if len(delta_bias.shape) != 2:
         raise ValueError("Array delta_bias must be [nchi, npix]")
     nchi, npix = delta_bias.shape
@@ -37,8 +42,8 @@ def _check(psi, delta_bias, delta_m, chi, out):
     _assert_shape(delta_m, (nchi, npix), "delta_m")
     _assert_shape(chi, (nchi,), "chi")
     _assert_shape(out, (nchi, npix), "out")
-    if nchi < 3:
-        raise ValueError("za_density_sph needs at least 3 radial slices (got %d)" % nchi)
+    if nchi < min_slices:
+        raise ValueError("%s needs at least %d radial slices (got %d)" % (name, min_slices, nchi))
     return nchi, nside
 
 
@@ -102,6 +107,74 @@ def za_density_sph(psi, delta_bias, delta_m, chi, out, sigma_chi=None):
 
 
 # ------------------------------------------------------------------------------------
+# the grid form (cora/signal/lss.py:996-1096)
+# ------------------------------------------------------------------------------------
+def _check_grid(psi, delta_bias, delta_m, chi, out):
+    """``_check`` with the grid form's slice count, plus what its radial search needs: chi strictly ascending."""
+    nchi, nside = _check(psi, delta_bias, delta_m, chi, out, min_slices=2, name="za_density_grid")
+    chi_h = np.asarray(_host(chi), dtype=np.float64)
+    if not (np.diff(chi_h) > 0).all():
+        raise ValueError("za_density_grid needs chi ascending")
+    return nchi, nside
+
+
+def _check_device_f64(ctx, **tensors):
+    """The kernels read raw float64 device memory: anything else is refused here, not by an assert further down."""
+    import torch
+
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != ctx.device or not t.is_contiguous():
+            raise ValueError("Array %s must be a contiguous float64 tensor on %s" % (name, ctx.device))
+
+
+def za_density_grid_device(psi, delta_bias, delta_m, chi, out):
+    """``za_density_grid`` on device tensors (float64, contiguous, on the context's GPU).  ``out`` [nchi, npix] is
+    accumulated into, then 1 is subtracted from it; it is returned.  The inputs are left unchanged; ``delta_m`` is
+    shape-checked and, as in the reference, not read.  Sums use float atomics: two calls agree to rounding, not bit for
+    bit."""
+    _check_grid(psi, delta_bias, delta_m, chi, out)
+    ctx = _lib.get_context()
+    _check_device_f64(ctx, psi=psi, delta_bias=delta_bias, chi=chi, out=out)
+    return ctx.za_density_grid(psi, delta_bias, chi, out)
+
+
+def za_density_grid(psi, delta_bias, delta_m, chi, out):
+    """Calculate the density field under the Zel'dovich approximation, grid form (cora/signal/lss.py:996-1096).
+
+    Every voxel (slice ``ii``, RING pixel ``p``) is a particle of mass ``1 + delta_bias[ii, p]`` moved exactly as in
+    :func:`za_density_sph`.  Its mass is shared among the 4 pixels of the HEALPix bilinear interpolation at its new
+    direction (``cora_amd.util.hputil.get_interp_weights``) and the 2 radial bins around its new distance: ``chi`` is
+    extended by one extrapolated cell at each end, ``np.digitize`` picks the cell ``[chi0, chi1)``, the weights are
+    ``|chi1 - x| / dchi`` and ``|x - chi0| / dchi``; a bin outside ``[0, nchi)`` drops its share (it is not
+    redistributed, as in the reference).  Bin ``ri`` of pixel ``pix`` receives into ``out[ri, pix]``: the intended
+    placement, not the row stride of 4 the reference's C scatter uses.
+
+    Parameters
+    ----------
+    psi : np.ndarray[3, nchi, npix]
+        The vector displacement field.
+    delta_bias : np.ndarray[nchi, npix]
+        The biased density field.
+    delta_m : np.ndarray[nchi, npix]
+        The underlying matter density field.  Shape-checked; not used (nor is it by the reference).
+    chi : np.ndarray[nchi]
+        The comoving distance of each slice (ascending; nchi >= 2).
+    out : np.ndarray[nchi, npix]
+        Accumulated into in place (not zeroed), then 1 is subtracted.
+
+    Returns
+    -------
+    out
+    """
+    _check_grid(psi, delta_bias, delta_m, chi, out)
+    ctx = _lib.get_context()
+    dev = [ctx.to_device(a) for a in (psi, delta_bias, chi, out)]
+    res = ctx.za_density_grid(*dev)
+    out[...] = res.cpu().numpy()
+    return out
+
+
+# ------------------------------------------------------------------------------------
 # the displacement field and the whole Zel'dovich step (cora/signal/lss.py:777-856)
 # ------------------------------------------------------------------------------------
 def _host(a):
@@ -154,13 +227,15 @@ def _check_density(phi, delta, delta_bias, chi, D, f):
     return nchi, nside
 
 
-def zeldovich_density_device(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lmax=None, niter=3):
+def zeldovich_density_device(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lmax=None, niter=3, sph=True):
     """The numerical content of ``ZeldovichDynamics.process(sph=True)`` (cora/signal/lss.py:777-856) on device tensors:
     ``psi = zeldovich_displacement_device(phi, chi, D, f)``, ``delta_m = delta * D[:, None]``, ``out = 0``, then
     ``za_density_sph_device(psi, delta_bias, delta_m, chi, out, sigma_chi)``.  ``phi``, ``delta`` (the matter
     density at the initial time) and ``delta_bias`` (the biased Lagrangian field) are [nchi, npix], nchi >= 3, ``chi``
     ascending.  Returns the final density contrast [nchi, npix].  Device memory beyond the three inputs: ``psi``,
-    ``delta_m`` and the result (5 nchi npix doubles) plus ``lssutil.gradient_bytes(nside, lmax)``."""
+    ``delta_m`` and the result (5 nchi npix doubles) plus ``lssutil.gradient_bytes(nside, lmax)``.  ``sph=False`` is
+    the reference's ``sph=False``: the last step is ``za_density_grid_device(psi, delta_bias, delta_m, chi, out)``
+    (``sigma_chi`` is not used there)."""
     import torch
 
     chi_h, D_h = _host(chi), _host(D)
@@ -172,10 +247,12 @@ def zeldovich_density_device(phi, delta, delta_bias, chi, D, f=None, sigma_chi=N
     delta_m = delta * D_dev[:, None]
     out = torch.zeros_like(delta_bias)
     chi_dev = chi if isinstance(chi, torch.Tensor) else ctx.to_device(np.asarray(chi_h, dtype=np.float64))
+    if not sph:
+        return za_density_grid_device(psi, delta_bias, delta_m, chi_dev, out)
     return za_density_sph_device(psi, delta_bias, delta_m, chi_dev, out, sigma_chi)
 
 
-def zeldovich_density(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lmax=None, niter=3):
+def zeldovich_density(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lmax=None, niter=3, sph=True):
     """:func:`zeldovich_density_device` for numpy arrays; returns the final density contrast [nchi, npix]."""
     phi, delta, delta_bias = np.asarray(phi), np.asarray(delta), np.asarray(delta_bias)
     chi, D = np.asarray(chi), np.asarray(D)
@@ -183,7 +260,7 @@ def zeldovich_density(phi, delta, delta_bias, chi, D, f=None, sigma_chi=None, lm
     _check_density(phi, delta, delta_bias, chi, D, f)
     ctx = _lib.get_context()
     res = zeldovich_density_device(ctx.to_device(phi), ctx.to_device(delta), ctx.to_device(delta_bias), chi, D, f,
-                                   sigma_chi=sigma_chi, lmax=lmax, niter=niter)
+                                   sigma_chi=sigma_chi, lmax=lmax, niter=niter, sph=sph)
     return ctx.to_host(res)
 
 
@@ -325,19 +402,22 @@ def biased_lss_to_map(delta, lognormal=False, map_prefactor=1.0, T_b=None, polar
 def tracer_map_device(phi, delta, chi, D, f, b1, b2=None, sigmaP=None, dynamics="zeldovich", lognormal=False,
                       lightcone=True, redshift_space=True, fog_D=None, alpha_FoG=1.0, band_cut=None,
                       map_lognormal=False, map_prefactor=1.0, T_b=None, polarisation=True, sigma_chi=None, lmax=None,
-                      niter=3):
+                      niter=3, sph=True):
     """``phi, delta`` [nchi, npix] (device, from ``mkfullsky_device``) -> tracer map [nchi, 4 or 1, npix] on the device:
     :func:`biased_field_device` -> :func:`zeldovich_density_device` (``dynamics="zeldovich"``) or
     :func:`linear_dynamics_device` (``"linear"``) -> :func:`fingers_of_god_device` (skipped when ``sigmaP`` is None)
     -> :func:`biased_lss_to_map_device`.  A composition only: every number comes from those four calls, with the
     arguments passed through (``redshift_space=False`` passes ``f=None`` to the dynamics; ``fog_D`` is the growth factor
-    the FoG kernel divides out and re-applies, None = 1)."""
+    the FoG kernel divides out and re-applies, None = 1; ``sph`` goes to :func:`zeldovich_density_device`)."""
     if dynamics not in ("zeldovich", "linear"):
         raise ValueError("dynamics must be 'zeldovich' or 'linear' (got %r)" % (dynamics,))
     fd = f if redshift_space else None
     bias = biased_field_device(delta, D, b1, b2, lognormal=lognormal, lightcone=lightcone)
     if dynamics == "zeldovich":
-        final = zeldovich_density_device(phi, delta, bias, chi, D, fd, sigma_chi=sigma_chi, lmax=lmax, niter=niter)
+        # the default call is the one made before the keyword existed, keyword for keyword
+        # (tests/test_gpu_lsschain.py::test_tracer_map_is_the_composition compares them): only the grid form names sph
+        grid = {} if sph else {"sph": False}
+        final = zeldovich_density_device(phi, delta, bias, chi, D, fd, sigma_chi=sigma_chi, lmax=lmax, niter=niter, **grid)
     else:
         final = linear_dynamics_device(phi, delta, bias, chi, D, fd)
     del bias

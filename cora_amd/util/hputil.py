@@ -581,3 +581,160 @@ def anafast(map1, map2=None, lmax=None, iter=3, use_weights=False, pol=False):
         return cl[:, 0, 0].copy()
     i, j = spectra_pair_order(m1.shape[0])
     return np.ascontiguousarray(cl[:, i, j].T)
+
+
+# ------------------------------------------------------------------------------------
+# bilinear interpolation and coordinate rotation: healpy.get_interp_weights / get_interp_val and
+# cora/util/hputil.py:534-604 (csrc/hpinterp.hip)
+# ------------------------------------------------------------------------------------
+# The interpolation scheme is the published HEALPix one (get_interpol, Gorski et al. 2005), restated; healpy is not a
+# dependency of this package and its own numbers are neither used nor tested against.
+def _query(nside, theta, phi, nest, lonlat):
+    if nest:
+        raise NotImplementedError("NEST ordering is not implemented; pass nest=False")
+    if phi is None:
+        ipix = np.asarray(theta, dtype=np.int64)
+        if ipix.size and (ipix.min() < 0 or ipix.max() >= nside2npix(nside)):
+            raise ValueError("pixel index out of range for nside %d" % int(nside))
+        theta, phi = pix2ang(nside, ipix)
+    else:
+        theta, phi = np.broadcast_arrays(np.asarray(theta, dtype=np.float64), np.asarray(phi, dtype=np.float64))
+        if lonlat:
+            theta, phi = np.pi / 2.0 - np.radians(phi), np.radians(theta)
+    if theta.size and not ((theta >= 0).all() and (theta <= np.pi).all()):
+        raise ValueError("THETA is out of range [0,pi]")
+    ctx = _lib.get_context()
+    return ctx, theta.shape, ctx.to_device(theta.reshape(-1)), ctx.to_device(phi.reshape(-1))
+
+
+def get_interp_weights(nside, theta, phi=None, nest=False, lonlat=False):
+    """``healpy.get_interp_weights`` in RING order: the 4 pixels and bilinear weights around each direction, host
+    arrays ``(pix [4, ...] int64, weights [4, ...] float64)`` of the arguments' (broadcast) shape, the two pixels of
+    the upper ring first.  ``theta``, ``phi``: scalars or arrays (colatitude and longitude in radians; with
+    ``lonlat=True`` longitude and latitude in degrees); ``phi=None``: ``theta`` holds pixel indices, whose centres are
+    taken.  North of the first ring (south of the last) the pole is a virtual sample, the mean of the ring's 4 pixels:
+    the ring's two pixels and their opposites are returned.  ``nest=True`` raises NotImplementedError.
+
+    The scheme is HEALPix's published one, computed on the device (corahip_healpix_interp_weights); it is pinned by its
+    properties and an independent numpy oracle (tests/_interp_oracle.py), not by healpy's output.  Ring colatitudes are
+    those of :func:`pix2ang`, so a pixel centre taken from there gets weight 1 on its own pixel in theta."""
+    ctx, shape, th, ph = _query(int(nside), theta, phi, nest, lonlat)
+    pix, w = ctx.healpix_interp_weights(int(nside), th, ph)
+    return pix.cpu().numpy().reshape((4,) + shape), w.cpu().numpy().reshape((4,) + shape)
+
+
+def get_interp_val_device(maps, theta, phi):
+    """Device maps [n, npix] sampled at the directions ``theta``, ``phi`` (1-d float64 device tensors, theta in
+    [0, pi], not checked) -> device [n, len(theta)].  The weights are formed once per direction and applied to every
+    map in one launch; no atomics, identical bits from call to call."""
+    return _lib.get_context().healpix_interp_val(maps, theta, phi)
+
+
+def get_interp_val(m, theta, phi, nest=False, lonlat=False):
+    """``healpy.get_interp_val`` in RING order: the bilinear interpolation of the map ``m`` [npix], or of each map of
+    ``m`` [n, npix], at the directions (scalars or arrays, as :func:`get_interp_weights`).  Host result of the
+    directions' shape, with a leading axis ``n`` for several maps."""
+    m = np.asarray(m, dtype=np.float64)
+    if m.ndim not in (1, 2):
+        raise ValueError("get_interp_val takes one map [npix] or maps [n, npix]")
+    nside = _npix2nside(m.shape[-1])
+    ctx, shape, th, ph = _query(nside, theta, phi, nest, lonlat)
+    val = ctx.healpix_interp_val(ctx.to_device(m.reshape(-1, m.shape[-1])), th, ph).cpu().numpy()
+    if m.ndim == 1:
+        val = val[0].reshape(shape)
+        return val if val.ndim else float(val)
+    return val.reshape((m.shape[0],) + shape)
+
+
+def rotate_map_device(maps, R, out=None):
+    """Device maps [n, npix] rotated by the 3 x 3 host matrix ``R``: ``out[i, p] = interp(maps[i], R n_p)`` with
+    ``n_p`` the centre of pixel p, i.e. output pixel p samples the input at ``R n_p``.  One fused kernel
+    (corahip_healpix_rotate_maps): no angle arrays in memory, the weights of a pixel serve all n maps.  ``out`` must not
+    overlap ``maps`` (ValueError).  No atomics: identical bits from call to call."""
+    return _lib.get_context().healpix_rotate_maps(maps, R, out=out)
+
+
+# J2000 constants of the coordinate systems (IAU 1958 galactic system transformed to J2000, as in the Hipparcos
+# catalogue vol. 1 sec. 1.5.3; mean obliquity of the IAU 1976 system): degrees
+GAL_POLE_RA, GAL_POLE_DEC, GAL_LON_NCP = 192.85948, 27.12825, 122.93192
+ECL_OBLIQUITY = 23.4392911
+
+
+def _rot(axis, angle_deg):
+    """Active rotation by ``angle_deg`` about coordinate axis 0, 1 or 2."""
+    a = np.radians(angle_deg)
+    c, s = np.cos(a), np.sin(a)
+    i, j = [(1, 2), (2, 0), (0, 1)][axis]
+    r = np.eye(3)
+    r[i, i], r[i, j], r[j, i], r[j, j] = c, -s, s, c
+    return r
+
+
+def _mm(a, b):
+    """3 x 3 product with a fixed order of the sums, so that ``_mm(a, b.T) == _mm(b, a.T).T`` bit for bit."""
+    return np.array([[(a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j] for j in range(3)] for i in range(3)])
+
+
+def _from_celestial(y):
+    if y == "G":
+        # turn about z to the pole's right ascension, tip the pole onto z, then turn the celestial pole (now at
+        # longitude 180 deg) to its galactic longitude
+        return _mm(_rot(2, GAL_LON_NCP - 180.0), _mm(_rot(1, GAL_POLE_DEC - 90.0), _rot(2, -GAL_POLE_RA)))
+    if y == "E":
+        return _rot(0, -ECL_OBLIQUITY)
+    return np.eye(3)
+
+
+def coord_matrix(x, y):
+    """The 3 x 3 matrix taking a unit vector given in system ``x`` to system ``y``; 'C' celestial (equatorial J2000),
+    'G' galactic, 'E' ecliptic.  Composed from elementary rotations by the defining angles, so it is orthonormal to
+    rounding, ``coord_matrix(x, y) == coord_matrix(y, x).T`` exactly and ``coord_matrix(x, x)`` is the identity.
+
+    Galactic (J2000): north pole at RA 192.85948 deg, Dec 27.12825 deg, galactic longitude of the celestial pole
+    122.93192 deg; ecliptic: J2000 obliquity 23.4392911 deg.  These are the project's own constants; healpy composes
+    its matrices from slightly different ones, and agreement with healpy below about 1e-5 rad is neither claimed nor
+    tested."""
+    if x not in ["C", "G", "E"] or y not in ["C", "G", "E"]:
+        raise Exception("Co-ordinate system invalid.")
+    if x == y:
+        return np.eye(3)
+    return _mm(_from_celestial(y), _from_celestial(x).T)
+
+
+ROTATE_MAX_BYTES = 1 << 31     # device bytes (input + output chunk) coord_x2y uses at a time
+
+
+def coord_x2y(map, x, y, max_bytes=None):
+    """Rotate maps [..., npix] from co-ordinate system ``x`` into system ``y`` ('C', 'G' or 'E';
+    cora/util/hputil.py:534-566): output pixel p is the bilinear interpolation of the input at
+    ``coord_matrix(y, x) n_p``, the position in ``x`` of the point whose ``y`` co-ordinates are the pixel centre.
+    Polarisation planes are rotated as scalars, as the reference does (no rotation of the polarisation angle).
+
+    Returns a NEW array of the input's shape; the reference overwrites its argument and returns it.  The maps go to
+    the device in chunks of channels whose input and output together stay within ``max_bytes`` (default
+    ``ROTATE_MAX_BYTES``, 2 GiB; never less than one map); chunking does not change a bit of the result.  The rotation
+    matrix is :func:`coord_matrix`: see there for the constants."""
+    if x not in ["C", "G", "E"] or y not in ["C", "G", "E"]:
+        raise Exception("Co-ordinate system invalid.")
+    map = np.asarray(map, dtype=np.float64)
+    npix = map.shape[-1]
+    _npix2nside(npix)
+    R = coord_matrix(y, x)
+    flat = np.ascontiguousarray(map.reshape((-1, npix)))
+    out = np.empty_like(flat)
+    budget = ROTATE_MAX_BYTES if max_bytes is None else int(max_bytes)
+    chunk = max(1, budget // (2 * npix * 8))
+    ctx = _lib.get_context()
+    for c0 in range(0, flat.shape[0], chunk):
+        out[c0:c0 + chunk] = ctx.to_host(rotate_map_device(ctx.to_device(flat[c0:c0 + chunk]), R))
+    return out.reshape(map.shape)
+
+
+def coord_g2c(map_):
+    """Rotate maps [..., npix] from galactic into celestial co-ordinates (cora/util/hputil.py:569-585)."""
+    return coord_x2y(map_, "G", "C")
+
+
+def coord_c2g(map_):
+    """Rotate maps [..., npix] from celestial into galactic co-ordinates (cora/util/hputil.py:588-604)."""
+    return coord_x2y(map_, "C", "G")

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 8      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra */
+#define CORAHIP_ABI_MINOR 9      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -574,6 +574,34 @@ int corahip_lognormal(corahip_ctx *ctx, const double *f, const double *hv, const
  * out must overlap neither operand.  nx, ny >= 1, lmax >= 0. */
 int corahip_alm_cross_spectra(corahip_ctx *ctx, const double *alm_a, int nx, const double *alm_b, int ny, int lmax,
                               double *out);
+
+/* ---- HEALPix RING bilinear interpolation (csrc/hpinterp.hip): healpy.get_interp_weights / get_interp_val ------------
+ * The published HEALPix scheme (get_interpol), restated: the two iso-latitude rings around theta (ring colatitudes are
+ * acos of the ring z of hputil.pix2ang), on each ring the two nearest pixel centres with weights linear in phi
+ * (wrapping round), between the rings weights linear in theta; north of the first / south of the last ring the pole is
+ * a virtual sample, the mean of the 4 pixels of that ring.  theta in [0, pi]; phi is taken mod 2 pi.  Every returned or
+ * touched pixel index lies in [0, npix) whatever theta and phi hold.  1 <= nside <= 8192, any nside.
+ * healpix_interp_weights: theta, phi [n] -> pix_out int64 [4][n], w_out [4][n]: the upper ring's two pixels, then the lower
+ *            ring's; past the first ring the upper pair is the opposite pair (p + 2) & 3 of ring 1 with weight
+ *            (1 - wt) / 4 each (ring 1's own pair: w wt + (1 - wt) / 4), mirrored past the last ring.
+ * healpix_interp_val: maps [nmap][npix] -> out [nmap][n], out[m][q] = sum_k w_k maps[m][pix_k]; weights computed once per
+ *            query.  No atomics: identical bits from call to call.
+ * healpix_rotate_maps: out[m][p] = interp(maps[m], R n_p) for the centre n_p of every output pixel; R a HOST double[9],
+ *            row major.  Fused: no theta / phi arrays.  out must not overlap maps (CORAHIP_EINVAL).
+ * za_density_grid: cora/signal/lss.py:996-1096: every voxel (ii, p) of delta_bias [nchi, npix] is a particle of mass
+ *            1 + delta_bias moved by psi [3, nchi, npix] exactly as in za_density_sph; its mass goes to the 4
+ *            interpolation pixels of its new direction x the 2 radial bins around its new distance (chi extended by one
+ *            extrapolated cell at each end, np.digitize, weights |chi1 - x| / dchi and |x - chi0| / dchi); a bin outside
+ *            [0, nchi) drops its share.  out [nchi, npix] is ADDED to, then 1 is subtracted from every element.  Bin ri
+ *            goes to out[ri, pix] (the reference's C scatter uses a row stride of 4 instead of npix).
+ *            chi ascending, nchi >= 2.  Global f64 atomics: repeated calls agree to rounding, not bit for bit.          */
+int corahip_healpix_interp_weights(corahip_ctx *ctx, int nside, const double *theta, const double *phi, long n,
+                                   int64_t *pix_out, double *w_out);
+int corahip_healpix_interp_val(corahip_ctx *ctx, const double *maps, long nmap, int nside, const double *theta,
+                               const double *phi, long n, double *out);
+int corahip_healpix_rotate_maps(corahip_ctx *ctx, const double *maps, long nmap, int nside, const double *R, double *out);
+int corahip_za_density_grid(corahip_ctx *ctx, const double *psi, const double *delta_bias, const double *chi, int nchi,
+                            int nside, double *out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
