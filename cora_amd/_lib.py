@@ -87,6 +87,7 @@ SIGNATURES = {
     "corahip_alm2map_spin2": (c_int, [c_void_p, c_void_p, PTR, c_int, PTR, c_void_p, c_size_t]),
     "corahip_spin2_ring_scale": (c_int, [c_void_p, c_void_p, PTR, c_int, PTR]),
     "corahip_spin2_combine": (c_int, [c_void_p, c_void_p, PTR, c_int, c_int, PTR, c_int]),
+    "corahip_xi_table_max_knots": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "corahip_xi_table_average": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, c_double, c_double, PTR, c_int, PTR, PTR,
                                          c_int, c_int, PTR]),
     "corahip_ps_table21cm": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, c_double, PTR, c_int, PTR, c_int, c_double,
@@ -1215,18 +1216,30 @@ class Context:
         return out
 
     # -- n3: xi(r) -> C_l --------------------------------------------------------------
-    def xi_table_average(self, kx, ky, ky2, kind, x_t, f_t, mu, xa, xw, F, xint):
+    def xi_table_max_knots(self):
+        """Largest spline table ``xi_table_average`` takes: it has to fit the LDS of one workgroup."""
+        n = c_int(0)
+        _check(self.lib.corahip_xi_table_max_knots(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def xi_table_average(self, kx, ky, ky2, kind, x_t, f_t, mu, xa, xw, F, xint, out=None):
         nm = mu.numel()
-        out = self.empty((nm, F, F))
+        if out is None:
+            out = self.empty((nm, F, F))
+        if tuple(out.shape) != (nm, F, F) or not out.is_contiguous():
+            raise ValueError("Given output array is incompatible.")
         _check(self.lib.corahip_xi_table_average(self.h, self._f64(kx), self._f64(ky), self._f64(ky2), kx.numel(), kind,
                                                  float(x_t), float(f_t), self._f64(mu), nm, self._f64(xa), self._f64(xw),
                                                  F, xint, self._f64(out)))
         return out
 
-    def legendre_project(self, mu, wt, lmax, xi):
+    def legendre_project(self, mu, wt, lmax, xi, out=None):
         nm = mu.numel()
         ncol = xi.numel() // nm
-        out = self.empty((lmax + 1, ncol))
+        if out is None:
+            out = self.empty((lmax + 1, ncol))
+        if tuple(out.shape) != (lmax + 1, ncol) or not out.is_contiguous():
+            raise ValueError("Given output array is incompatible.")
         _check(self.lib.corahip_legendre_project(self.h, self._f64(mu), self._f64(wt), nm, lmax, self._f64(xi),
                                                  ncol, self._f64(out)))
         return out

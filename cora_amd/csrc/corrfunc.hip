@@ -8,7 +8,7 @@
 //   dgemm_nn_kernel      C[L x N] = A[L x M] B[M x N] on FP64 MFMA, 128 x 128 tiles, LDS-staged 16-deep K chunks
 #include "common.h"
 
-#include "rng_dev.h"   // fast_log01 (valid for any positive normal argument), fast_sqrt_pos
+#include "rng_dev.h"   // fast_log01, fast_sqrt_pos (both hold their accuracy over every positive normal argument met here)
 
 // natural cubic spline with end-slope extrapolation, as cubicspline.pyx:126-175.  Knot tables in LDS:
 // xs, ys, y2 and per interval 1/h and h^2/6 (no divisions per evaluation); the interval comes from a uniform
@@ -75,10 +75,11 @@ __device__ static inline double fast_sinh(double y) {
     const double s = 0.5 * (E + E / (E + 1.0));
     return y < 0.0 ? -s : s;
 }
-// e^y, |y| < ~700 (e^{-inf} = 0)
+// e^y: the short kernel for |y| < 700; beyond it (2^k or its reciprocal would leave the normal range on the way: the
+// subnormal results down to y ~ -745, the last normal ones up to y ~ 709.78, e^{-inf} = 0, NaN) the library's exp
 __device__ static inline double fast_exp(double y) {
     const double ay = fabs(y);
-    if (!(ay < 700.0)) return y < 0.0 ? 0.0 : exp(y);
+    if (!(ay < 700.0)) return exp(y);
     const double E1 = fast_expm1_pos(ay) + 1.0;
     return y < 0.0 ? 1.0 / E1 : E1;
 }
@@ -139,7 +140,9 @@ xi_table_kernel(const double *__restrict__ kx, const double *__restrict__ ky, co
             for (int b = 0; b < xint; b++) {
                 const double x2 = xa[j * xint + b];
                 const double dx12 = x1 - x2;
-                const double r = sqrt(dx12 * dx12 + 2.0 * x1 * x2 * om);
+                // one fma on the rounded product ((2 x1) x2) om - what the compiler contracts the plain expression to,
+                // written out so that the host oracle of the tests can restate r bit for bit
+                const double r = sqrt(fma(dx12, dx12, 2.0 * x1 * x2 * om));
                 double v;
                 if (kind == 1) v = fast_exp(spline_eval(S, r > 0.0 ? fast_log01(r) : -INFINITY));
                 else if (kind == 2) v = f_t * fast_sinh(spline_eval(S, fast_asinh_pos(r * inv_xt)));
@@ -259,16 +262,40 @@ dgemm_nn_kernel(const double *__restrict__ A, int lda, const double *__restrict_
         }
 }
 
+// LDS of xi_table_kernel per knot: xs, ys, y2, 1/h, h^2/6 (5 doubles) and the 4 look-up cells (4 ints)
+#define XI_LDS_PER_KNOT (5 * sizeof(double) + 4 * sizeof(int))
+
+static int xi_lds_bytes(corahip_ctx *ctx, int *bytes) {
+    HIP_TRY(hipDeviceGetAttribute(bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+    return 0;
+}
+
 extern "C" {
+
+int corahip_xi_table_max_knots(corahip_ctx *ctx, int *max_knots) {
+    ARG_CHECK(ctx != nullptr && max_knots != nullptr);
+    int lds = 0;
+    if (int rc = xi_lds_bytes(ctx, &lds)) return rc;
+    *max_knots = (int)((size_t)lds / XI_LDS_PER_KNOT);
+    return 0;
+}
 
 int corahip_xi_table_average(corahip_ctx *ctx, const double *knots_x, const double *knots_y, const double *knots_y2,
                              int nk, int kind, double x_t, double f_t, const double *mu, int nm, const double *xa,
                              const double *xw, int F, int xint, double *out) {
     ARG_CHECK(ctx != nullptr && knots_x && knots_y && knots_y2 && mu && xa && xw && out);
-    ARG_CHECK(nk >= 4 && nk <= 6000 && kind >= 0 && kind <= 2 && nm >= 1 && F >= 1 && xint >= 1);
+    ARG_CHECK(nk >= 4 && kind >= 0 && kind <= 2 && nm >= 1 && F >= 1 && xint >= 1);
+    int lds = 0;
+    if (int rc = xi_lds_bytes(ctx, &lds)) return rc;
+    const int nk_max = (int)((size_t)lds / XI_LDS_PER_KNOT);
+    if (nk > nk_max) {   // the whole table lives in the LDS of every workgroup: nothing is launched for one that cannot
+        corahip_set_error("invalid argument: nk = %d knots exceed the limit of %d (%d bytes of LDS per workgroup, %d per knot) (%s:%d)",
+                          nk, nk_max, lds, (int)XI_LDS_PER_KNOT, __FILE__, __LINE__);
+        return CORAHIP_EINVAL;
+    }
     StageTimer t(ctx, "xi_average");
     const int nlut = 4 * nk;
-    const size_t shm = sizeof(double) * 5 * (size_t)nk + sizeof(int) * (size_t)nlut;
+    const size_t shm = XI_LDS_PER_KNOT * (size_t)nk;
     HIP_TRY(hipFuncSetAttribute((const void *)xi_table_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     const long total = (long)nm * F * (F + 1) / 2;
     const int blocks = (int)std::min<long>((total + 255) / 256, (long)ctx->num_cu * 8);

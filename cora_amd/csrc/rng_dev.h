@@ -52,9 +52,11 @@ __device__ static const double2 LOG_TAB[47] = {
 #include "log_tab.inc"
 };
 
+// x: K3 calls it on (0, 1]; corrfunc.hip on separations and on q + sqrt(q^2 + 1) >= 1, held to its bound up to 2e8
+// (tests/test_gpu_corrfunc.py).
 // `tab`: the 47-entry table, LOG_TAB itself or a copy of it in LDS (K3: a look-up in global memory is a dependent
 // vmcnt-ordered load on the critical path of every normal pair - and waits for the LDS-DMA stage issued before it)
-__device__ static inline double fast_log01(double x, const double2 *tab = LOG_TAB) {  // x in (0, 1]
+__device__ static inline double fast_log01(double x, const double2 *tab = LOG_TAB) {  // any positive normal x
     double m = __builtin_amdgcn_frexp_mant(x);           // [0.5, 1)
     int e = __builtin_amdgcn_frexp_exp(x);
     const bool lo = m < 0.70710678118654752440;
@@ -74,7 +76,7 @@ __device__ static inline double fast_log01(double x, const double2 *tab = LOG_TA
     return fma((double)e, 0.69314718055994530942, tc.y + p);
 }
 
-__device__ static inline double fast_sqrt_pos(double t) {  // t in [0, ~80]
+__device__ static inline double fast_sqrt_pos(double t) {  // t >= 0: scale-free (K3: [0, ~80]; corrfunc.hip: q^2 + 1 up to 1e16)
     const double y = __builtin_amdgcn_rsq(t);
     double g = t * y, h = 0.5 * y;
     double r = fma(-h, g, 0.5);

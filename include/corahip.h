@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 9      /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid */
+#define CORAHIP_ABI_MINOR 10     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -429,11 +429,15 @@ int corahip_dct1_rows(corahip_ctx *ctx, double *data, long nrows, int n, double 
  * xi_table_average: for every Gauss-Legendre node mu_m and channel pair (i, j) the radial-bin average
  *   sum_ab xw_a xw_b xi(r(mu_m, xa[i xint + a], xa[j xint + b])),  r^2 = (x - x')^2 + 2 x x' (1 - mu)
  *   (corrfunc.py:368-381) of a correlation function given as a natural cubic spline with end-slope
- *   extrapolation (cora/util/cubicspline.pyx:126-231): knots (x, y, y'') [nk];
+ *   extrapolation (cora/util/cubicspline.pyx:126-231): knots (x, y, y'') [nk],
+ *   4 <= nk <= the limit xi_table_max_knots reports: the table and its look-up grid live in the LDS of every
+ *   workgroup, 56 bytes per knot of the device's shared memory per workgroup (160 KB: 2925 knots); a larger table is
+ *   CORAHIP_EINVAL with the limit in corahip_last_error(), before anything is launched;
  *   kind 0: spline(r); 1: exp(spline(log r)) (LogInterpolater); 2: f_t sinh(spline(asinh(r / x_t)))
  *   (SinhInterpolater).  out [nm, F, F].
  * legendre_project: out[l, n] = sum_m wt[m] P_l(mu[m]) xi[m, n], l = 0..lmax (corrfunc.py:387-397, where
  *   wt = w 4 pi / wsum); xi [nm, ncol], out [lmax+1, ncol]: Legendre matrix by recurrence + FP64 MFMA GEMM. */
+int corahip_xi_table_max_knots(corahip_ctx *ctx, int *max_knots);
 int corahip_xi_table_average(corahip_ctx *ctx, const double *knots_x, const double *knots_y,
                              const double *knots_y2, int nk, int kind, double x_t, double f_t,
                              const double *mu, int nm, const double *xa, const double *xw, int F, int xint,
