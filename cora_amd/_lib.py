@@ -122,6 +122,9 @@ SIGNATURES = {
     "corahip_healpix_interp_val": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, PTR, PTR, ctypes.c_long, PTR]),
     "corahip_healpix_rotate_maps": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, ctypes.POINTER(c_double), PTR]),
     "corahip_za_density_grid": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, PTR]),
+    "corahip_complex_variance": (c_int, [c_void_p, PTR, ctypes.c_long, PTR]),
+    "corahip_faraday_mix": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, PTR, PTR, PTR, c_int, c_double, PTR, PTR]),
+    "corahip_faraday_pack": (c_int, [c_void_p, PTR, c_int, ctypes.c_long, c_int, c_int, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -1432,6 +1435,102 @@ class Context:
         _check(self.lib.corahip_za_density_grid(self.h, self._f64(psi), self._f64(delta_bias), self._f64(chi), int(nchi),
                                                 self._nside_of(npix), self._f64(out)))
         return out
+
+    # -- polarised galaxy: Faraday-depth synthesis (csrc/faraday.hip) --------------------------------------------------
+    def _cfield2d(self, t, name):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError("%s must be a 2-D complex128 device tensor (got shape %r)" % (name, tuple(getattr(t, "shape", ()))))
+        if t.dtype != torch.complex128 or not t.is_contiguous() or t.device != self.device:
+            raise ValueError("%s must be a contiguous complex128 tensor on %s" % (name, self.device))
+        return int(t.shape[0]), int(t.shape[1])
+
+    def complex_variance(self, y):
+        """``chunk_var`` (cora/foreground/galaxy.py:58-83) of a complex128 device array: ``(var, mean)`` as a host float
+        and complex, ``var = sum |y - mean|^2 / y.size``.  Fixed summation order (block partials, ordered final pass):
+        identical bits from call to call.  Waits for the result."""
+        torch = _torch()
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.complex128 or y.device != self.device:
+            raise ValueError("complex_variance takes a complex128 tensor on %s" % (self.device,))
+        if not y.is_contiguous() or y.numel() < 1:
+            raise ValueError("complex_variance takes a contiguous, non-empty tensor")
+        out = self.empty((3,))
+        _check(self.lib.corahip_complex_variance(self.h, self._p(y), int(y.numel()), self._f64(out)))
+        v = out.cpu().numpy()
+        return float(v[0]), complex(v[1], v[2])
+
+    def faraday_mix(self, y, phi, sigma, A, scale, intensity=None, out=None):
+        """The fused depth -> frequency step of ``getpolsky`` (cora/foreground/galaxy.py:286-331), one FP64 MFMA kernel.
+
+        y : complex128 device [ncol, nphi], the depth cube after the inverse FFT, unweighted; nphi even
+        phi : [nphi] depth grid, sigma : [ncol] positive widths (host arrays or device tensors)
+        A : complex128 [nfreq, nphi] (host or device), the transpose of the reference's ``pta``
+        scale : float, ``1 / (2 sqrt(var))``
+
+        ``w = exp(-0.25 (phi / sigma)^2)`` normalised over depth, ``z = scale * A @ (w y).T``, ``P = z tanh|z| / |z|``
+        (0 where z = 0; the reference gives NaN there).  Returns P, complex128 [nfreq, ncol]; with ``intensity``
+        (float64 device [nfreq, ncol]) returns float64 [nfreq, 4, ncol] = (intensity, Re P intensity, Im P intensity, 0).
+        ``out`` must not overlap an input (ValueError).  No atomics: identical bits from call to call."""
+        torch = _torch()
+        ncol, nphi = self._cfield2d(y, "y")
+        if nphi < 2 or nphi % 2 or ncol < 1:
+            raise ValueError("faraday_mix: nphi must be even and >= 2 (got y of shape %r)" % ((ncol, nphi),))
+        if isinstance(A, torch.Tensor):
+            if A.dim() != 2:
+                raise ValueError("A must be [nfreq, nphi] (got shape %r)" % (tuple(A.shape),))
+        else:
+            A = np.ascontiguousarray(A, dtype=np.complex128)
+            if A.ndim != 2:
+                raise ValueError("A must be [nfreq, nphi] (got shape %r)" % (A.shape,))
+        nfreq = int(A.shape[0])
+        if nfreq < 1 or int(A.shape[1]) != nphi:
+            raise ValueError("Array A has the wrong shape (got %r, expected (nfreq, %d))" % (tuple(A.shape), nphi))
+        for name, v, n in (("phi", phi, nphi), ("sigma", sigma, ncol)):
+            if tuple(np.shape(v)) != (n,):
+                raise ValueError("Array %s has shape %r, expected (%d,)" % (name, tuple(np.shape(v)), n))
+        scale = float(scale)
+        if intensity is not None:
+            if (not isinstance(intensity, torch.Tensor) or tuple(intensity.shape) != (nfreq, ncol)
+                    or intensity.dtype != torch.float64 or not intensity.is_contiguous() or intensity.device != self.device):
+                raise ValueError("intensity must be a contiguous float64 [%d, %d] tensor on %s" % (nfreq, ncol, self.device))
+            oshape, odtype = (nfreq, 4, ncol), torch.float64
+        else:
+            oshape, odtype = (nfreq, ncol), torch.complex128
+        if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != oshape or out.dtype != odtype
+                                or not out.is_contiguous() or out.device != self.device):
+            raise ValueError("out must be a contiguous %s %r tensor on %s" % (odtype, oshape, self.device))
+        if not isinstance(A, torch.Tensor):
+            A = torch.from_numpy(A).to(self.device)
+        self._cfield2d(A, "A")
+        phi = self._rowvec(phi, nphi, "phi")
+        sigma = self._rowvec(sigma, ncol, "sigma")
+        if out is None:
+            out = torch.empty(oshape, dtype=odtype, device=self.device)
+        obytes = out.numel() * out.element_size()
+        for name, t in (("y", y), ("A", A), ("phi", phi), ("sigma", sigma), ("intensity", intensity)):
+            if t is not None and self._overlap(out, obytes, t, t.numel() * t.element_size()):
+                raise ValueError("faraday_mix: out overlaps %s" % name)
+        _check(self.lib.corahip_faraday_mix(self.h, self._p(y), ncol, nphi, self._f64(phi), self._f64(sigma), self._p(A),
+                                            nfreq, scale, None if intensity is None else self._f64(intensity),
+                                            self._p(out)))
+        return out
+
+    def faraday_pack(self, maps, y, k0):
+        """Real device maps ``[2 nchunk, npix]`` (rows 2 j, 2 j + 1: real and imaginary part of depth channel k0 + j) into
+        columns ``k0 .. k0 + nchunk - 1`` of the complex128 depth cube ``y`` [npix, nphi] (an LDS tile transpose)."""
+        torch = _torch()
+        npix, nphi = self._cfield2d(y, "y")
+        if (not isinstance(maps, torch.Tensor) or maps.dim() != 2 or maps.dtype != torch.float64 or not maps.is_contiguous()
+                or maps.device != self.device):
+            raise ValueError("maps must be a contiguous float64 [2 nchunk, npix] tensor on %s" % (self.device,))
+        R = int(maps.shape[0])
+        k0 = int(k0)
+        if R < 2 or R % 2 or int(maps.shape[1]) != npix or k0 < 0 or k0 + R // 2 > nphi:
+            raise ValueError("faraday_pack: maps %r at k0 = %d do not fit y %r" % (tuple(maps.shape), k0, (npix, nphi)))
+        if self._overlap(y, npix * nphi * 16, maps, R * npix * 8):
+            raise ValueError("faraday_pack: y overlaps maps")
+        _check(self.lib.corahip_faraday_pack(self.h, self._f64(maps), R // 2, npix, k0, nphi, self._p(y)))
+        return y
 
     def sht_rings(self, nside, lmax):
         plan = self.sht_plan(nside, lmax)

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 10     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots */
+#define CORAHIP_ABI_MINOR 11     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -606,6 +606,27 @@ int corahip_healpix_interp_val(corahip_ctx *ctx, const double *maps, long nmap, 
 int corahip_healpix_rotate_maps(corahip_ctx *ctx, const double *maps, long nmap, int nside, const double *R, double *out);
 int corahip_za_density_grid(corahip_ctx *ctx, const double *psi, const double *delta_bias, const double *chi, int nchi,
                             int nside, double *out);
+
+/* Polarised galactic emission: the body of ConstrainedGalaxy.getpolsky (cora/foreground/galaxy.py:209-344) behind its
+ * random maps (csrc/faraday.hip).  Complex arrays are interleaved (re, im) float64, 16-byte aligned.
+ * complex_variance: chunk_var (galaxy.py:58-83) of a complex array: with m = mean(y), out2[0] = sum |y - m|^2 / count,
+ *            out2[1..2] = m (device).  Block partials, then one ordered pass, for the mean and again for the squares: no
+ *            atomics, identical bits from call to call.
+ * faraday_mix: y [ncol, nphi] complex (the depth cube after the inverse FFT, unweighted), phi [nphi] the depth grid,
+ *            sigma [ncol] > 0, A [nfreq, nphi] complex (the transpose of the reference's pta), scale = 1 / (2 sqrt(var)):
+ *              w[p, k] = exp(-0.25 (phi[k] / sigma[p])^2) / sum_k' exp(-0.25 (phi[k'] / sigma[p])^2)      (:288-292)
+ *              z[f, p] = scale sum_k A[f, k] w[p, k] y[p, k]                                              (:286, :295, :313)
+ *              P[f, p] = z tanh|z| / |z|, 0 where z = 0 (the reference gives NaN there)                   (:319-320)
+ *            intensity [nfreq, ncol] given: out [nfreq, 4, ncol] = (intensity, Re P intensity, Im P intensity, 0)
+ *            (:324-331); NULL: out complex [nfreq, ncol] = P.  FP64 MFMA, M = channel, N = column, K = depth; weighting,
+ *            saturation and the product with intensity are the operand prologue and the epilogue of the one kernel.
+ *            nphi even, >= 2; nfreq, ncol >= 1.  out must not overlap an input.  No atomics, fixed sum order.
+ * faraday_pack: maps [2 nchunk, npix] real (rows 2 j, 2 j + 1: real and imaginary part of depth channel k0 + j) into
+ *            y[p, k0 + j] of the complex [npix, nphi] cube; k0 + nchunk <= nphi.                                        */
+int corahip_complex_variance(corahip_ctx *ctx, const double *y, long count, double *out2);
+int corahip_faraday_mix(corahip_ctx *ctx, const double *y, long ncol, int nphi, const double *phi, const double *sigma,
+                        const double *A, int nfreq, double scale, const double *intensity, double *out);
+int corahip_faraday_pack(corahip_ctx *ctx, const double *maps, int nchunk, long npix, int k0, int nphi, double *y);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
