@@ -125,6 +125,13 @@ SIGNATURES = {
     "corahip_complex_variance": (c_int, [c_void_p, PTR, ctypes.c_long, PTR]),
     "corahip_faraday_mix": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, PTR, PTR, PTR, c_int, c_double, PTR, PTR]),
     "corahip_faraday_pack": (c_int, [c_void_p, PTR, c_int, ctypes.c_long, c_int, c_int, PTR]),
+    "corahip_pointsource_population": (c_int, [c_void_p, c_u64, ctypes.c_long, PTR, PTR, PTR, c_int, c_double, c_double,
+                                               c_double, ctypes.c_long, PTR, PTR, PTR, PTR, PTR]),
+    "corahip_pointsource_paint": (c_int, [c_void_p, ctypes.c_long, PTR, PTR, PTR, PTR, PTR, PTR, PTR, c_double, c_int, c_int,
+                                          ctypes.c_long, c_int, PTR]),
+    "corahip_polarise_rotate": (c_int, [c_void_p, PTR, PTR, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
+    "corahip_faraday_rotate": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, ctypes.c_long]),
+    "corahip_healpix_ud_grade": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, c_int, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -1531,6 +1538,136 @@ class Context:
             raise ValueError("faraday_pack: y overlaps maps")
         _check(self.lib.corahip_faraday_pack(self.h, self._f64(maps), R // 2, npix, k0, nphi, self._p(y)))
         return y
+
+    # -- point sources (csrc/pointsource.hip) ---------------------------------------------------------------------------
+    def _vec(self, v, n, name, dtype=None):
+        """A host array or device tensor as a contiguous device vector of ``n`` elements (ValueError otherwise)."""
+        torch = _torch()
+        dtype = dtype or torch.float64
+        if not isinstance(v, torch.Tensor):
+            v = np.asarray(v)
+            if v.shape != (n,):
+                raise ValueError("%s has shape %r, expected (%d,)" % (name, v.shape, n))
+            return torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64 if dtype == torch.int64 else np.float64)).to(self.device)
+        if tuple(v.shape) != (n,) or v.dtype != dtype or v.device != self.device or not v.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of %d elements on %s" % (name, dtype, n, self.device))
+        return v
+
+    def pointsource_population(self, seed, n, knots, values, second, flux_min, spectral_mean, spectral_width, npix,
+                               interval=False):
+        """``n`` synthetic sources in one launch: ``(pix int64 [n], flux [n], index [n])`` device tensors (and the int32
+        spline interval and float64 spline value of every source with ``interval=True``).  ``knots, values, second``: the inverse-CDF spline
+        (``Interpolater.data()``), host arrays.  The mapping from ``(seed, i)`` to source i is written down in
+        include/corahip.h and tests/_pointsource_oracle.py."""
+        torch = _torch()
+        n, npix = int(n), int(npix)
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        if knots.ndim != 1 or knots.size < 2:
+            raise ValueError("knots must be a 1-d array of at least 2 elements")
+        if n < 0 or npix < 1:
+            raise ValueError("pointsource_population: n >= 0 and npix >= 1 (got %d, %d)" % (n, npix))
+        if not (knots[0] <= 0.0 and knots[-1] >= 1.0 and np.all(np.diff(knots) >= 0)):
+            raise ValueError("knots must ascend from 0 to 1 (an inverse CDF)")
+        xs = self._vec(knots, knots.size, "knots")
+        ys, y2 = self._vec(values, knots.size, "values"), self._vec(second, knots.size, "second")
+        pix = torch.empty((n,), dtype=torch.int64, device=self.device)
+        flux, index = self.empty((n,)), self.empty((n,))
+        iv = torch.empty((n,), dtype=torch.int32, device=self.device) if interval else None
+        sv = self.empty((n,)) if interval else None
+        _check(self.lib.corahip_pointsource_population(self.h, c_u64(int(seed) & (2**64 - 1)), n, self._f64(xs), self._f64(ys),
+                                                       self._f64(y2), int(knots.size), float(flux_min), float(spectral_mean),
+                                                       float(spectral_width), npix, self._p(pix), self._f64(flux),
+                                                       self._f64(index), self._p0(iv), self._p0(sv)))
+        return (pix, flux, index, iv, sv) if interval else (pix, flux, index)
+
+    def pointsource_paint(self, pix, flux, beta, x, den, c2, npix, gamma=None, polw=None, npol=1, out=None, accumulate=False):
+        """Sources sorted by pixel painted into ``out`` [nfreq, npol, npix] (``npol`` 1: [nfreq, npix]):
+        ``out[f, 0, p] (+)= ((sum_i flux_i exp(beta_i x_f + gamma_i x_f^2)) 1e-26 c2) / den_f`` over the sources of pixel p,
+        planes 1, 2 the same sums weighted by ``polw[:, 0 / 1]``.  ``pix`` int64 ascending in [0, npix) (the caller
+        sorts); ``x``, ``den`` host arrays [nfreq].  One writer per element, fixed summation order, no atomics: identical
+        bits from call to call and for any subset of channels.  ``accumulate``: add to ``out`` (occupied pixels only)
+        instead of writing all of it."""
+        torch = _torch()
+        if not isinstance(pix, torch.Tensor) or pix.dim() != 1:
+            raise ValueError("pix must be a 1-d int64 device tensor")
+        n, npix, npol = int(pix.shape[0]), int(npix), int(npol)
+        if npol not in (1, 4) or (polw is not None and npol != 4):
+            raise ValueError("npol must be 1 or 4, and 4 with polw")
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        den = np.ascontiguousarray(den, dtype=np.float64)
+        if x.ndim != 1 or x.size < 1 or den.shape != x.shape:
+            raise ValueError("x and den must be 1-d arrays of one length (got %r, %r)" % (x.shape, den.shape))
+        F = int(x.size)
+        pix = self._vec(pix, n, "pix", torch.int64)
+        flux, beta = self._vec(flux, n, "flux"), self._vec(beta, n, "beta")
+        gamma = None if gamma is None else self._vec(gamma, n, "gamma")
+        if polw is not None:
+            if not isinstance(polw, torch.Tensor):
+                polw = self.to_device(np.asarray(polw, dtype=np.float64))
+            if tuple(polw.shape) != (n, 2) or polw.dtype != torch.float64 or polw.device != self.device or not polw.is_contiguous():
+                raise ValueError("polw must be a contiguous float64 [%d, 2] tensor on %s" % (n, self.device))
+        shape = (F, npix) if npol == 1 else (F, npol, npix)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs out")
+            out = self.empty(shape)
+        elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape or out.dtype != torch.float64
+              or out.device != self.device or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous float64 %r tensor on %s" % (shape, self.device))
+        xd, dend = self.to_device(x), self.to_device(den)     # named: they must outlive the argument list
+        _check(self.lib.corahip_pointsource_paint(self.h, n, self._p(pix), self._f64(flux), self._f64(beta), self._p0(gamma),
+                                                  self._p0(polw), self._f64(xd), self._f64(dend), float(c2), F, npol, npix,
+                                                  1 if accumulate else 0, self._f64(out)))
+        return out
+
+    def _cube(self, t, rank, name):
+        torch = _torch()
+        if (not isinstance(t, torch.Tensor) or t.dim() != rank or t.dtype != torch.float64 or t.device != self.device
+                or not t.is_contiguous() or t.numel() < 1):
+            raise ValueError("%s must be a contiguous, non-empty float64 device tensor of rank %d on %s" % (name, rank, self.device))
+        return t
+
+    def polarise_rotate(self, intensity, qfrac, ufrac, wv=None, rm=None, out=None):
+        """``intensity`` [nfreq, npix] -> [nfreq, 4, npix] = (I, Re P, Im P, 0), ``P = I (qfrac + i ufrac) exp(-2i wv_f rm_p)``
+        (pointsource.py:258-276); ``rm=None``: no rotation.  ``wv`` [nfreq] host array, the wavelength ``1e-6 c / freq``."""
+        intensity = self._cube(intensity, 2, "intensity")
+        F, npix = int(intensity.shape[0]), int(intensity.shape[1])
+        q, u = self._vec(qfrac, npix, "qfrac"), self._vec(ufrac, npix, "ufrac")
+        rmd = None if rm is None else self._vec(rm, npix, "rm")
+        if rm is not None and wv is None:
+            raise ValueError("polarise_rotate: rm needs wv")
+        wvd = None if wv is None else self._vec(np.asarray(wv, dtype=np.float64), F, "wv")
+        if out is None:
+            out = self.empty((F, 4, npix))
+        elif self._cube(out, 3, "out").shape != (F, 4, npix):
+            raise ValueError("out must be [%d, 4, %d]" % (F, npix))
+        _check(self.lib.corahip_polarise_rotate(self.h, self._f64(intensity), self._f64(q), self._f64(u), self._p0(rmd),
+                                                self._p0(wvd), F, npix, self._f64(out)))
+        return out
+
+    def faraday_rotate(self, polmap, rm, wv):
+        """``faraday_rotate`` (pointsource.py:21-51) in place on the device cube ``polmap`` [nfreq, npol >= 3, npix]."""
+        polmap = self._cube(polmap, 3, "polmap")
+        F, npol, npix = (int(v) for v in polmap.shape)
+        if npol < 3:
+            raise ValueError("polmap needs the planes T, Q, U (got %d planes)" % npol)
+        rmd = self._vec(rm, npix, "rm")
+        wvd = self._vec(np.asarray(wv, dtype=np.float64), F, "wv")
+        _check(self.lib.corahip_faraday_rotate(self.h, self._f64(polmap), self._f64(rmd), self._f64(wvd), F, npol, npix))
+        return polmap
+
+    def healpix_ud_grade(self, maps, nside_out):
+        """``healpy.ud_grade(power=None)`` of device maps [nmap, npix], RING in and out: [nmap, 12 nside_out^2]."""
+        nmap, nside_in = self._map_stack(maps)
+        nside_out = int(nside_out)
+        for ns in (nside_in, nside_out):
+            if ns < 1 or ns & (ns - 1) or ns > 8192:
+                raise ValueError("ud_grade: nside must be a power of two up to 8192 (got %d)" % ns)
+        if nside_in > 64 * nside_out:
+            raise ValueError("ud_grade degrades by at most a factor 64 in nside per call (got %d -> %d)" % (nside_in, nside_out))
+        out = self.empty((nmap, 12 * nside_out * nside_out))
+        _check(self.lib.corahip_healpix_ud_grade(self.h, self._f64(maps), nmap, nside_in, nside_out, self._f64(out)))
+        return out
 
     def sht_rings(self, nside, lmax):
         plan = self.sht_plan(nside, lmax)

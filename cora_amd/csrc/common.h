@@ -46,7 +46,7 @@ int flat_r2c_ct(corahip_ctx *ctx, const double *in, double *spec, long nlines, i
 int flat_c2c_ct(corahip_ctx *ctx, const double *in, double *out, long nouter, int n, long inner, int inverse, double scale, bool gen,
                 uint64_t seed, bool *took);
 
-#define CORAHIP_NSCRATCH 11
+#define CORAHIP_NSCRATCH 12
 struct corahip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -74,7 +74,7 @@ struct corahip_ctx {
     //        4 Legendre matrix of legendre_project, 5 its zero-padded operand, 6 block tables of normals_pcg64 /
     //        segment tables of normals_mt19937_legacy, 7 the two-slot ring of the l-range pipeline (drawstream.hip),
     //        8 barrier words of the cooperative Cholesky, 9 position lists of the MT19937 jump polynomials,
-    //        10 block partials of complex_variance (faraday.hip)
+    //        10 block partials of complex_variance (faraday.hip), 11 per-pixel source offsets of pointsource_paint
     void *scratch[CORAHIP_NSCRATCH] = {};
     size_t scratch_bytes[CORAHIP_NSCRATCH] = {};
     // K1 transposed tables resident in scratch slot 0: valid for the pinned (dd, dv, vv, generation) only

@@ -2,10 +2,10 @@
 
 Mirrors the command-line surface of cora/scripts/makesky.py: the frequency-channelisation options
 (``FreqState``, :44-198), the map options (``--nside --pol --filename``, :170-198), the ``21cm``
-(:313-345), ``gaussianfg`` (:348-390) and ``singlesource`` (:393-409) commands and the map container
-written by ``write_map`` (:412-450).  The ``foreground`` / ``galaxy`` / ``pointsource`` commands need the
-constrained-galaxy and point-source catalogue models (non-Gaussian, data-file driven), which are not part
-of the hot path: they exist here so that scripts fail with a clear message rather than "no such command".
+(:313-345), ``gaussianfg`` (:348-390), ``pointsource`` (:283-310) and ``singlesource`` (:393-409) commands and the map
+container written by ``write_map`` (:412-450).  The ``foreground`` / ``galaxy`` commands need the constrained-galaxy
+model (data-file driven, healpy smoothing), which is not part of this package: they exist here so that scripts fail
+with a clear message rather than "no such command".
 
     python -m cora_amd.scripts.makesky 21cm --nside 256 --freq 400 800 64 --freq-mode edge --pol none --filename m.h5
 """
@@ -146,10 +146,32 @@ def galaxy(fstate, nside, pol, filename, spectral_index):
 
 @cli.command()
 @map_options
-@click.option("--maxflux", default=1e6, type=float)
-def pointsource(fstate, nside, pol, filename, maxflux):
-    """Point source only foreground map: not available in cora_amd."""
-    _not_in_scope("pointsource")
+@click.option("--maxflux", default=1e6, type=float,
+              help="Maximum flux of point included point source (in Jy). Default is 1 MJy.")
+@click.option("--catalogue", type=click.Path(exists=True, dir_okay=False), default=None,
+              help="Table of the real sources above 4 Jy (columns RA DEC S600 P600 POLANG BETA GAMMA); without it that "
+                   "component is left out (cora_amd extension).")
+@click.option("--faraday-map", type=click.Path(exists=True, dir_okay=False), default=None,
+              help="Rotation-measure map (rad / m^2, RING order) as a .npy file; needed by --pol full (cora_amd extension).")
+@click.option("--seed", type=int, default=None, help="Seed of the numpy Generator (cora_amd extension).")
+def pointsource(fstate, nside, pol, filename, maxflux, catalogue, faraday_map, seed):
+    """Generate a point source only foreground map.
+
+    For S > 4 Jy (at 600 MHz) use real point sources (--catalogue), for dimmer sources (but S > 0.1 Jy at 151 MHz)
+    generate a synthetic population, for even dimmer sources use a Gaussian realisation of unresolved sources.
+    """
+    from ..foreground import pointsource as ps_mod
+
+    if pol == "full" and faraday_map is None:
+        raise click.ClickException("--pol full Faraday rotates the polarised sources and needs the rotation-measure map: "
+                                   "pass --faraday-map FILE.npy, or use --pol zero / --pol none")
+    ps = ps_mod.CombinedPointSources(catalogue=catalogue, faraday_map=None if faraday_map is None else np.load(faraday_map))
+    ps.nside = nside
+    ps.frequencies = fstate.frequencies
+    ps.flux_max = maxflux
+    rng = np.random.default_rng(seed) if seed is not None else None
+    cs = ps.getpolsky(rng=rng) if pol == "full" else ps.getsky(rng=rng)
+    write_map(filename, cs, ps.frequencies, fstate.freq_width, pol != "none")
 
 
 @cli.command("21cm")

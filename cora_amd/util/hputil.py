@@ -654,6 +654,22 @@ def rotate_map_device(maps, R, out=None):
     return _lib.get_context().healpix_rotate_maps(maps, R, out=out)
 
 
+def ud_grade(map_in, nside_out):
+    """``healpy.ud_grade(map_in, nside_out)`` with its defaults (``power=None``, RING in and out) for one map [npix] or
+    maps [n, npix], between two power-of-two resolutions: degrading takes the arithmetic mean of the ``4^k`` children,
+    upgrading replicates the parent.  numpy in, numpy out; a device tensor stays on the device.  No ``UNSEEN`` handling.
+    Restated from the NESTED hierarchy of Gorski et al. 2005 (corahip_healpix_ud_grade) and pinned by its properties and
+    a numpy oracle (tests/_pointsource_oracle.py), not by healpy's output."""
+    ctx = _lib.get_context()
+    host = not hasattr(map_in, "data_ptr")
+    m = ctx.to_device(np.asarray(map_in, dtype=np.float64)) if host else map_in
+    if m.dim() not in (1, 2):
+        raise ValueError("ud_grade takes one map [npix] or maps [n, npix]")
+    out = ctx.healpix_ud_grade(m.reshape(-1, m.shape[-1]).contiguous(), nside_out)
+    out = out[0] if m.dim() == 1 else out
+    return out.cpu().numpy() if host else out
+
+
 # J2000 constants of the coordinate systems (IAU 1958 galactic system transformed to J2000, as in the Hipparcos
 # catalogue vol. 1 sec. 1.5.3; mean obliquity of the IAU 1976 system): degrees
 GAL_POLE_RA, GAL_POLE_DEC, GAL_LON_NCP = 192.85948, 27.12825, 122.93192

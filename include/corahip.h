@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 11     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -627,6 +627,50 @@ int corahip_complex_variance(corahip_ctx *ctx, const double *y, long count, doub
 int corahip_faraday_mix(corahip_ctx *ctx, const double *y, long ncol, int nphi, const double *phi, const double *sigma,
                         const double *A, int nfreq, double scale, const double *intensity, double *out);
 int corahip_faraday_pack(corahip_ctx *ctx, const double *maps, int nchunk, long npix, int k0, int nphi, double *y);
+
+/* Extra-galactic point sources (cora/foreground/pointsource.py; csrc/pointsource.hip).
+ * pointsource_population: the synthetic population of PointSourceModel.getsky (:213-243) in one launch.  Source i draws
+ *            from two Philox4x32-10 blocks that depend on (seed, i) alone, A = counter (i lo, i hi, 0, 0x50535243) and
+ *            B = counter (i lo, i hi, 1, 0x50535243), key = seed (the a_lm and flat-sky streams use counter words 2, 3 = 0,
+ *            so the streams share no block):
+ *              u1 = (A0 2^21 + (A1 >> 11)) 2^-53,  u2 = (A2 2^21 + (A3 >> 11)) 2^-53,  z = first Box-Muller normal of B
+ *              flux[i] = flux_min exp(spline(u1)),  index[i] = spectral_mean + spectral_width z,
+ *              pix[i] = min((int64)(u2 npix), npix - 1)
+ *            spline: the natural cubic spline of cora_amd.util.cubicspline.Interpolater through (knots, values) with
+ *            second derivatives `second` (nknots each; knots ascending from 0 to 1: the inverse CDF of poisson.py:196-206),
+ *            bisection for the last knot <= u1, then the cubic of that interval.  interval: NULL, or int32 [n] receiving
+ *            that knot's index, and spline_value: NULL, or float64 [n] receiving spline(u1) (test hooks).
+ * pointsource_paint: sources sorted by pixel (pix ascending, int64 [n], every value in [0, npix)) into out [nfreq, npol, npix],
+ *            npol 1 or 4.  With T(i, f) = flux[i] exp(beta[i] x[f] + gamma[i] x[f]^2) (gamma NULL: no quadratic term),
+ *              out[f, 0, p] (+)= ((sum over the sources i of pixel p of T(i, f)) 1e-26 c2) / den[f]
+ *            and, with polw [n, 2] given (npol 4), planes 1 and 2 the same sums of T polw[i, 0] and T polw[i, 1].
+ *            accumulate 0: every element of out is written (pixels without a source, plane 3, and planes 1, 2 without
+ *            polw: 0).  accumulate 1: the sums are added to the occupied pixels, nothing else is touched.  One writer per
+ *            element, a pixel's sources summed in ascending order of i (more than 16 of them: lane l of a wave sums sources
+ *            l, l + 64, ..., then a fixed butterfly): no atomics, the same bits from call to call and for any subset of
+ *            channels.  n < 2^31.  x = log(freq / pivot), den = 2 k_B nu^2 1e12 pxarea and c2 = c^2 come from the host.
+ * polarise_rotate: the end of PointSourceModel.getpolsky (:258-276): intensity [nfreq, npix], qfrac, ufrac [npix] ->
+ *            out [nfreq, 4, npix] = (I, Re P, Im P, 0), P = I (qfrac + i ufrac) exp(-2i wv[f] rm[p]); rm NULL: no rotation.
+ * faraday_rotate: faraday_rotate (:21-51) in place on planes 1, 2 of polmap [nfreq, npol, npix], npol >= 3.
+ *            In both the angle is -2 wv rm with wv = 1e-6 c / freq, the wavelength and not its square, as the reference
+ *            has it (:43-45).
+ * healpix_ud_grade: healpy.ud_grade(power = None) of maps [nmap, npix_in], RING in and out, nside_in and nside_out powers of
+ *            two: the arithmetic mean of the 4^k children (summed pairwise in NESTED order) when degrading, replication when
+ *            upgrading; no UNSEEN handling.  out [nmap, npix_out] must not overlap maps.  One thread walks the 4^k children of its
+ *            pixel, so nside_in <= 64 nside_out (EINVAL beyond): degrade further in two calls.  nfreq <= 65535 in the two
+ *            rotation entry points (one grid row per channel).                              */
+int corahip_pointsource_population(corahip_ctx *ctx, uint64_t seed, long n, const double *knots, const double *values,
+                                   const double *second, int nknots, double flux_min, double spectral_mean,
+                                   double spectral_width, long npix, int64_t *pix, double *flux, double *index,
+                                   int32_t *interval, double *spline_value);
+int corahip_pointsource_paint(corahip_ctx *ctx, long n, const int64_t *pix, const double *flux, const double *beta,
+                              const double *gamma, const double *polw, const double *x, const double *den, double c2,
+                              int nfreq, int npol, long npix, int accumulate, double *out);
+int corahip_polarise_rotate(corahip_ctx *ctx, const double *intensity, const double *qfrac, const double *ufrac,
+                            const double *rm, const double *wv, int nfreq, long npix, double *out);
+int corahip_faraday_rotate(corahip_ctx *ctx, double *polmap, const double *rm, const double *wv, int nfreq, int npol,
+                           long npix);
+int corahip_healpix_ud_grade(corahip_ctx *ctx, const double *maps, long nmap, int nside_in, int nside_out, double *out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
