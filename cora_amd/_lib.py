@@ -132,6 +132,10 @@ SIGNATURES = {
     "corahip_polarise_rotate": (c_int, [c_void_p, PTR, PTR, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
     "corahip_faraday_rotate": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, ctypes.c_long]),
     "corahip_healpix_ud_grade": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, c_int, PTR]),
+    "corahip_healpix_reorder": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, c_int, PTR]),
+    "corahip_healpix_block_variance": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, c_int, PTR]),
+    "corahip_alm_scale_l": (c_int, [c_void_p, PTR, c_int, c_int, PTR, PTR]),
+    "corahip_galaxy_combine": (c_int, [c_void_p, PTR, PTR, PTR, PTR, PTR, c_double, PTR, c_int, c_int, ctypes.c_long, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -1667,6 +1671,116 @@ class Context:
             raise ValueError("ud_grade degrades by at most a factor 64 in nside per call (got %d -> %d)" % (nside_in, nside_out))
         out = self.empty((nmap, 12 * nside_out * nside_out))
         _check(self.lib.corahip_healpix_ud_grade(self.h, self._f64(maps), nmap, nside_in, nside_out, self._f64(out)))
+        return out
+
+    # -- constrained galaxy (csrc/galaxy.hip) ----------------------------------------------------------------------------
+    def _out_like(self, out, shape, name):
+        torch = _torch()
+        if out is None:
+            return self.empty(shape)
+        if (not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float64
+                or out.device != self.device or not out.is_contiguous()):
+            raise ValueError("%s: out must be a contiguous float64 %r tensor on %s" % (name, tuple(shape), self.device))
+        return out
+
+    def healpix_reorder(self, maps, r2n, out=None):
+        """``healpy.reorder`` of device maps [nmap, npix]: RING -> NESTED with ``r2n`` true, NESTED -> RING otherwise.  A
+        gather with the pixel map computed in the kernel; ``out`` must not overlap ``maps`` (ValueError)."""
+        nmap, nside = self._map_stack(maps)
+        if nside & (nside - 1) or nside > 8192:
+            raise ValueError("healpix_reorder: nside must be a power of two up to 8192 (got %d)" % nside)
+        out = self._out_like(out, maps.shape, "healpix_reorder")
+        nbytes = maps.numel() * 8
+        if self._overlap(out, nbytes, maps, nbytes):
+            raise ValueError("healpix_reorder: out overlaps maps")
+        _check(self.lib.corahip_healpix_reorder(self.h, self._f64(maps), nmap, nside, 1 if r2n else 0, self._f64(out)))
+        return out
+
+    def healpix_block_variance(self, maps, nside_out):
+        """``map_variance`` (cora/foreground/galaxy.py:43-55) of device maps [nmap, npix]: [nmap, 12 nside_out^2], the
+        variance (numpy ``var``, ddof 0) of the children of every RING pixel at ``nside_out``.  Two passes, pairwise sums in
+        NESTED child order."""
+        nmap, nside_in = self._map_stack(maps)
+        nside_out = int(nside_out)
+        for ns in (nside_in, nside_out):
+            if ns < 1 or ns & (ns - 1) or ns > 8192:
+                raise ValueError("block_variance: nside must be a power of two up to 8192 (got %d)" % ns)
+        if nside_out > nside_in:
+            raise ValueError("block_variance: nside_out must not exceed the maps' nside (got %d -> %d)" % (nside_in, nside_out))
+        if nside_in > 64 * nside_out:
+            raise ValueError("block_variance takes at most a factor 64 in nside per call (got %d -> %d)" % (nside_in, nside_out))
+        out = self.empty((nmap, 12 * nside_out * nside_out))
+        _check(self.lib.corahip_healpix_block_variance(self.h, self._f64(maps), nmap, nside_in, nside_out, self._f64(out)))
+        return out
+
+    def alm_scale_l(self, alm, lmax, fl, out=None):
+        """a_lm in the device layout [nalm, G, 2, 4] times ``fl[channel, l]``: ``fl`` [nnu, lmax + 1] with
+        ``4 (G - 1) < nnu <= 4 G``, or [lmax + 1] for all ``4 G`` channels (host array or device tensor).  One multiply per
+        component; padding channels are copied.  ``out`` may be ``alm`` itself (in place) but not overlap it in part."""
+        torch = _torch()
+        lmax = int(lmax)
+        nalm = (lmax + 1) * (lmax + 2) // 2
+        if (not isinstance(alm, torch.Tensor) or alm.dim() != 4 or alm.shape[0] != nalm or tuple(alm.shape[2:]) != (2, 4)
+                or alm.dtype != torch.float64 or alm.device != self.device or not alm.is_contiguous() or alm.shape[1] < 1):
+            raise ValueError("alm must be a contiguous float64 [%d, G, 2, 4] tensor on %s" % (nalm, self.device))
+        G = int(alm.shape[1])
+        if not isinstance(fl, torch.Tensor):
+            fl = self.to_device(np.asarray(fl, dtype=np.float64))
+        if fl.dtype != torch.float64 or fl.device != self.device:
+            raise ValueError("fl must be float64 on %s" % (self.device,))
+        if fl.dim() == 1 and fl.shape[0] == lmax + 1:
+            fl = fl[None, :].expand(4 * G, lmax + 1)
+        if fl.dim() != 2 or fl.shape[1] != lmax + 1 or not 4 * (G - 1) < fl.shape[0] <= 4 * G:
+            raise ValueError("fl must be [lmax + 1] or [nnu, lmax + 1] with %d < nnu <= %d (got %r)"
+                             % (4 * (G - 1), 4 * G, tuple(fl.shape)))
+        fl = fl.contiguous()
+        nnu = int(fl.shape[0])
+        out = alm if out is alm else self._out_like(out, alm.shape, "alm_scale_l")
+        nbytes = alm.numel() * 8
+        if out.data_ptr() != alm.data_ptr() and self._overlap(out, nbytes, alm, nbytes):
+            raise ValueError("alm_scale_l: out overlaps alm in part")
+        _check(self.lib.corahip_alm_scale_l(self.h, self._f64(alm), lmax, nnu, self._f64(fl), self._f64(out)))
+        return out
+
+    def galaxy_combine(self, fg, fgs, haslam, sc, am, mv, efreq, skip=2, out=None):
+        """The end of ``ConstrainedGalaxy.getsky`` (cora/foreground/galaxy.py:181-198) in one launch: [nchan - skip, npix],
+        ``S (1 + tanh_lin(((am / mv) (fg - fgs)) / S))`` with ``S = haslam (efreq / 408)^sc`` for the channels from ``skip``.
+
+        fg, fgs : device [nchan, npix]; haslam, sc, am : [npix] (host arrays or device tensors); efreq : host [nchan] in
+        MHz; mv : host float.  ``haslam`` and ``mv`` must be finite and positive (the reference gives NaN otherwise) and
+        ``|sc log(efreq / 408)| < 512``: ValueError before the launch."""
+        torch = _torch()
+        fg, fgs = self._cube(fg, 2, "fg"), self._cube(fgs, 2, "fgs")
+        nchan, npix = int(fg.shape[0]), int(fg.shape[1])
+        self._nside_of(npix)
+        if tuple(fgs.shape) != (nchan, npix):
+            raise ValueError("fgs has shape %r, expected %r" % (tuple(fgs.shape), (nchan, npix)))
+        skip = int(skip)
+        if not 0 <= skip < nchan:
+            raise ValueError("skip must be in [0, %d) (got %d)" % (nchan, skip))
+        efreq = np.asarray(efreq, dtype=np.float64)
+        if efreq.shape != (nchan,) or not (np.all(np.isfinite(efreq)) and np.all(efreq > 0)):
+            raise ValueError("efreq must hold %d finite, positive frequencies" % nchan)
+        mv = float(mv)
+        if not (np.isfinite(mv) and mv > 0 and np.isfinite(1.0 / mv)):
+            raise ValueError("mv must be finite and positive (got %r)" % mv)
+        haslam, sc, am = self._vec(haslam, npix, "haslam"), self._vec(sc, npix, "sc"), self._vec(am, npix, "am")
+        if not bool((torch.isfinite(haslam) & (haslam > 0)).all()):
+            raise ValueError("haslam must be finite and positive")
+        lnr = np.log(efreq / 408.0)
+        if not float(sc.abs().max()) * float(np.abs(lnr).max()) < 512.0:      # (NaN fails too)
+            raise ValueError("sc: |sc log(efreq / 408)| must stay below 512")
+        out = self._out_like(out, (nchan - skip, npix), "galaxy_combine")
+        obytes = out.numel() * 8
+        for t, name in ((fg, "fg"), (fgs, "fgs"), (haslam, "haslam"), (sc, "sc"), (am, "am")):
+            if self._overlap(out, obytes, t, t.numel() * 8):
+                raise ValueError("galaxy_combine: out overlaps %s" % name)
+        if out.data_ptr() % 16:
+            raise ValueError("galaxy_combine: out must be 16-byte aligned")
+        fg, fgs, haslam, sc, am = (t if t.data_ptr() % 16 == 0 else t.clone() for t in (fg, fgs, haslam, sc, am))
+        lnrd = self.to_device(lnr)
+        _check(self.lib.corahip_galaxy_combine(self.h, self._f64(fg), self._f64(fgs), self._f64(haslam), self._f64(sc),
+                                               self._f64(am), 1.0 / mv, self._f64(lnrd), nchan, skip, npix, self._f64(out)))
         return out
 
     def sht_rings(self, nside, lmax):

@@ -238,77 +238,6 @@ __global__ __launch_bounds__(256) void ps_rotate_kernel(const double *__restrict
     }
 }
 
-// ---- NESTED hierarchy --------------------------------------------------------------------------------------------
-
-__device__ static const int PS_JRLL[12] = {2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4};
-__device__ static const int PS_JPLL[12] = {1, 3, 5, 7, 0, 2, 4, 6, 1, 3, 5, 7};
-
-// RING pixel -> (x, y, face): x runs to the north-east, y to the north-west, inside base pixel `face`
-__device__ inline void ring2xyf(const Geom &g, long pixel, long &ix, long &iy, int &face) {
-    const long ns = g.nside, nl2 = 2 * ns;
-    long iring, iphi, kshift, nr;
-    if (pixel < g.ncap) {
-        iring = (1 + isqrt_l(1 + 2 * pixel)) >> 1;
-        iphi = pixel + 1 - 2 * iring * (iring - 1);
-        kshift = 0;
-        nr = iring;
-        face = (int)((iphi - 1) / nr);
-    } else if (pixel < g.npix - g.ncap) {
-        const long ip = pixel - g.ncap;
-        const long tmp = ip / (4 * ns);
-        iring = tmp + ns;
-        iphi = ip - tmp * 4 * ns + 1;
-        kshift = (iring + ns) & 1;
-        nr = ns;
-        const long ire = tmp + 1, irm = nl2 + 1 - tmp;
-        const long ifm = (iphi - (ire >> 1) + ns - 1) / ns, ifp = (iphi - (irm >> 1) + ns - 1) / ns;
-        face = (int)(ifp == ifm ? (ifp | 4) : (ifp < ifm ? ifp : ifm + 8));
-    } else {
-        const long ip = g.npix - pixel;
-        iring = (1 + isqrt_l(2 * ip - 1)) >> 1;
-        iphi = 4 * iring + 1 - (ip - 2 * iring * (iring - 1));
-        kshift = 0;
-        nr = iring;
-        iring = 2 * nl2 - iring;
-        face = 8 + (int)((iphi - 1) / nr);
-    }
-    const long irt = iring - PS_JRLL[face] * ns + 1;
-    long ipt = 2 * iphi - PS_JPLL[face] * nr - kshift - 1;
-    if (ipt >= nl2) ipt -= 8 * ns;
-    ix = (ipt - irt) >> 1;
-    iy = (-ipt - irt) >> 1;
-}
-
-__device__ inline long xyf2ring(const Geom &g, long ix, long iy, int face) {
-    const long ns = g.nside, nl4 = 4 * ns;
-    const long jr = PS_JRLL[face] * ns - ix - iy - 1;
-    long nr, kshift, before;
-    if (jr < ns) {
-        nr = jr;
-        before = 2 * nr * (nr - 1);
-        kshift = 0;
-    } else if (jr > 3 * ns) {
-        nr = nl4 - jr;
-        before = g.npix - 2 * (nr + 1) * nr;
-        kshift = 0;
-    } else {
-        nr = ns;
-        before = g.ncap + (jr - ns) * nl4;
-        kshift = (jr - ns) & 1;
-    }
-    long jp = (PS_JPLL[face] * nr + ix - iy + 1 + kshift) / 2;
-    if (jp > nl4) jp -= nl4;
-    else if (jp < 1) jp += nl4;
-    return before + jp - 1;
-}
-
-// every second bit of j, from bit `from`: the x (from = 0) or y (from = 1) offset of NESTED child j
-__device__ inline long child_offset(long j, int from, int k) {
-    long v = 0;
-    for (int b = 0; b < k; b++) v |= ((j >> (2 * b + from)) & 1L) << b;
-    return v;
-}
-
 // k = log2(nside_out / nside_in): > 0 replicates, < 0 averages 4^-k children, 0 copies
 __global__ __launch_bounds__(256) void ps_udgrade_kernel(Geom gin, Geom gout, int k, const double *__restrict__ in, long nmap,
                                                          double *__restrict__ out) {

@@ -1,11 +1,18 @@
-"""Counterpart of the Gaussian part of cora/foreground/galaxy.py: the full-sky synchrotron
-parameter sets (galaxy.py:20-40), and the body of ``ConstrainedGalaxy.getpolsky`` (galaxy.py:209-344) given its two
-data-derived inputs, the Faraday-width map and the unpolarised sky: :func:`polarised_fraction_device`,
-:func:`polarised_galaxy_device`, :func:`polarised_galaxy`.  ``ConstrainedGalaxy`` itself (``skydata.npz``, healpy
-smoothing, ``getsky``) is not part of this package."""
+"""Counterpart of cora/foreground/galaxy.py: the full-sky synchrotron parameter sets (galaxy.py:20-40),
+:func:`map_variance` and :func:`chunk_var` (:43-83) and :class:`ConstrainedGalaxy` (:86-344), the constrained realisation
+of the galactic synchrotron emission.
+
+``ConstrainedGalaxy.getsky`` runs on the device: the Gaussian maps (``skysim.mkfullsky_device``), the three beam
+smoothings in one batch (``hputil.smoothing_device``), the variance chain (``Context.healpix_block_variance``), the
+last third of the routine in one streaming launch (``Context.galaxy_combine``) and the rotation into celestial
+co-ordinates; ``skysim.mkconstrained`` keeps its per-l eigenproblems on the host.  ``getpolsky`` multiplies that sky by
+the polarised fraction of :func:`polarised_fraction_device` (galaxy.py:209-344; csrc/faraday.hip).  The sky data
+(``skydata.npz``: Haslam map, spectral-index maps, Faraday map) is not part of this package: the class takes the file's
+path or the arrays."""
 import numpy as np
 
 from . import gaussianfg
+from ..core import maps
 
 
 class FullSkySynchrotron(gaussianfg.Synchrotron):
@@ -26,6 +33,45 @@ class FullSkyPolarisedSynchrotron(gaussianfg.Synchrotron):
     nu_0 = 408.0
     l_0 = 100.0
     zeta = 0.04
+
+
+# ---- variance maps (galaxy.py:43-83) -------------------------------------------------------------------------------------
+
+def map_variance(input_map, nside):
+    """Variance of ``input_map`` (RING, one map [npix] or maps [n, npix]) inside every pixel of the coarser resolution
+    ``nside`` (galaxy.py:43-55), RING order.  numpy in, numpy out; a device tensor stays on the device.  One kernel
+    (``Context.healpix_block_variance``: two passes, pairwise sums in NESTED child order) in place of the reference's two
+    reordered copies."""
+    from .. import _lib
+    from ..util import hputil
+
+    host = not hasattr(input_map, "data_ptr")
+    shape = np.shape(input_map) if host else tuple(input_map.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError("map_variance takes one map [npix] or maps [n, npix]")
+    nside_in, nside = hputil.get_nside(input_map), int(nside)
+    for ns in (nside_in, nside):
+        if ns < 1 or ns & (ns - 1):
+            raise ValueError("map_variance: nside must be a power of two (got %d)" % ns)
+    if nside > nside_in or nside_in > 64 * nside:
+        raise ValueError("map_variance takes a factor 1 to 64 in nside per call (got %d -> %d)" % (nside_in, nside))
+    ctx = _lib.get_context()
+    m = ctx.to_device(np.asarray(input_map, dtype=np.float64)) if host else input_map
+    out = ctx.healpix_block_variance(m.reshape(-1, shape[-1]).contiguous(), nside)
+    out = out[0] if len(shape) == 1 else out
+    return out.cpu().numpy() if host else out
+
+
+def chunk_var(a):
+    """Variance of all elements of the (real or complex) host array ``a``, ``sum |a - mean|^2 / a.size``, accumulated
+    over at most 30 pieces so that no temporary of the array's size is made (galaxy.py:58-83).  The device arrays of
+    ``getpolsky`` go through the fixed-order ``Context.complex_variance`` instead."""
+    a = np.asarray(a)
+    mean = a.mean()
+    total = 0.0
+    for piece in np.array_split(a.ravel(), min(30, a.size)):
+        total += np.sum(np.abs(piece - mean) ** 2)
+    return total / a.size
 
 
 # ---- polarised emission: Faraday-depth synthesis (galaxy.py:209-344; csrc/faraday.hip) -------------------------------
@@ -213,3 +259,176 @@ def polarised_galaxy(intensity, sigma_phi, freq, nside, rng=None, celestial=True
     if kw.get("debug", False):
         return (_lib.get_context().to_host(res[0]),) + tuple(res[1:])
     return _lib.get_context().to_host(res)
+
+
+# ---- the constrained galaxy (galaxy.py:86-344) ---------------------------------------------------------------------------
+
+_SPECTRAL_KEYS = ("gsm", "md", "gd")
+
+
+class ConstrainedGalaxy(maps.Sky3d):
+    """Realistic simulations of the galactic synchrotron sky, constrained to the Haslam map (galaxy.py:86-344).
+
+    Attributes
+    ----------
+    spectral_map : one of ['gsm', 'md', 'gd']
+        Which spectral index map to use: ``gsm`` a GSM-derived map (two constraints, at 408 and 1420 MHz), ``md`` the
+        map of Miville-Deschenes et al. 2008 (default), ``gd`` that of Giardino et al. 2002.
+
+    Parameters
+    ----------
+    skydata : path of an ``.npz`` with the arrays ``haslam``, ``spectral_gsm``, ``spectral_md``, ``spectral_gd`` and
+        ``faraday`` (the reference's ``skydata.npz``, which is not part of this package), or
+    haslam, spectral, faraday : the arrays themselves, RING maps; ``spectral`` a dict keyed 'gsm' | 'md' | 'gd' or one map,
+        used for whichever key ``spectral_map`` selects; ``faraday`` is needed by ``getpolsky`` only.
+    amp_nside : resolution of the amplitude map (an extension: the reference hard-codes 512).
+    """
+
+    spectral_map = "md"
+
+    _dphi = 1.0
+    _maxphi = 500.0
+
+    def __init__(self, skydata=None, haslam=None, spectral=None, faraday=None, amp_nside=512):
+        from .. import _lib
+        from ..util import hputil
+
+        if skydata is not None:
+            with np.load(skydata) as f:
+                haslam = f["haslam"]
+                spectral = {k: f["spectral_" + k] for k in _SPECTRAL_KEYS}
+                faraday = f["faraday"]
+        if haslam is None or spectral is None:
+            raise ValueError("ConstrainedGalaxy: the sky data file is not part of cora_amd: pass skydata=FILE.npz "
+                             "(arrays haslam, spectral_md, spectral_gsm, spectral_gd, faraday) or the arrays haslam, spectral")
+        self._haslam = self._ring_map(haslam, "haslam")
+        if not (np.all(np.isfinite(self._haslam)) and np.all(self._haslam > 0)):
+            raise ValueError("haslam must be finite and positive")
+        if isinstance(spectral, dict):
+            bad = sorted(set(spectral) - set(_SPECTRAL_KEYS))
+            if bad or not spectral:
+                raise ValueError("spectral must be keyed by 'gsm', 'md', 'gd' (got %r)" % (sorted(spectral),))
+            self._sp_ind = {k: self._ring_map(v, "spectral[%r]" % k) for k, v in spectral.items()}
+        else:
+            one = self._ring_map(spectral, "spectral")
+            self._sp_ind = {k: one for k in _SPECTRAL_KEYS}
+        self._faraday = None if faraday is None else self._ring_map(faraday, "faraday")
+        amp_nside = int(amp_nside)
+        if amp_nside < 1 or amp_nside & (amp_nside - 1):
+            raise ValueError("amp_nside must be a power of two (got %d)" % amp_nside)
+        if hputil.get_nside(self._haslam) < 16:
+            raise ValueError("haslam must have nside >= 16: its variance is taken inside the pixels of nside 16")
+
+        # galaxy.py:109-111
+        ctx = _lib.get_context()
+        vm = map_variance(hputil.smoothing_device(ctx.to_device(self._haslam[None]), sigma=np.radians(0.5)), 16)
+        self._amp_map = hputil.smoothing_device(hputil.ud_grade(vm.sqrt(), amp_nside), sigma=np.radians(2.0))[0]
+
+    @staticmethod
+    def _ring_map(m, name):
+        from ..util import hputil
+
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        if m.ndim != 1:
+            raise ValueError("%s must be one RING map [npix] (got shape %r)" % (name, m.shape))
+        nside = hputil.get_nside(m)
+        if nside & (nside - 1):
+            raise ValueError("%s: nside must be a power of two (got %d)" % (name, nside))
+        return m
+
+    def _spectral(self):
+        if self.spectral_map not in self._sp_ind:
+            raise ValueError("spectral_map %r: no such spectral index map was given" % (self.spectral_map,))
+        return self._sp_ind[self.spectral_map]
+
+    def getsky_device(self, debug=False, celestial=True, rng=None):
+        """A realisation of the unpolarised sky on the device, [nfreq, npix] (galaxy.py:133-207).
+
+        debug : also return the intermediate products ``(fgt, fg, fgs, fgsmooth, am, mv)`` as the reference does.
+        celestial : rotate the maps from galactic into celestial co-ordinates.
+        rng : as for ``Sky3d.getsky`` (an extension): the maps have the reference's distribution, not numpy's sequence
+            of numbers.
+        """
+        import torch
+
+        from .. import _lib
+        from ..core import skysim
+        from ..util import hputil
+
+        nside = int(self.nside)
+        if nside < 32:
+            raise ValueError("ConstrainedGalaxy needs nside >= 32 (got %d): the fluctuations are scaled by their variance "
+                             "inside the pixels of nside 16, which is zero below" % nside)
+        ctx = _lib.get_context()
+        spectral = self._spectral()
+        syn = FullSkySynchrotron()
+        lmax = 3 * nside - 1
+        efreq = np.concatenate((np.array([408.0, 1420.0]), np.asarray(self.nu_pixels, dtype=np.float64)))
+
+        # the random fluctuations
+        cla = skysim.clarray(syn.angular_powerspectrum, lmax, efreq, zromb=0)
+        fg = skysim.mkfullsky_device(cla, nside, rng=rng)
+
+        # the three smoothings of galaxy.py:160-161 and :176 in one batch: fg[0] at fwhm 1 deg, fg[1] at fwhm 5.8 deg,
+        # fg[0] at sigma 0.5 deg
+        beams = np.stack([hputil.gauss_beam(np.radians(1.0), lmax), hputil.gauss_beam(np.radians(5.8), lmax),
+                          hputil.gauss_beam(np.radians(0.5) * np.sqrt(8.0 * np.log(2.0)), lmax)])
+        sm = hputil.smoothing_device(fg[[0, 1, 0]], fl=beams)
+
+        # maps constrained to the smoothed ones: at both frequencies (GSM) or at the Haslam frequency alone
+        sub = ctx.to_host(sm[:2])
+        cons = [(0, sub[0]), (1, sub[1])] if self.spectral_map == "gsm" else [(0, sub[0])]
+        fgs = ctx.to_device(skysim.mkconstrained(cla, cons, nside))
+
+        haslam = hputil.ud_grade(ctx.to_device(self._haslam), nside)
+        sc = hputil.ud_grade(ctx.to_device(spectral), nside)
+        am = hputil.ud_grade(self._amp_map, nside)
+
+        # the variance of the fluctuations on the scale of the variance map; the mean over the sphere is the mean of the
+        # 12 base-pixel means (ud_grade's fixed pairwise order), added up in order on the host
+        vm = hputil.smoothing_device(map_variance(sm[2:3], 16).sqrt(), sigma=np.radians(2.0))
+        mv = sum(ctx.to_host(hputil.ud_grade(vm, 1))[0].tolist()) / 12.0
+
+        fgt = ctx.galaxy_combine(fg, fgs, haslam, sc, am, mv, efreq, skip=2)
+        if celestial:
+            fgt = hputil.rotate_map_device(fgt, hputil.coord_matrix("C", "G"))
+        if debug:
+            fgsmooth = haslam[None, :] * torch.pow(ctx.to_device(efreq / 408.0)[:, None], sc[None, :])
+            return fgt, fg, fgs, fgsmooth, am, mv
+        return fgt
+
+    def getsky(self, debug=False, celestial=True, rng=None):
+        """:meth:`getsky_device` delivered to the host: ndarray [nfreq, npix] (with ``debug`` the reference's tuple, its
+        arrays on the host)."""
+        from .. import _lib
+
+        res = self.getsky_device(debug=debug, celestial=celestial, rng=rng)
+        ctx = _lib.get_context()
+        if debug:
+            return tuple(ctx.to_host(r) for r in res[:5]) + (res[5],)
+        return ctx.to_host(res)
+
+    def getpolsky_device(self, debug=False, celestial=True, rng=None):
+        """A realisation of the polarised sky on the device, [nfreq, 4, npix] (galaxy.py:209-344): the unpolarised sky
+        times the polarised fraction of :func:`polarised_galaxy_device`, whose Faraday width is the smoothed ``|faraday|``
+        map.  ``debug``: the tuple of :func:`polarised_galaxy_device`."""
+        from .. import _lib
+        from ..util import hputil
+
+        if self._faraday is None:
+            raise ValueError("getpolsky needs the Faraday rotation map: pass faraday= (or skydata=) to ConstrainedGalaxy")
+        ctx = _lib.get_context()
+        sigma_phi = hputil.ud_grade(
+            hputil.smoothing_device(ctx.to_device(np.abs(self._faraday)[None]), fwhm=np.radians(10.0)), int(self.nside))[0]
+        return polarised_galaxy_device(self.getsky_device(celestial=False, rng=rng), ctx.to_host(sigma_phi), self.nu_pixels,
+                                       self.nside, rng=rng, celestial=celestial, dphi=self._dphi, maxphi=self._maxphi,
+                                       debug=debug)
+
+    def getpolsky(self, debug=False, celestial=True, rng=None):
+        """:meth:`getpolsky_device` delivered to the host: ndarray [nfreq, 4, npix]."""
+        from .. import _lib
+
+        res = self.getpolsky_device(debug=debug, celestial=celestial, rng=rng)
+        if debug:
+            return (_lib.get_context().to_host(res[0]),) + tuple(res[1:])
+        return _lib.get_context().to_host(res)

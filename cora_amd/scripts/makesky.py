@@ -3,9 +3,9 @@
 Mirrors the command-line surface of cora/scripts/makesky.py: the frequency-channelisation options
 (``FreqState``, :44-198), the map options (``--nside --pol --filename``, :170-198), the ``21cm``
 (:313-345), ``gaussianfg`` (:348-390), ``pointsource`` (:283-310) and ``singlesource`` (:393-409) commands and the map
-container written by ``write_map`` (:412-450).  The ``foreground`` / ``galaxy`` commands need the constrained-galaxy
-model (data-file driven, healpy smoothing), which is not part of this package: they exist here so that scripts fail
-with a clear message rather than "no such command".
+container written by ``write_map`` (:412-450).  The ``foreground`` / ``galaxy`` commands (:215-280) run the constrained
+galaxy of ``cora_amd.foreground.galaxy``; its sky data file does not ship with this package, so they take it from
+``--skydata FILE.npz`` and refuse to run without.
 
     python -m cora_amd.scripts.makesky 21cm --nside 256 --freq 400 800 64 --freq-mode edge --pol none --filename m.h5
 """
@@ -119,29 +119,92 @@ def map_options(f):
 
 @click.group()
 def cli():
-    """Generate a map of the low frequency radio sky (MI355X build: Gaussian components)."""
+    """Generate a map of the low frequency radio sky (MI355X build)."""
 
 
-def _not_in_scope(name):
-    raise click.ClickException(
-        "'%s' needs cora's constrained-galaxy / point-source catalogue models, which are not part of cora_amd "
-        "(Gaussian-sky hot path only); use the reference package for this component." % name)
+def _galaxy_of(fstate, nside, skydata):
+    """The ``ConstrainedGalaxy`` of the two galactic commands, or their refusal without the sky data."""
+    if skydata is None:
+        raise click.ClickException(
+            "the constrained galaxy needs the Haslam, spectral-index and Faraday maps, and the sky data file is not part of "
+            "cora_amd: pass --skydata FILE.npz (arrays haslam, spectral_md, spectral_gsm, spectral_gd, faraday)")
+    from ..foreground import galaxy as galaxy_mod
+
+    try:
+        gal = galaxy_mod.ConstrainedGalaxy(skydata=skydata)
+    except (KeyError, ValueError) as e:
+        raise click.ClickException("--skydata %s: %s" % (skydata, e))
+    gal.nside = nside
+    gal.frequencies = fstate.frequencies
+    return gal
+
+
+_SKYDATA_OPTIONS = [
+    (("--skydata",), dict(type=click.Path(exists=True, dir_okay=False), default=None,
+                          help="The sky data of the galaxy model as an .npz file (arrays haslam, spectral_md, spectral_gsm, "
+                               "spectral_gd, faraday; RING order).  Required: the file is not part of cora_amd.")),
+    (("--seed",), dict(type=int, default=None, help="Seed of the numpy Generator (cora_amd extension).")),
+]
+
+
+def galaxy_options(f):
+    for names, kw in _SKYDATA_OPTIONS:
+        f = click.option(*names, **kw)(f)
+    return f
 
 
 @cli.command()
 @map_options
-@click.option("--maxflux", default=1e6, type=float)
-def foreground(fstate, nside, pol, filename, maxflux):
-    """Full foreground sky (galaxy + point sources): not available in cora_amd."""
-    _not_in_scope("foreground")
+@click.option("--maxflux", default=1e6, type=float,
+              help="Maximum flux of point included point source (in Jy). Default is 1 MJy.")
+@click.option("--catalogue", type=click.Path(exists=True, dir_okay=False), default=None,
+              help="Table of the real sources above 4 Jy (as for pointsource); without it that component is left out.")
+@click.option("--faraday-map", type=click.Path(exists=True, dir_okay=False), default=None,
+              help="Rotation-measure map for the point sources as a .npy file; default: the faraday array of --skydata.")
+@galaxy_options
+def foreground(fstate, nside, pol, filename, maxflux, catalogue, faraday_map, skydata, seed):
+    """Generate a full foreground sky map (galaxy + point sources).
+
+    The requested map must have more than two frequencies for this type.
+    """
+    if fstate.frequencies.shape[0] < 2:
+        print("Number of frequencies must be more than two.")
+        return
+
+    from ..foreground import pointsource as ps_mod
+
+    gal = _galaxy_of(fstate, nside, skydata)
+    rng = np.random.default_rng(seed) if seed is not None else None
+    cs = gal.getpolsky(rng=rng) if pol == "full" else gal.getsky(rng=rng)
+
+    rm = np.load(faraday_map) if faraday_map is not None else (gal._faraday if pol == "full" else None)
+    ps = ps_mod.CombinedPointSources.like_map(gal, catalogue=catalogue, faraday_map=rm)
+    ps.flux_max = maxflux
+    cs = cs + (ps.getpolsky(rng=rng) if pol == "full" else ps.getsky(rng=rng))
+    write_map(filename, cs, gal.frequencies, fstate.freq_width, pol != "none")
 
 
 @cli.command()
 @map_options
 @click.option("--spectral-index", default="md", type=click.Choice(["md", "gsm", "gd"]))
-def galaxy(fstate, nside, pol, filename, spectral_index):
-    """Milky way only foreground map: not available in cora_amd."""
-    _not_in_scope("galaxy")
+@galaxy_options
+def galaxy(fstate, nside, pol, filename, spectral_index, skydata, seed):
+    """Generate a Milky way only foreground map.
+
+    Use Haslam (extrapolated with a spatially varying spectral index) as a base, and then generate random spatial,
+    spectral and polarisation fluctuations for unconstrained modes.
+
+    The requested map must have more than two frequencies for this type.
+    """
+    if fstate.frequencies.shape[0] < 2:
+        print("Number of frequencies must be more than two.")
+        return
+
+    gal = _galaxy_of(fstate, nside, skydata)
+    gal.spectral_map = spectral_index
+    rng = np.random.default_rng(seed) if seed is not None else None
+    cs = gal.getpolsky(rng=rng) if pol == "full" else gal.getsky(rng=rng)
+    write_map(filename, cs, gal.frequencies, fstate.freq_width, pol != "none")
 
 
 @cli.command()

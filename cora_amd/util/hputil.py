@@ -670,6 +670,161 @@ def ud_grade(map_in, nside_out):
     return out.cpu().numpy() if host else out
 
 
+# ------------------------------------------------------------------------------------
+# RING <-> NESTED, Gaussian-beam smoothing: healpy.reorder / ring2nest / nest2ring / gauss_beam / smoothing
+# (csrc/galaxy.hip).  Restated from the published definitions (Gorski et al. 2005, section 4.1; a Gaussian beam of
+# width sigma multiplies a_lm by exp(-l (l + 1) sigma^2 / 2)) and pinned by their properties and a numpy oracle
+# (tests/_galaxy_oracle.py), not by healpy's output.
+# ------------------------------------------------------------------------------------
+_FACE_RING = np.array([2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4])       # ring of a base pixel's northern corner, in nside
+_FACE_PHI = np.array([1, 3, 5, 7, 0, 2, 4, 6, 1, 3, 5, 7])        # its longitude, in units of pi / 4
+
+
+def get_nside(m):
+    """``healpy.get_nside``: the nside of one map [npix] or of maps [n, npix]."""
+    return _npix2nside(np.shape(m)[-1])
+
+
+def _order_of(nside, what):
+    nside = int(nside)
+    if nside < 1 or nside & (nside - 1) or nside > 8192:
+        raise ValueError("%s: nside must be a power of two up to 8192 (got %d)" % (what, nside))
+    return nside, nside.bit_length() - 1
+
+
+def _index_array(nside, ipix, what):
+    ipix = np.asarray(ipix)
+    if ipix.dtype.kind not in "iu":
+        raise ValueError("%s takes integer pixel indices" % what)
+    ipix = ipix.astype(np.int64)
+    if ipix.size and (ipix.min() < 0 or ipix.max() >= nside2npix(nside)):
+        raise ValueError("pixel index out of range for nside %d" % nside)
+    return ipix
+
+
+def _bits(v, k, src_step, dst_step):
+    """Bit ``src_step b`` of ``v`` moved to place ``dst_step b``, b < k."""
+    out = np.zeros_like(v)
+    for b in range(k):
+        out |= ((v >> (src_step * b)) & 1) << (dst_step * b)
+    return out
+
+
+def nest2ring(nside, ipix):
+    """``healpy.nest2ring``: RING index of NESTED pixels (host index arrays).  A NESTED index is
+    ``face nside^2 + (bits of x on the even places, bits of y on the odd places)``; the pixel (x, y) of a face lies on
+    ring ``jr = face_ring nside - x - y - 1`` at the position that ``x - y`` fixes."""
+    nside, k = _order_of(nside, "nest2ring")
+    ipix = _index_array(nside, ipix, "nest2ring")
+    face, rest = ipix >> (2 * k), ipix & (nside * nside - 1)
+    ix, iy = _bits(rest, k, 2, 1), _bits(rest >> 1, k, 2, 1)
+    jr = _FACE_RING[face] * nside - ix - iy - 1
+    nr = np.where(jr < nside, jr, np.where(jr > 3 * nside, 4 * nside - jr, nside))           # pixels per quarter ring
+    first = np.where(jr < nside, 2 * nr * (nr - 1),
+                     np.where(jr > 3 * nside, 12 * nside * nside - 2 * nr * (nr + 1), 2 * nside * (nside - 1) + (jr - nside) * 4 * nside))
+    shift = np.where((jr >= nside) & (jr <= 3 * nside), (jr - nside) & 1, 0)
+    jp = (_FACE_PHI[face] * nr + ix - iy + 1 + shift) // 2
+    jp = np.where(jp > 4 * nside, jp - 4 * nside, np.where(jp < 1, jp + 4 * nside, jp))
+    out = first + jp - 1
+    return out if out.ndim else int(out)
+
+
+_r2n_cache = {}
+
+
+def ring2nest(nside, ipix):
+    """``healpy.ring2nest``: NESTED index of RING pixels (host index arrays): the inverse permutation of
+    :func:`nest2ring`, tabulated once per nside."""
+    nside, _ = _order_of(nside, "ring2nest")
+    ipix = _index_array(nside, ipix, "ring2nest")
+    table = _r2n_cache.get(nside)
+    if table is None:
+        npix = nside2npix(nside)
+        table = np.empty(npix, dtype=np.int64)
+        table[nest2ring(nside, np.arange(npix))] = np.arange(npix)
+        if nside <= 256:                                   # 6 MB at most; larger tables are rebuilt per call
+            _r2n_cache[nside] = table
+    out = table[ipix]
+    return out if out.ndim else int(out)
+
+
+def reorder(map_in, inp=None, out=None, r2n=None, n2r=None):
+    """``healpy.reorder`` for one map [npix] or maps [n, npix]: ``r2n=True`` (or ``inp='RING', out='NESTED'``) RING ->
+    NESTED, ``n2r=True`` (or ``inp='NESTED', out='RING'``) the other way; equal orderings return a copy.  numpy in,
+    numpy out; a device tensor stays on the device (corahip_healpix_reorder).  nside a power of two."""
+    if r2n and n2r:
+        raise ValueError("reorder: r2n and n2r are exclusive")
+    if r2n:
+        inp, out = "RING", "NESTED"
+    if n2r:
+        inp, out = "NESTED", "RING"
+    names = {"RING": "RING", "NEST": "NESTED", "NESTED": "NESTED"}
+    if not isinstance(inp, str) or not isinstance(out, str) or inp.upper() not in names or out.upper() not in names:
+        raise ValueError("reorder: inp and out must be 'RING' or 'NESTED' (or pass r2n / n2r)")
+    inp, out = names[inp.upper()], names[out.upper()]
+    host = not hasattr(map_in, "data_ptr")
+    shape = np.shape(map_in) if host else tuple(map_in.shape)
+    if len(shape) not in (1, 2):
+        raise ValueError("reorder takes one map [npix] or maps [n, npix]")
+    _order_of(_npix2nside(shape[-1]), "reorder")
+    if inp == out:
+        return np.array(map_in, dtype=np.float64) if host else map_in.clone()
+    ctx = _lib.get_context()
+    m = ctx.to_device(np.asarray(map_in, dtype=np.float64)) if host else map_in
+    res = ctx.healpix_reorder(m.reshape(-1, shape[-1]).contiguous(), inp == "RING").reshape(shape)
+    return res.cpu().numpy() if host else res
+
+
+def gauss_beam(fwhm, lmax):
+    """``healpy.gauss_beam(fwhm, lmax)`` for temperature: ``exp(-l (l + 1) sigma^2 / 2)``, ``sigma = fwhm / sqrt(8 ln 2)``,
+    l = 0 .. lmax (fwhm in radians)."""
+    sigma = float(fwhm) / np.sqrt(8.0 * np.log(2.0))
+    ell = np.arange(int(lmax) + 1, dtype=np.float64)
+    return np.exp(-0.5 * ell * (ell + 1.0) * (sigma * sigma))
+
+
+def _beams(n, lmax, fl, fwhm, sigma):
+    """[n, lmax + 1] transfer functions of ``smoothing_device`` from ``fl``, or ``sigma``, or ``fwhm`` (in that order)."""
+    if fl is not None:
+        fl = np.asarray(fl, dtype=np.float64)
+        if fl.shape != (n, lmax + 1):
+            raise ValueError("fl has shape %r, expected %r" % (fl.shape, (n, lmax + 1)))
+        return fl
+    width = np.asarray(0.0 if fwhm is None else fwhm, dtype=np.float64) if sigma is None \
+        else np.asarray(sigma, dtype=np.float64) * np.sqrt(8.0 * np.log(2.0))
+    if width.ndim > 1 or (width.ndim == 1 and width.shape[0] != n):
+        raise ValueError("fwhm / sigma must be a scalar or one value per map (%d)" % n)
+    return np.stack([gauss_beam(w, lmax) for w in np.broadcast_to(width, (n,))])
+
+
+def smoothing_device(maps, fl=None, fwhm=None, sigma=None, lmax=None, niter=3, use_weights=False):
+    """``healpy.smoothing`` with its defaults (``iter=3``, no ring weights, ``lmax = 3 nside - 1``) for device maps
+    [n, npix]: :func:`map2alm_device`, ``Context.alm_scale_l`` and ``Context.alm2map``, all maps in one batch.  ``fwhm``
+    or ``sigma`` (radians): a scalar, or one value per map; ``fl`` [n, lmax + 1] overrides both."""
+    if maps.dim() != 2:
+        raise ValueError("maps must be [n, npix]")
+    n, nside = int(maps.shape[0]), _npix2nside(maps.shape[1])
+    lmax = 3 * nside - 1 if lmax is None else int(lmax)
+    beams = _beams(n, lmax, fl, fwhm, sigma)
+    ctx = _lib.get_context()
+    alm = map2alm_device(maps.contiguous(), nside, lmax, use_weights=use_weights, niter=niter)
+    ctx.alm_scale_l(alm, lmax, beams, out=alm)
+    return ctx.alm2map(alm, nside, lmax, n)
+
+
+def smoothing(map_in, fwhm=0.0, sigma=None, lmax=None, iter=3, use_weights=False):
+    """``healpy.smoothing`` for one temperature map [npix] or maps [n, npix]: numpy in, numpy out
+    (:func:`smoothing_device`)."""
+    m = np.asarray(map_in, dtype=np.float64)
+    if m.ndim not in (1, 2):
+        raise ValueError("smoothing takes one map [npix] or maps [n, npix]")
+    _npix2nside(m.shape[-1])
+    ctx = _lib.get_context()
+    out = smoothing_device(ctx.to_device(m.reshape(-1, m.shape[-1])), fwhm=fwhm, sigma=sigma, lmax=lmax, niter=iter,
+                           use_weights=use_weights)
+    return ctx.to_host(out).reshape(m.shape)
+
+
 # J2000 constants of the coordinate systems (IAU 1958 galactic system transformed to J2000, as in the Hipparcos
 # catalogue vol. 1 sec. 1.5.3; mean obliquity of the IAU 1976 system): degrees
 GAL_POLE_RA, GAL_POLE_DEC, GAL_LON_NCP = 192.85948, 27.12825, 122.93192

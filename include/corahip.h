@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -671,6 +671,35 @@ int corahip_polarise_rotate(corahip_ctx *ctx, const double *intensity, const dou
 int corahip_faraday_rotate(corahip_ctx *ctx, double *polmap, const double *rm, const double *wv, int nfreq, int npol,
                            long npix);
 int corahip_healpix_ud_grade(corahip_ctx *ctx, const double *maps, long nmap, int nside_in, int nside_out, double *out);
+
+/* ---- constrained galaxy (cora/foreground/galaxy.py:43-55, :109-111, :147-207; csrc/galaxy.hip) ------------------------
+ * All FP64, no atomics, one writer per element: the same bits from call to call.  Maps are [nmap, npix] row-major.
+ * healpix_reorder: healpy.reorder between RING and NESTED for nside a power of two up to 8192; r2n != 0: maps in RING order
+ *            -> out in NESTED order, r2n == 0: the other way.  A gather, out[i, q] = maps[i, p(q)], with the pixel map computed
+ *            in the kernel (NESTED pixel = face nside^2 + the bits of x on the even places and of y on the odd ones, Gorski et
+ *            al. 2005 section 4.1).  out must not overlap maps.
+ * healpix_block_variance: map_variance (:43-55) without its two reordered copies: out[i, P], P a RING pixel at nside_out, is
+ *            numpy's var (ddof 0) of the (nside_in / nside_out)^2 children of P in maps[i] (RING, nside_in).  Two passes, the
+ *            mean and then the mean of the squared deviations, both summed over the balanced binary tree of the NESTED child
+ *            order (healpix_ud_grade's tree): a block of equal values has variance exactly 0, and nside_out = nside_in gives
+ *            zeros.  Up to 16 children a lane owns an output pixel, from 64 a wave does; the bits do not depend on which.
+ *            nside_in <= 64 nside_out (EINVAL beyond).  out [nmap, npix_out] must not overlap maps.
+ * alm_scale_l: out = alm fl[channel, l] for a_lm in the device layout [nalm][ceil(nnu / 4)][re, im][4] (packed index
+ *            m (2 lmax + 1 - m) / 2 + l) and fl [nnu, lmax + 1] real: what healpy.smoothing / almxfl do between analysis and
+ *            synthesis, for all channels at once.  One multiply per component: the host product, bit for bit.  The padding
+ *            channels of the last group are copied.  out == alm (in place) is allowed, a partial overlap is not.
+ * galaxy_combine: the end of ConstrainedGalaxy.getsky (:181-198) in one launch.  fg, fgs [nchan, npix]; haslam, sc, am [npix];
+ *            lnr [nchan] = log(efreq / 408) from the host; inv_mv = 1 / mv.  For c >= skip:
+ *              S = haslam[p] exp(sc[p] lnr[c]),  x = ((am[p] inv_mv) (fg[c, p] - fgs[c, p])) / S,
+ *              out[c - skip, p] = S (1 + (x < 0 ? tanh(x) : x)),
+ *            every operation rounded once, in this order (no contraction); exp is glibc's (< 1 ulp, |sc lnr| < 512 is the
+ *            caller's to ensure), tanh the device library's.  haslam must be positive (not checked here).  npix even, all
+ *            map pointers 16-byte aligned; out [nchan - skip, npix] must not overlap an input.                        */
+int corahip_healpix_reorder(corahip_ctx *ctx, const double *maps, long nmap, int nside, int r2n, double *out);
+int corahip_healpix_block_variance(corahip_ctx *ctx, const double *maps, long nmap, int nside_in, int nside_out, double *out);
+int corahip_alm_scale_l(corahip_ctx *ctx, const double *alm, int lmax, int nnu, const double *fl, double *out);
+int corahip_galaxy_combine(corahip_ctx *ctx, const double *fg, const double *fgs, const double *haslam, const double *sc,
+                           const double *am, double inv_mv, const double *lnr, int nchan, int skip, long npix, double *out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
