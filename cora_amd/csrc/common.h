@@ -136,6 +136,34 @@ struct StageTimer {
 
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
+// ---- host-side launch helpers of the streaming entry points (the K1-K5 launches are tuned per kernel, not these) ----
+
+// blocks of 256 threads for a grid-stride kernel over n elements: ceil(n / 256), at most per_cu per CU, at least 1
+static inline unsigned grid_blocks(const corahip_ctx *ctx, long n, int per_cu = 16) {
+    long blocks = (n + 255) / 256;
+    const long cap = (long)ctx->num_cu * per_cu;
+    if (blocks > cap) blocks = cap;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte?  A null pointer (an optional argument left out) overlaps
+// nothing.  The guard changes no accepted call of the entry points that used to test without it: a null b "overlapped"
+// only an a below nb, and a real device pointer is never smaller than a buffer length.
+static inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+
+// log2 of a power of two, -1 for anything else
+static inline int log2_exact(int v) {
+    int k = 0;
+    while ((1 << k) < v) k++;
+    return (1 << k) == v ? k : -1;
+}
+
+// p on a multiple of `bytes` (a power of two); true for a null pointer
+static inline bool is_aligned(const void *p, unsigned bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+
 __host__ __device__ static inline long nalm_of(int lmax) { return (long)(lmax + 1) * (lmax + 2) / 2; }
 // healpy packed index (m-major): idx(l,m) = m(2 lmax+1-m)/2 + l
 __host__ __device__ static inline long alm_idx(int l, int m, int lmax) {

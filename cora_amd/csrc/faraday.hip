@@ -269,18 +269,13 @@ faraday_pack_kernel(const double *__restrict__ maps, int R, long npix, long ld, 
     }
 }
 
-inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 extern "C" {
 
 int corahip_complex_variance(corahip_ctx *ctx, const double *y, long count, double *out2) {
     ARG_CHECK(ctx && y && out2 && count >= 1);
-    ARG_CHECK(((uintptr_t)y & 15) == 0 && ((uintptr_t)out2 & 7) == 0);
+    ARG_CHECK(is_aligned(y, 16) && is_aligned(out2, 8));
     ARG_CHECK(!overlaps(out2, 3 * sizeof(double), y, (size_t)count * 16));
     int nb;
     long per;
@@ -305,9 +300,9 @@ int corahip_faraday_mix(corahip_ctx *ctx, const double *y, long ncol, int nphi, 
                         const double *A, int nfreq, double scale, const double *intensity, double *out) {
     ARG_CHECK(ctx && y && phi && sigma && A && out);
     ARG_CHECK(ncol >= 1 && nfreq >= 1 && nphi >= 2 && (nphi & 1) == 0);
-    ARG_CHECK(((uintptr_t)y & 15) == 0 && ((uintptr_t)A & 15) == 0);
-    ARG_CHECK(((uintptr_t)phi & 7) == 0 && ((uintptr_t)sigma & 7) == 0 && ((uintptr_t)intensity & 7) == 0);
-    ARG_CHECK(((uintptr_t)out & (intensity ? 7 : 15)) == 0);
+    ARG_CHECK(is_aligned(y, 16) && is_aligned(A, 16));
+    ARG_CHECK(is_aligned(phi, 8) && is_aligned(sigma, 8) && is_aligned(intensity, 8));
+    ARG_CHECK(is_aligned(out, intensity ? 8 : 16));
     const size_t ybytes = (size_t)ncol * (size_t)nphi * 16, abytes = (size_t)nfreq * (size_t)nphi * 16;
     const size_t tbytes = (size_t)nfreq * (size_t)ncol * 8;
     const size_t obytes = intensity ? 4 * tbytes : 2 * tbytes;
@@ -330,7 +325,7 @@ int corahip_faraday_mix(corahip_ctx *ctx, const double *y, long ncol, int nphi, 
 
 int corahip_faraday_pack(corahip_ctx *ctx, const double *maps, int nchunk, long npix, int k0, int nphi, double *y) {
     ARG_CHECK(ctx && maps && y && nchunk >= 1 && npix >= 1 && k0 >= 0 && nphi >= 1 && (long)k0 + nchunk <= nphi);
-    ARG_CHECK(((uintptr_t)maps & 7) == 0 && ((uintptr_t)y & 7) == 0);
+    ARG_CHECK(is_aligned(maps, 8) && is_aligned(y, 8));
     ARG_CHECK(!overlaps(y, (size_t)npix * (size_t)nphi * 16, maps, (size_t)nchunk * 2 * (size_t)npix * 8));
     const int R = 2 * nchunk;
     const long nrb = (R + 31) / 32, npb = (npix + 31) / 32;

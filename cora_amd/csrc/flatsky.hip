@@ -751,10 +751,7 @@ int corahip_randomfield_draw(corahip_ctx *ctx, const double *kweight, int64_t co
     ARG_CHECK(ctx && kweight && spec && count >= 0);
     if (count == 0) return 0;
     StageTimer st(ctx, "flatdraw");
-    long blocks = (count + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(randomfield_draw_kernel, dim3((int)blocks), dim3(256), 0, ctx->stream, kweight, (long)count,
+    hipLaunchKernelGGL(randomfield_draw_kernel, dim3(grid_blocks(ctx, count)), dim3(256), 0, ctx->stream, kweight, (long)count,
                        seed, reinterpret_cast<double2 *>(spec));
     LAUNCH_CHECK();
     return 0;
@@ -776,10 +773,7 @@ int corahip_spec_mul_real(corahip_ctx *ctx, double *spec, const double *weight, 
     ARG_CHECK(ctx && spec && weight && count >= 0);
     if (count == 0) return 0;
     StageTimer st(ctx, "spec_mul");
-    long blocks = (count + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(spec_mul_real_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(spec_mul_real_kernel, dim3(grid_blocks(ctx, count)), dim3(256), 0, ctx->stream,
                        reinterpret_cast<double2 *>(spec), weight, (long)count);
     LAUNCH_CHECK();
     return 0;

@@ -3,13 +3,14 @@
 // third of getsky (:181-198) as one streaming launch.
 //
 //   gx_reorder_kernel      RING <-> NESTED gather, out[i, q] = in[i, p(q)], one lane per output pixel and the pixel map
-//                          computed in the lane (healpix_geom.h): no index array in memory.  NESTED pixel
-//                          q = face nside^2 + (x bits on the even places, y bits on the odd ones).
+//                          computed in the lane (nest2ring_dev / ring2nest_dev of healpix_geom.h): no index array in
+//                          memory.
 //   gx_blockvar_kernel     out[i, P] = numpy var (ddof 0) of the 4^k children of RING pixel P at nside_out, two passes:
 //                          the mean, then the mean of the squared deviations (never E[x^2] - E[x]^2).  Both sums run
-//                          over the balanced binary tree of the NESTED child order (ps_udgrade_kernel's tree), in which
-//                          equal children sum exactly: a constant block has variance 0.  WAVE = 0 (up to 16 children): a
-//                          lane owns an output pixel and walks its children with a binary counter of partial sums.
+//                          over the balanced binary tree of the NESTED child order (tree_push of healpix_geom.h, as in
+//                          ps_udgrade_kernel), in which equal children sum exactly: a constant block has variance 0.
+//                          WAVE = 0 (up to 16 children): a lane owns an output pixel and walks its children with a
+//                          binary counter of partial sums.
 //                          WAVE = 1 (64 children and more): a wave owns an output pixel, lane l takes children
 //                          64 i + l, a xor butterfly (offsets 1 .. 32) sums 64 neighbours - the six lowest levels of
 //                          the same tree - and the binary counter runs over i.  The two forms give the same bits.
@@ -28,27 +29,6 @@ namespace {
 constexpr int GX_MAXK = 6;      // block variance: at most 4^6 children per output pixel (as ud_grade)
 constexpr int GX_CH = 16;       // combine: channels per thread
 
-// the bits of v spread onto the even places
-__device__ inline long spread_bits(long v, int k) {
-    long r = 0;
-    for (int b = 0; b < k; b++) r |= ((v >> b) & 1L) << (2 * b);
-    return r;
-}
-
-__device__ inline long nest2ring_dev(const Geom &g, int k, long q) {
-    const long nn = g.nside * g.nside;
-    const int face = (int)(q / nn);
-    const long j = q - face * nn;
-    return xyf2ring(g, child_offset(j, 0, k), child_offset(j, 1, k), face);
-}
-
-__device__ inline long ring2nest_dev(const Geom &g, int k, long p) {
-    long ix, iy;
-    int face;
-    ring2xyf(g, p, ix, iy, face);
-    return (long)face * g.nside * g.nside + (spread_bits(ix, k) | (spread_bits(iy, k) << 1));
-}
-
 // r2n 1: out in NESTED order from in in RING order; 0: the other way
 __global__ __launch_bounds__(256) void gx_reorder_kernel(Geom g, int k, int r2n, const double *__restrict__ in, long nmap,
                                                          double *__restrict__ out) {
@@ -56,11 +36,6 @@ __global__ __launch_bounds__(256) void gx_reorder_kernel(Geom g, int k, int r2n,
         const long p = r2n ? nest2ring_dev(g, k, q) : ring2nest_dev(g, k, q);
         for (long m = 0; m < nmap; m++) out[m * g.npix + q] = in[m * g.npix + p];
     }
-}
-
-// RING pixel at gin of NESTED child j of the output pixel (ix, iy, face)
-__device__ inline long child_pixel(const Geom &gin, long ix, long iy, int face, int k, long j) {
-    return xyf2ring(gin, (ix << k) + child_offset(j, 0, k), (iy << k) + child_offset(j, 1, k), face);
 }
 
 template <int WAVE>
@@ -89,9 +64,7 @@ __global__ __launch_bounds__(256) void gx_blockvar_kernel(Geom gin, Geom gout, i
                     }
 #pragma unroll
                     for (int o = 1; o <= 32; o <<= 1) v = v + __shfl_xor(v, o, 64);
-                    int lvl = 0;
-                    for (; (i >> lvl) & 1; lvl++) v = part[lvl] + v;
-                    part[lvl] = v;
+                    tree_push(part, i, v);
                 }
                 mean = part[2 * k - 6] / dn;
             }
@@ -112,9 +85,7 @@ __global__ __launch_bounds__(256) void gx_blockvar_kernel(Geom gin, Geom gout, i
                         v = v - mean;
                         v = v * v;
                     }
-                    int lvl = 0;
-                    for (; (j >> lvl) & 1; lvl++) v = part[lvl] + v;
-                    part[lvl] = v;
+                    tree_push(part, j, v);
                 }
                 mean = part[2 * k] / dn;
             }
@@ -188,59 +159,38 @@ __global__ __launch_bounds__(256) void gx_combine_kernel(const double *__restric
     }
 }
 
-unsigned gx_grid(const corahip_ctx *ctx, long n) {
-    long blocks = (n + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
-inline bool gx_overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + nb && pb < pa + na;
-}
-
-inline int gx_log2(int v) {
-    int k = 0;
-    while ((1 << k) < v) k++;
-    return (1 << k) == v ? k : -1;
-}
-
-inline bool gx_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-inline bool gx_aligned32(const void *p) { return ((uintptr_t)p & 31u) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int corahip_healpix_reorder(corahip_ctx *ctx, const double *maps, long nmap, int nside, int r2n, double *out) {
     ARG_CHECK(ctx && maps && out && nmap >= 1 && nside >= 1 && nside <= 8192);
-    const int k = gx_log2(nside);
+    const int k = log2_exact(nside);
     ARG_CHECK(k >= 0);
     const Geom g = make_geom(nside);
     const size_t bytes = (size_t)nmap * (size_t)g.npix * 8;
-    ARG_CHECK(!gx_overlaps(out, bytes, maps, bytes));
+    ARG_CHECK(!overlaps(out, bytes, maps, bytes));
     StageTimer t(ctx, "healpix_reorder");
-    hipLaunchKernelGGL(gx_reorder_kernel, dim3(gx_grid(ctx, g.npix)), dim3(256), 0, ctx->stream, g, k, r2n ? 1 : 0, maps, nmap, out);
+    hipLaunchKernelGGL(gx_reorder_kernel, dim3(grid_blocks(ctx, g.npix)), dim3(256), 0, ctx->stream, g, k, r2n ? 1 : 0, maps, nmap, out);
     LAUNCH_CHECK();
     return 0;
 }
 
 int corahip_healpix_block_variance(corahip_ctx *ctx, const double *maps, long nmap, int nside_in, int nside_out, double *out) {
     ARG_CHECK(ctx && maps && out && nmap >= 1 && nside_in >= 1 && nside_in <= 8192 && nside_out >= 1 && nside_out <= nside_in);
-    const int ki = gx_log2(nside_in), ko = gx_log2(nside_out);
+    const int ki = log2_exact(nside_in), ko = log2_exact(nside_out);
     ARG_CHECK(ki >= 0 && ko >= 0);
     const int k = ki - ko;
     ARG_CHECK(k <= GX_MAXK);
     const Geom gin = make_geom(nside_in), gout = make_geom(nside_out);
-    ARG_CHECK(!gx_overlaps(out, (size_t)nmap * (size_t)gout.npix * 8, maps, (size_t)nmap * (size_t)gin.npix * 8));
+    ARG_CHECK(!overlaps(out, (size_t)nmap * (size_t)gout.npix * 8, maps, (size_t)nmap * (size_t)gin.npix * 8));
     const long nitem = nmap * gout.npix;
     StageTimer t(ctx, "healpix_block_variance");
     if (k >= 3)
-        hipLaunchKernelGGL(gx_blockvar_kernel<1>, dim3(gx_grid(ctx, nitem * 64)), dim3(256), 0, ctx->stream, gin, gout, k, maps, nmap,
+        hipLaunchKernelGGL(gx_blockvar_kernel<1>, dim3(grid_blocks(ctx, nitem * 64)), dim3(256), 0, ctx->stream, gin, gout, k, maps, nmap,
                            out);
     else
-        hipLaunchKernelGGL(gx_blockvar_kernel<0>, dim3(gx_grid(ctx, nitem)), dim3(256), 0, ctx->stream, gin, gout, k, maps, nmap, out);
+        hipLaunchKernelGGL(gx_blockvar_kernel<0>, dim3(grid_blocks(ctx, nitem)), dim3(256), 0, ctx->stream, gin, gout, k, maps, nmap, out);
     LAUNCH_CHECK();
     return 0;
 }
@@ -249,11 +199,11 @@ int corahip_alm_scale_l(corahip_ctx *ctx, const double *alm, int lmax, int nnu, 
     ARG_CHECK(ctx && alm && fl && out && lmax >= 0 && nnu >= 1);
     const int G = (nnu + 3) / 4;
     const size_t abytes = (size_t)nalm_of(lmax) * (size_t)G * 64;
-    ARG_CHECK(out == alm || !gx_overlaps(out, abytes, alm, abytes));          // in place, or apart
-    ARG_CHECK(!gx_overlaps(out, abytes, fl, (size_t)nnu * (size_t)(lmax + 1) * 8));
-    ARG_CHECK(gx_aligned32(alm) && gx_aligned32(out));
+    ARG_CHECK(out == alm || !overlaps(out, abytes, alm, abytes));          // in place, or apart
+    ARG_CHECK(!overlaps(out, abytes, fl, (size_t)nnu * (size_t)(lmax + 1) * 8));
+    ARG_CHECK(is_aligned(alm, 32) && is_aligned(out, 32));
     StageTimer t(ctx, "alm_scale_l");
-    hipLaunchKernelGGL(gx_alm_scale_kernel, dim3(gx_grid(ctx, nalm_of(lmax) * G)), dim3(256), 0, ctx->stream, alm, lmax, nnu, G, fl,
+    hipLaunchKernelGGL(gx_alm_scale_kernel, dim3(grid_blocks(ctx, nalm_of(lmax) * G)), dim3(256), 0, ctx->stream, alm, lmax, nnu, G, fl,
                        out);
     LAUNCH_CHECK();
     return 0;
@@ -265,12 +215,12 @@ int corahip_galaxy_combine(corahip_ctx *ctx, const double *fg, const double *fgs
     ARG_CHECK(skip >= 0 && nchan > skip && npix >= 2 && (npix & 1) == 0 && inv_mv > 0.0 && inv_mv <= 1.7976931348623157e308);
     const int nout = nchan - skip;
     ARG_CHECK((nout + GX_CH - 1) / GX_CH <= 65535 && (npix / 2 + 255) / 256 <= 0x7fffffffL);
-    ARG_CHECK(gx_aligned16(fg) && gx_aligned16(fgs) && gx_aligned16(haslam) && gx_aligned16(sc) && gx_aligned16(am) &&
-              gx_aligned16(out));
+    ARG_CHECK(is_aligned(fg, 16) && is_aligned(fgs, 16) && is_aligned(haslam, 16) && is_aligned(sc, 16) && is_aligned(am, 16) &&
+              is_aligned(out, 16));
     const size_t obytes = (size_t)nout * (size_t)npix * 8, ibytes = (size_t)nchan * (size_t)npix * 8, pbytes = (size_t)npix * 8;
-    ARG_CHECK(!gx_overlaps(out, obytes, fg, ibytes) && !gx_overlaps(out, obytes, fgs, ibytes));
-    ARG_CHECK(!gx_overlaps(out, obytes, haslam, pbytes) && !gx_overlaps(out, obytes, sc, pbytes));
-    ARG_CHECK(!gx_overlaps(out, obytes, am, pbytes) && !gx_overlaps(out, obytes, lnr, (size_t)nchan * 8));
+    ARG_CHECK(!overlaps(out, obytes, fg, ibytes) && !overlaps(out, obytes, fgs, ibytes));
+    ARG_CHECK(!overlaps(out, obytes, haslam, pbytes) && !overlaps(out, obytes, sc, pbytes));
+    ARG_CHECK(!overlaps(out, obytes, am, pbytes) && !overlaps(out, obytes, lnr, (size_t)nchan * 8));
     StageTimer t(ctx, "galaxy_combine");
     hipLaunchKernelGGL(gx_combine_kernel, dim3((unsigned)((npix / 2 + 255) / 256), (unsigned)((nout + GX_CH - 1) / GX_CH)), dim3(256), 0,
                        ctx->stream, fg, fgs, haslam, sc, am, inv_mv, lnr, nchan, skip, npix, out);

@@ -1,8 +1,8 @@
-// healpix_geom.h - HEALPix geometry shared by pmesh.hip, hpinterp.hip, pointsource.hip and galaxy.hip: the NESTED
-// hierarchy (RING pixel <-> (x, y, face)) and the RING pixel-centre arithmetic of
-// cora_amd/util/hputil.py (pix2ang, ang2pix), repeated operation for operation so that the host oracles and the
-// kernels pick the same pixels; no contraction into FMAs there.  Restated from the published HEALPix algorithm
-// (Gorski et al. 2005).
+// healpix_geom.h - the one HEALPix geometry of the library, shared by pmesh.hip, hpinterp.hip, pointsource.hip and
+// galaxy.hip: the RING pixel-centre arithmetic of cora_amd/util/hputil.py (pix2ang, ang2pix), repeated operation for
+// operation so that the host oracles and the kernels pick the same pixels (no contraction into FMAs there), and the
+// NESTED hierarchy: RING pixel <-> (x, y, face) at any nside, RING <-> NESTED index at a power of two, the child offsets
+// and the balanced-tree sum over NESTED children.  Restated from the published HEALPix algorithm (Gorski et al. 2005).
 #pragma once
 #include "common.h"
 
@@ -124,11 +124,15 @@ __device__ inline void displaced_position(double thp, double php, double dth, do
 
 // ---- NESTED hierarchy --------------------------------------------------------------------------------------------
 
-__device__ static const int PS_JRLL[12] = {2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4};
-__device__ static const int PS_JPLL[12] = {1, 3, 5, 7, 0, 2, 4, 6, 1, 3, 5, 7};
+// the southern corner of base face f: its ring in units of nside, {2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4}, and its longitude
+// in units of pi / 4, {1, 3, 5, 7, 0, 2, 4, 6, 1, 3, 5, 7}.  Computed, not tabulated: no memory access in the lane.
+__device__ inline int face_jrll(int f) { return (f >> 2) + 2; }
+__device__ inline int face_jpll(int f) { return 2 * (f & 3) + ((f >> 2) == 1 ? 0 : 1); }
 
-// RING pixel -> (x, y, face): x runs to the north-east, y to the north-west, inside base pixel `face`
-__device__ inline void ring2xyf(const Geom &g, long pixel, long &ix, long &iy, int &face) {
+// RING pixel -> (x, y, face): x runs to the north-east, y to the north-west, inside base pixel `face`.  I: the type the
+// caller keeps its coordinates in (int or long; they are below nside); the arithmetic is 64-bit for either.
+template <typename I>
+__device__ inline void ring2xyf(const Geom &g, long pixel, I &ix, I &iy, int &face) {
     const long ns = g.nside, nl2 = 2 * ns;
     long iring, iphi, kshift, nr;
     if (pixel < g.ncap) {
@@ -156,16 +160,17 @@ __device__ inline void ring2xyf(const Geom &g, long pixel, long &ix, long &iy, i
         iring = 2 * nl2 - iring;
         face = 8 + (int)((iphi - 1) / nr);
     }
-    const long irt = iring - PS_JRLL[face] * ns + 1;
-    long ipt = 2 * iphi - PS_JPLL[face] * nr - kshift - 1;
+    const long irt = iring - face_jrll(face) * ns + 1;
+    long ipt = 2 * iphi - face_jpll(face) * nr - kshift - 1;
     if (ipt >= nl2) ipt -= 8 * ns;
-    ix = (ipt - irt) >> 1;
-    iy = (-ipt - irt) >> 1;
+    ix = (I)((ipt - irt) >> 1);
+    iy = (I)((-ipt - irt) >> 1);
 }
 
-__device__ inline long xyf2ring(const Geom &g, long ix, long iy, int face) {
+template <typename I>
+__device__ inline long xyf2ring(const Geom &g, I ix, I iy, int face) {
     const long ns = g.nside, nl4 = 4 * ns;
-    const long jr = PS_JRLL[face] * ns - ix - iy - 1;
+    const long jr = face_jrll(face) * ns - ix - iy - 1;
     long nr, kshift, before;
     if (jr < ns) {
         nr = jr;
@@ -180,7 +185,7 @@ __device__ inline long xyf2ring(const Geom &g, long ix, long iy, int face) {
         before = g.ncap + (jr - ns) * nl4;
         kshift = (jr - ns) & 1;
     }
-    long jp = (PS_JPLL[face] * nr + ix - iy + 1 + kshift) / 2;
+    long jp = (face_jpll(face) * nr + ix - iy + 1 + kshift) / 2;
     if (jp > nl4) jp -= nl4;
     else if (jp < 1) jp += nl4;
     return before + jp - 1;
@@ -191,6 +196,42 @@ __device__ inline long child_offset(long j, int from, int k) {
     long v = 0;
     for (int b = 0; b < k; b++) v |= ((j >> (2 * b + from)) & 1L) << b;
     return v;
+}
+
+// the bits of v spread onto the even places
+__device__ inline long spread_bits(long v, int k) {
+    long r = 0;
+    for (int b = 0; b < k; b++) r |= ((v >> b) & 1L) << (2 * b);
+    return r;
+}
+
+// RING <-> NESTED pixel at nside = 2^k: NESTED pixel q = face nside^2 + (x bits on the even places, y bits on the odd)
+__device__ inline long nest2ring_dev(const Geom &g, int k, long q) {
+    const long nn = g.nside * g.nside;
+    const int face = (int)(q / nn);
+    const long j = q - face * nn;
+    return xyf2ring(g, child_offset(j, 0, k), child_offset(j, 1, k), face);
+}
+
+__device__ inline long ring2nest_dev(const Geom &g, int k, long p) {
+    long ix, iy;
+    int face;
+    ring2xyf(g, p, ix, iy, face);
+    return (long)face * g.nside * g.nside + (spread_bits(ix, k) | (spread_bits(iy, k) << 1));
+}
+
+// RING pixel at gin (nside 2^k times finer) of NESTED child j of the pixel (ix, iy, face)
+__device__ inline long child_pixel(const Geom &gin, long ix, long iy, int face, int k, long j) {
+    return xyf2ring(gin, (ix << k) + child_offset(j, 0, k), (iy << k) + child_offset(j, 1, k), face);
+}
+
+// One step of the balanced-tree sum over j = 0, 1, 2, ...: v joins the partial sums of the set low bits of j (a binary
+// counter), so that after j = 2^n - 1 part[n] holds the pairwise sum of all 2^n values, in which equal values sum
+// exactly.  Every user sums through this one function: the same operations in the same order.
+__device__ inline void tree_push(double *part, long j, double v) {
+    int lvl = 0;
+    for (; (j >> lvl) & 1; lvl++) v = part[lvl] + v;
+    part[lvl] = v;
 }
 
 __global__ __launch_bounds__(256) void minus_one_kernel(double *__restrict__ out, long n) {

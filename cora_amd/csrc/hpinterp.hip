@@ -226,13 +226,6 @@ __global__ __launch_bounds__(256) void za_grid_kernel(Geom g, const double *__re
     }
 }
 
-unsigned grid_for(const corahip_ctx *ctx, long n) {
-    long blocks = (n + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
 }  // namespace
 
 int corahip_healpix_interp_weights(corahip_ctx *ctx, int nside, const double *theta, const double *phi, long n,
@@ -240,7 +233,7 @@ int corahip_healpix_interp_weights(corahip_ctx *ctx, int nside, const double *th
     ARG_CHECK(ctx && theta && phi && pix_out && w_out && nside >= 1 && nside <= 8192 && n >= 0);
     if (n == 0) return 0;
     StageTimer st(ctx, "healpix_interp_weights");
-    hipLaunchKernelGGL(interp_weights_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, make_geom(nside), theta,
+    hipLaunchKernelGGL(interp_weights_kernel, dim3(grid_blocks(ctx, n)), dim3(256), 0, ctx->stream, make_geom(nside), theta,
                        phi, n, (long *)pix_out, w_out);
     LAUNCH_CHECK();
     return 0;
@@ -251,7 +244,7 @@ int corahip_healpix_interp_val(corahip_ctx *ctx, const double *maps, long nmap, 
     ARG_CHECK(ctx && maps && theta && phi && out && nside >= 1 && nside <= 8192 && nmap >= 1 && n >= 0);
     if (n == 0) return 0;
     StageTimer st(ctx, "healpix_interp_val");
-    hipLaunchKernelGGL(interp_val_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, make_geom(nside), maps, nmap,
+    hipLaunchKernelGGL(interp_val_kernel, dim3(grid_blocks(ctx, n)), dim3(256), 0, ctx->stream, make_geom(nside), maps, nmap,
                        theta, phi, n, out);
     LAUNCH_CHECK();
     return 0;
@@ -260,13 +253,12 @@ int corahip_healpix_interp_val(corahip_ctx *ctx, const double *maps, long nmap, 
 int corahip_healpix_rotate_maps(corahip_ctx *ctx, const double *maps, long nmap, int nside, const double *R, double *out) {
     ARG_CHECK(ctx && maps && R && out && nside >= 1 && nside <= 8192 && nmap >= 1);
     const Geom g = make_geom(nside);
-    const char *a = (const char *)maps, *b = (const char *)out;
     const size_t bytes = (size_t)nmap * (size_t)g.npix * sizeof(double);
-    ARG_CHECK(a + bytes <= b || b + bytes <= a);                      // out must not overlap maps
+    ARG_CHECK(!overlaps(out, bytes, maps, bytes));
     Rot rot;
     for (int i = 0; i < 9; ++i) rot.m[i] = R[i];
     StageTimer st(ctx, "healpix_rotate_maps");
-    hipLaunchKernelGGL(rotate_maps_kernel, dim3(grid_for(ctx, g.npix)), dim3(256), 0, ctx->stream, g, maps, nmap, rot, out);
+    hipLaunchKernelGGL(rotate_maps_kernel, dim3(grid_blocks(ctx, g.npix)), dim3(256), 0, ctx->stream, g, maps, nmap, rot, out);
     LAUNCH_CHECK();
     return 0;
 }
@@ -278,9 +270,9 @@ int corahip_za_density_grid(corahip_ctx *ctx, const double *psi, const double *d
     StageTimer st(ctx, "za_density_grid");
     const Geom g = make_geom(nside);
     const long n = (long)nchi * g.npix;
-    hipLaunchKernelGGL(za_grid_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, g, psi, delta_bias, chi, nchi, out);
+    hipLaunchKernelGGL(za_grid_kernel, dim3(grid_blocks(ctx, n)), dim3(256), 0, ctx->stream, g, psi, delta_bias, chi, nchi, out);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(minus_one_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, ctx->stream, out, n);
+    hipLaunchKernelGGL(minus_one_kernel, dim3(grid_blocks(ctx, n)), dim3(256), 0, ctx->stream, out, n);
     LAUNCH_CHECK();
     return 0;
 }

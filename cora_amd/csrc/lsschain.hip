@@ -365,19 +365,6 @@ lognormal_kernel(const double *f, const double *__restrict__ hv, const double *_
     }
 }
 
-inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-inline long stream_blocks(corahip_ctx *ctx, long nv) {
-    long blocks = (nv + 255) / 256;
-    const long cap = (long)ctx->num_cu * 32;
-    return blocks > cap ? cap : blocks;
-}
-
-inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 // nb (partials per row) and per (columns per partial, even) of slice_moments
 inline void moments_split(long ncol, int *nb, long *per) {
     long b = (ncol + 8191) / 8192;
@@ -395,14 +382,14 @@ extern "C" {
 int corahip_slice_mix(corahip_ctx *ctx, const double *K, const double *f, const int32_t *ranges, int n, long ncol,
                       double *out) {
     ARG_CHECK(ctx && K && f && out && n >= 1 && n <= 4096 && ncol >= 1);
-    ARG_CHECK(((uintptr_t)K & 7) == 0 && ((uintptr_t)f & 7) == 0 && ((uintptr_t)out & 7) == 0);
-    ARG_CHECK(ranges == nullptr || ((uintptr_t)ranges & 3) == 0);
+    ARG_CHECK(is_aligned(K, 8) && is_aligned(f, 8) && is_aligned(out, 8));
+    ARG_CHECK(ranges == nullptr || is_aligned(ranges, 4));
     const size_t nbytes = (size_t)n * (size_t)ncol * 8;
     ARG_CHECK(!overlaps(out, nbytes, f, nbytes) && !overlaps(out, nbytes, K, (size_t)n * n * 8));
     const long nrb = (n + SM_T - 1) / SM_T, ncb = (ncol + SM_T - 1) / SM_T;
     ARG_CHECK(nrb * ncb <= 0x7fffffffL);
     StageTimer t(ctx, "slice_mix");
-    const int vec = (ncol & 1) == 0 && al16(f);
+    const int vec = (ncol & 1) == 0 && is_aligned(f, 16);
     hipLaunchKernelGGL(slice_mix_kernel, dim3((unsigned)(nrb * ncb)), dim3(SM_NT), 0, ctx->stream, K, f, ranges, n, ncol,
                        (int)nrb, vec, out);
     LAUNCH_CHECK();
@@ -416,18 +403,18 @@ int corahip_slice_diff2(corahip_ctx *ctx, const double *f, const double *coef, c
     ARG_CHECK(f != nullptr || g != nullptr);
     ARG_CHECK(f == nullptr || (coef != nullptr && n >= 4));
     ARG_CHECK(g == nullptr || (s != nullptr && (f == nullptr || t != nullptr)));
-    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)g & 7) == 0 && ((uintptr_t)h & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    ARG_CHECK(is_aligned(f, 8) && is_aligned(g, 8) && is_aligned(h, 8) && is_aligned(out, 8));
     const size_t nbytes = (size_t)n * (size_t)ncol * 8;
     ARG_CHECK(f == nullptr || !overlaps(out, nbytes, f, nbytes));
     StageTimer tm(ctx, "slice_diff2");
-    const bool v2 = (ncol & 1) == 0 && al16(f) && al16(g) && al16(h) && al16(out);
+    const bool v2 = (ncol & 1) == 0 && is_aligned(f, 16) && is_aligned(g, 16) && is_aligned(h, 16) && is_aligned(out, 16);
     const long nv = v2 ? ncol / 2 : ncol;
-    const long blocks = stream_blocks(ctx, nv);
+    const unsigned blocks = grid_blocks(ctx, nv, 32);
     if (v2)
-        hipLaunchKernelGGL(slice_diff2_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, coef, g, h, s, t, n,
+        hipLaunchKernelGGL(slice_diff2_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, f, coef, g, h, s, t, n,
                            ncol, out);
     else
-        hipLaunchKernelGGL(slice_diff2_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, coef, g, h, s, t, n,
+        hipLaunchKernelGGL(slice_diff2_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, f, coef, g, h, s, t, n,
                            ncol, out);
     LAUNCH_CHECK();
     return 0;
@@ -445,14 +432,14 @@ int corahip_slice_moments_workspace_bytes(int n, long ncol, size_t *bytes) {
 int corahip_slice_moments(corahip_ctx *ctx, const double *f, long ld, const double *c, int n, long ncol, void *work,
                           size_t work_bytes, double *sum1, double *sum2) {
     ARG_CHECK(ctx && f && work && sum1 && sum2 && n >= 1 && ncol >= 1 && ld >= ncol);
-    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)work & 7) == 0);
+    ARG_CHECK(is_aligned(f, 8) && is_aligned(work, 8));
     int nb;
     long per;
     moments_split(ncol, &nb, &per);
     ARG_CHECK(work_bytes >= (size_t)n * nb * 2 * sizeof(double));
     ARG_CHECK((long)n * nb <= 0x7fffffffL);
     StageTimer t(ctx, "slice_moments");
-    const bool v2 = (ncol & 1) == 0 && (ld & 1) == 0 && al16(f);
+    const bool v2 = (ncol & 1) == 0 && (ld & 1) == 0 && is_aligned(f, 16);
     if (v2)
         hipLaunchKernelGGL(slice_moments_partial_kernel<2>, dim3((unsigned)((long)n * nb)), dim3(256), 0, ctx->stream, f, ld,
                            c, n, ncol, nb, per, (double *)work);
@@ -470,17 +457,17 @@ int corahip_bias_field(corahip_ctx *ctx, const double *f, const double *c1, cons
                        long ncol, double *out) {
     ARG_CHECK(ctx && f && c1 && out && n >= 1 && ncol >= 1);
     ARG_CHECK((c2 == nullptr) == (m2 == nullptr));
-    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    ARG_CHECK(is_aligned(f, 8) && is_aligned(out, 8));
     const size_t nbytes = (size_t)n * (size_t)ncol * 8;
     ARG_CHECK(out == f || !overlaps(out, nbytes, f, nbytes));
     StageTimer t(ctx, "bias_field");
-    const bool v2 = (ncol & 1) == 0 && al16(f) && al16(out);
+    const bool v2 = (ncol & 1) == 0 && is_aligned(f, 16) && is_aligned(out, 16);
     const long nv = v2 ? ncol / 2 : ncol;
-    const long blocks = stream_blocks(ctx, nv);
+    const unsigned blocks = grid_blocks(ctx, nv, 32);
     if (v2)
-        hipLaunchKernelGGL(bias_field_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, c1, c2, m2, n, ncol, out);
+        hipLaunchKernelGGL(bias_field_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, f, c1, c2, m2, n, ncol, out);
     else
-        hipLaunchKernelGGL(bias_field_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, c1, c2, m2, n, ncol, out);
+        hipLaunchKernelGGL(bias_field_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, f, c1, c2, m2, n, ncol, out);
     LAUNCH_CHECK();
     return 0;
 }
@@ -488,19 +475,19 @@ int corahip_bias_field(corahip_ctx *ctx, const double *f, const double *c1, cons
 int corahip_lognormal(corahip_ctx *ctx, const double *f, const double *hv, const double *rs, double pre, int n, long ncol,
                       long ld_out, double *out) {
     ARG_CHECK(ctx && f && out && n >= 1 && ncol >= 1 && ld_out >= ncol);
-    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    ARG_CHECK(is_aligned(f, 8) && is_aligned(out, 8));
     // in place (same pointer, same stride) or disjoint
     ARG_CHECK((out == f && ld_out == ncol) ||
               !overlaps(out, ((size_t)(n - 1) * (size_t)ld_out + (size_t)ncol) * 8, f, (size_t)n * (size_t)ncol * 8));
     StageTimer t(ctx, "lognormal");
-    const bool v2 = (ncol & 1) == 0 && (ld_out & 1) == 0 && al16(f) && al16(out);
+    const bool v2 = (ncol & 1) == 0 && (ld_out & 1) == 0 && is_aligned(f, 16) && is_aligned(out, 16);
     const long nv = v2 ? ncol / 2 : ncol;
-    const long blocks = stream_blocks(ctx, nv);
+    const unsigned blocks = grid_blocks(ctx, nv, 32);
     if (v2)
-        hipLaunchKernelGGL(lognormal_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, hv, rs, pre, n, ncol,
+        hipLaunchKernelGGL(lognormal_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, f, hv, rs, pre, n, ncol,
                            ld_out, out);
     else
-        hipLaunchKernelGGL(lognormal_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, hv, rs, pre, n, ncol,
+        hipLaunchKernelGGL(lognormal_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, f, hv, rs, pre, n, ncol,
                            ld_out, out);
     LAUNCH_CHECK();
     return 0;

@@ -1,11 +1,9 @@
 // pmesh.hip - Zel'dovich SPH density assignment (cora/signal/lss.py:1305-1419 za_density_sph with
 // cora/util/pmesh.pyx:29-279 + pmesh_util.c:4-42) and the HEALPix RING neighbour table it needs.
 //
-// Geometry: RING ang2pix / pix2vec / ang2vec and get_all_neighbours restated from the published HEALPix
-// algorithm (Gorski et al. 2005; ring -> (x, y, face), step within or across base faces, back to ring).  The
-// z / phi of a pixel centre and ang2pix repeat, operation for operation, cora_amd/util/hputil.py (pix2ang,
-// ang2pix) so that the host oracle and the kernel pick the same pixels; no contraction into FMAs there
-// (healpix_geom.h, shared with hpinterp.hip).
+// Geometry: get_all_neighbours restated from the published HEALPix algorithm (Gorski et al. 2005): ring -> (x, y, face),
+// step within or across base faces (the tables below), back to ring.  The two conversions, ang2pix and the pixel
+// centres are healpix_geom.h's, as for every other map-domain kernel; this file keeps (x, y) in int (nside <= 8192).
 //
 // Deposit: one workgroup owns a 16 x 16 block of one base face (RING pixels of those (x, y)) and 8 slices.  Its
 // particles add into an LDS f64 tile of that block with a 4-pixel halo and 3 radial bins of halo on each side
@@ -41,69 +39,6 @@ __constant__ int8_t c_nb_swap[9][3] = {{0, 0, 3}, {0, 0, 6}, {0, 0, 0}, {0, 0, 5
 // healpy's order of get_all_neighbours: SW, W, NW, N, NE, E, SE, S
 __constant__ int8_t c_nb_dx[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
 __constant__ int8_t c_nb_dy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-
-__device__ inline int face_jrll(int f) { return (f >> 2) + 2; }
-__device__ inline int face_jpll(int f) { return 2 * (f & 3) + ((f >> 2) == 1 ? 0 : 1); }
-
-__device__ void ring2xyf(const Geom &g, long pix, int &ix, int &iy, int &face) {
-    const long ns = g.nside, nl2 = 2 * ns;
-    long iring, iphi, kshift, nr;
-    if (pix < g.ncap) {
-        iring = (1 + isqrt_l(1 + 2 * pix)) >> 1;
-        iphi = (pix + 1) - 2 * iring * (iring - 1);
-        kshift = 0;
-        nr = iring;
-        face = (int)((iphi - 1) / nr);
-    } else if (pix < g.npix - g.ncap) {
-        long ip = pix - g.ncap;
-        long tmp = ip / (4 * ns);
-        iring = tmp + ns;
-        iphi = ip - tmp * 4 * ns + 1;
-        kshift = (iring + ns) & 1;
-        nr = ns;
-        long ire = tmp + 1, irm = nl2 + 1 - tmp;
-        long ifm = (iphi - (ire >> 1) + ns - 1) / ns;
-        long ifp = (iphi - (irm >> 1) + ns - 1) / ns;
-        face = (int)((ifp == ifm) ? (ifp | 4) : ((ifp < ifm) ? ifp : (ifm + 8)));
-    } else {
-        long ip = g.npix - pix;
-        iring = (1 + isqrt_l(2 * ip - 1)) >> 1;
-        iphi = 4 * iring + 1 - (ip - 2 * iring * (iring - 1));
-        kshift = 0;
-        nr = iring;
-        iring = 2 * nl2 - iring;
-        face = (int)((iphi - 1) / nr + 8);
-    }
-    long irt = iring - (long)face_jrll(face) * ns + 1;
-    long ipt = 2 * iphi - (long)face_jpll(face) * nr - kshift - 1;
-    if (ipt >= nl2) ipt -= 8 * ns;
-    ix = (int)((ipt - irt) >> 1);
-    iy = (int)((-ipt - irt) >> 1);
-}
-
-__device__ long xyf2ring(const Geom &g, int ix, int iy, int face) {
-    const long ns = g.nside, nl4 = 4 * ns;
-    long jr = (long)face_jrll(face) * ns - ix - iy - 1;
-    long nr, n_before;
-    bool shifted;
-    if (jr < ns) {
-        nr = jr;
-        n_before = 2 * jr * (jr - 1);
-        shifted = true;
-    } else if (jr < 3 * ns) {
-        nr = ns;
-        n_before = g.ncap + (jr - ns) * nl4;
-        shifted = ((jr - ns) & 1) == 0;
-    } else {
-        nr = 4 * ns - jr;
-        n_before = g.npix - 2 * nr * (nr + 1);
-        shifted = true;
-    }
-    long kshift = shifted ? 0 : 1;
-    long jp = ((long)face_jpll(face) * nr + ix - iy + 1 + kshift) / 2;
-    if (jp < 1) jp += nl4;
-    return n_before + jp - 1;
-}
 
 // the 8 neighbours of (ix, iy, face) in healpy's order: (x, y, face) each, face -1 where there is none
 __device__ void neighbours_xyf(const Geom &g, int ix, int iy, int face, int nx[8], int ny[8], int nf[8]) {
@@ -282,10 +217,7 @@ int corahip_healpix_neighbours(corahip_ctx *ctx, int nside, int32_t *out) {
     ARG_CHECK(ctx && out && nside >= 1 && nside <= 8192);
     StageTimer st(ctx, "healpix_neighbours");
     const Geom g = make_geom(nside);
-    long blocks = (g.npix + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(neighbours_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, g, out);
+    hipLaunchKernelGGL(neighbours_kernel, dim3(grid_blocks(ctx, g.npix)), dim3(256), 0, ctx->stream, g, out);
     LAUNCH_CHECK();
     return 0;
 }
@@ -302,10 +234,7 @@ int corahip_za_density_sph(corahip_ctx *ctx, const double *psi, const double *de
                        ctx->stream, g, psi, delta_bias, delta_m, chi, nchi, sigma_ang, sigma_chi, out);
     LAUNCH_CHECK();
     const long n = (long)nchi * g.npix;
-    long blocks = (n + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(minus_one_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, out, n);
+    hipLaunchKernelGGL(minus_one_kernel, dim3(grid_blocks(ctx, n)), dim3(256), 0, ctx->stream, out, n);
     LAUNCH_CHECK();
     return 0;
 }

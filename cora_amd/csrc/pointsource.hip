@@ -256,39 +256,14 @@ __global__ __launch_bounds__(256) void ps_udgrade_kernel(Geom gin, Geom gout, in
         } else {
             const int kk = -k;
             const long nchild = 1L << (2 * kk);
-            // pairwise over the NESTED order (child j joins the partial sums of the set bits of j, a binary counter):
-            // a balanced tree, in which equal children sum exactly
+            // pairwise over the NESTED order (tree_push of healpix_geom.h): equal children sum exactly
             for (long m = 0; m < nmap; m++) {
                 double part[2 * PS_UD_MAXK + 1];
-                for (long j = 0; j < nchild; j++) {
-                    const long q = xyf2ring(gin, (ix << kk) + child_offset(j, 0, kk), (iy << kk) + child_offset(j, 1, kk), face);
-                    double v = in[m * gin.npix + q];
-                    int lvl = 0;
-                    for (; (j >> lvl) & 1; lvl++) v = part[lvl] + v;
-                    part[lvl] = v;
-                }
+                for (long j = 0; j < nchild; j++) tree_push(part, j, in[m * gin.npix + child_pixel(gin, ix, iy, face, kk, j)]);
                 out[m * gout.npix + p] = part[2 * kk] / (double)nchild;
             }
         }
     }
-}
-
-unsigned ps_grid(const corahip_ctx *ctx, long n) {
-    long blocks = (n + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
-
-inline bool ps_overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + nb && pb < pa + na;
-}
-
-inline int log2_exact(int v) {
-    int k = 0;
-    while ((1 << k) < v) k++;
-    return (1 << k) == v ? k : -1;
 }
 
 }  // namespace
@@ -303,7 +278,7 @@ int corahip_pointsource_population(corahip_ctx *ctx, uint64_t seed, long n, cons
     if (n == 0) return 0;
     ARG_CHECK(pix && flux && index);
     StageTimer t(ctx, "pointsource_population");
-    hipLaunchKernelGGL(ps_population_kernel, dim3(ps_grid(ctx, n)), dim3(256), 0, ctx->stream, seed, n, knots, values, second,
+    hipLaunchKernelGGL(ps_population_kernel, dim3(grid_blocks(ctx, n)), dim3(256), 0, ctx->stream, seed, n, knots, values, second,
                        nknots, flux_min, spectral_mean, spectral_width, npix, (long *)pix, flux, index, (int *)interval,
                        spline_value);
     LAUNCH_CHECK();
@@ -318,16 +293,16 @@ int corahip_pointsource_paint(corahip_ctx *ctx, long n, const int64_t *pix, cons
     ARG_CHECK(polw == nullptr || npol == 4);
     ARG_CHECK((npix + 255) / 256 <= 0x7fffffffL);
     const size_t obytes = (size_t)nfreq * (size_t)npol * (size_t)npix * 8;
-    ARG_CHECK(!ps_overlaps(out, obytes, pix, (size_t)n * 8) && !ps_overlaps(out, obytes, flux, (size_t)n * 8));
-    ARG_CHECK(!ps_overlaps(out, obytes, beta, (size_t)n * 8) && !ps_overlaps(out, obytes, gamma, (size_t)n * 8));
-    ARG_CHECK(!ps_overlaps(out, obytes, polw, (size_t)n * 16) && !ps_overlaps(out, obytes, x, (size_t)nfreq * 8));
-    ARG_CHECK(!ps_overlaps(out, obytes, den, (size_t)nfreq * 8));
+    ARG_CHECK(!overlaps(out, obytes, pix, (size_t)n * 8) && !overlaps(out, obytes, flux, (size_t)n * 8));
+    ARG_CHECK(!overlaps(out, obytes, beta, (size_t)n * 8) && !overlaps(out, obytes, gamma, (size_t)n * 8));
+    ARG_CHECK(!overlaps(out, obytes, polw, (size_t)n * 16) && !overlaps(out, obytes, x, (size_t)nfreq * 8));
+    ARG_CHECK(!overlaps(out, obytes, den, (size_t)nfreq * 8));
     if (n == 0 && accumulate) return 0;
     void *start = nullptr;
     int rc = corahip_ctx_scratch(ctx, 11, ((size_t)npix + 1) * sizeof(int), &start);
     if (rc != 0) return rc;
     StageTimer t(ctx, "pointsource_paint");
-    hipLaunchKernelGGL(ps_csr_kernel, dim3(ps_grid(ctx, npix + 1)), dim3(256), 0, ctx->stream, (const long *)pix, n, npix,
+    hipLaunchKernelGGL(ps_csr_kernel, dim3(grid_blocks(ctx, npix + 1)), dim3(256), 0, ctx->stream, (const long *)pix, n, npix,
                        (int *)start);
     LAUNCH_CHECK();
     const unsigned pb = (unsigned)((npix + 255) / 256);
@@ -349,11 +324,11 @@ int corahip_polarise_rotate(corahip_ctx *ctx, const double *intensity, const dou
     ARG_CHECK(ctx && intensity && qfrac && ufrac && out && nfreq >= 1 && nfreq <= 65535 && npix >= 1);
     ARG_CHECK(rm == nullptr || wv != nullptr);
     const size_t ibytes = (size_t)nfreq * (size_t)npix * 8;
-    ARG_CHECK(!ps_overlaps(out, 4 * ibytes, intensity, ibytes) && !ps_overlaps(out, 4 * ibytes, qfrac, (size_t)npix * 8));
-    ARG_CHECK(!ps_overlaps(out, 4 * ibytes, ufrac, (size_t)npix * 8) && !ps_overlaps(out, 4 * ibytes, rm, (size_t)npix * 8));
-    ARG_CHECK(!ps_overlaps(out, 4 * ibytes, wv, (size_t)nfreq * 8));
+    ARG_CHECK(!overlaps(out, 4 * ibytes, intensity, ibytes) && !overlaps(out, 4 * ibytes, qfrac, (size_t)npix * 8));
+    ARG_CHECK(!overlaps(out, 4 * ibytes, ufrac, (size_t)npix * 8) && !overlaps(out, 4 * ibytes, rm, (size_t)npix * 8));
+    ARG_CHECK(!overlaps(out, 4 * ibytes, wv, (size_t)nfreq * 8));
     StageTimer t(ctx, "polarise_rotate");
-    hipLaunchKernelGGL(ps_rotate_kernel<0>, dim3(ps_grid(ctx, npix), (unsigned)nfreq), dim3(256), 0, ctx->stream, intensity, qfrac,
+    hipLaunchKernelGGL(ps_rotate_kernel<0>, dim3(grid_blocks(ctx, npix), (unsigned)nfreq), dim3(256), 0, ctx->stream, intensity, qfrac,
                        ufrac, rm, wv, nfreq, 4, npix, out);
     LAUNCH_CHECK();
     return 0;
@@ -363,9 +338,9 @@ int corahip_faraday_rotate(corahip_ctx *ctx, double *polmap, const double *rm, c
                            long npix) {
     ARG_CHECK(ctx && polmap && rm && wv && nfreq >= 1 && nfreq <= 65535 && npol >= 3 && npix >= 1);
     const size_t obytes = (size_t)nfreq * (size_t)npol * (size_t)npix * 8;
-    ARG_CHECK(!ps_overlaps(polmap, obytes, rm, (size_t)npix * 8) && !ps_overlaps(polmap, obytes, wv, (size_t)nfreq * 8));
+    ARG_CHECK(!overlaps(polmap, obytes, rm, (size_t)npix * 8) && !overlaps(polmap, obytes, wv, (size_t)nfreq * 8));
     StageTimer t(ctx, "faraday_rotate");
-    hipLaunchKernelGGL(ps_rotate_kernel<1>, dim3(ps_grid(ctx, npix), (unsigned)nfreq), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(ps_rotate_kernel<1>, dim3(grid_blocks(ctx, npix), (unsigned)nfreq), dim3(256), 0, ctx->stream,
                        (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, rm, wv, nfreq, npol, npix,
                        polmap);
     LAUNCH_CHECK();
@@ -378,9 +353,9 @@ int corahip_healpix_ud_grade(corahip_ctx *ctx, const double *maps, long nmap, in
     ARG_CHECK(ki >= 0 && ko >= 0);
     ARG_CHECK(ki - ko <= PS_UD_MAXK);
     const Geom gin = make_geom(nside_in), gout = make_geom(nside_out);
-    ARG_CHECK(!ps_overlaps(out, (size_t)nmap * (size_t)gout.npix * 8, maps, (size_t)nmap * (size_t)gin.npix * 8));
+    ARG_CHECK(!overlaps(out, (size_t)nmap * (size_t)gout.npix * 8, maps, (size_t)nmap * (size_t)gin.npix * 8));
     StageTimer t(ctx, "healpix_ud_grade");
-    hipLaunchKernelGGL(ps_udgrade_kernel, dim3(ps_grid(ctx, gout.npix)), dim3(256), 0, ctx->stream, gin, gout, ko - ki, maps,
+    hipLaunchKernelGGL(ps_udgrade_kernel, dim3(grid_blocks(ctx, gout.npix)), dim3(256), 0, ctx->stream, gin, gout, ko - ki, maps,
                        nmap, out);
     LAUNCH_CHECK();
     return 0;

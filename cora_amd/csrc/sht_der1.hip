@@ -147,14 +147,12 @@ int corahip_der1_alm_prep(corahip_ctx *ctx, corahip_sht_plan *plan, const double
                           double *alm3_dev) {
     ARG_CHECK(ctx && plan && alm_dev && alm3_dev);
     ARG_CHECK(g_in >= 1 && g0 >= 0 && g_src >= 1 && g0 + g_in <= g_src && g_in <= 16384);
-    ARG_CHECK(((uintptr_t)alm_dev & 15) == 0 && ((uintptr_t)alm3_dev & 15) == 0);
+    ARG_CHECK(is_aligned(alm_dev, 16) && is_aligned(alm3_dev, 16));
     StageTimer t(ctx, "der1_prep");
     const long W = 2L * g_in, total = plan->nalm * W;
-    long blocks = (total + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    const long stride = blocks * 256;
-    hipLaunchKernelGGL(der1_alm_prep_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, alm_dev, g_src, g0, g_in,
+    const unsigned blocks = grid_blocks(ctx, total);
+    const long stride = (long)blocks * 256;
+    hipLaunchKernelGGL(der1_alm_prep_kernel, dim3(blocks), dim3(256), 0, ctx->stream, alm_dev, g_src, g0, g_in,
                        plan->lmax, plan->nalm, stride / W, (int)(stride % W), alm3_dev);
     LAUNCH_CHECK();
     return 0;
@@ -165,7 +163,7 @@ int corahip_der1_combine(corahip_ctx *ctx, corahip_sht_plan *plan, const double 
     ARG_CHECK(ctx && plan && maps3 && out_theta && out_phi);
     ARG_CHECK(g_in >= 1 && nfields >= 1 && nfields <= 4 * g_in && nfields <= 65535);
     ARG_CHECK(phi_extra == 0 || phi_extra == 1);
-    ARG_CHECK(((uintptr_t)maps3 & 15) == 0 && ((uintptr_t)out_theta & 15) == 0 && ((uintptr_t)out_phi & 15) == 0);
+    ARG_CHECK(is_aligned(maps3, 16) && is_aligned(out_theta, 16) && is_aligned(out_phi, 16));
     StageTimer t(ctx, "der1_combine");
     dim3 grid((unsigned)plan->nring, (unsigned)nfields);
     hipLaunchKernelGGL(der1_combine_kernel, grid, dim3(256), 0, ctx->stream, maps3, g_in, plan->npix, plan->nring,
@@ -177,18 +175,16 @@ int corahip_der1_combine(corahip_ctx *ctx, corahip_sht_plan *plan, const double 
 int corahip_radial_gradient(corahip_ctx *ctx, const double *f, const double *x_coef, const double *s_r, int n, long npix,
                             double *out) {
     ARG_CHECK(ctx && f && x_coef && out && n >= 2 && npix >= 1);
-    ARG_CHECK(((uintptr_t)f & 7) == 0 && ((uintptr_t)out & 7) == 0);
+    ARG_CHECK(is_aligned(f, 8) && is_aligned(out, 8));
     StageTimer t(ctx, "radial_gradient");
-    const bool v2 = (npix & 1) == 0 && ((uintptr_t)f & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    const bool v2 = (npix & 1) == 0 && is_aligned(f, 16) && is_aligned(out, 16);
     const long nv = v2 ? npix / 2 : npix;
-    long blocks = (nv + 255) / 256;
-    const long cap = (long)ctx->num_cu * 32;
-    if (blocks > cap) blocks = cap;
+    const unsigned blocks = grid_blocks(ctx, nv, 32);
     if (v2)
-        hipLaunchKernelGGL(radial_gradient_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, x_coef, s_r, n,
+        hipLaunchKernelGGL(radial_gradient_kernel<2>, dim3(blocks), dim3(256), 0, ctx->stream, f, x_coef, s_r, n,
                            npix, out);
     else
-        hipLaunchKernelGGL(radial_gradient_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, f, x_coef, s_r, n,
+        hipLaunchKernelGGL(radial_gradient_kernel<1>, dim3(blocks), dim3(256), 0, ctx->stream, f, x_coef, s_r, n,
                            npix, out);
     LAUNCH_CHECK();
     return 0;

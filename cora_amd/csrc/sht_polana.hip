@@ -101,10 +101,7 @@ int corahip_spin2_combine(corahip_ctx *ctx, corahip_sht_plan *plan, const double
     const int G6 = g6, Gout = gout;
     HIP_TRY(hipMemsetAsync(alm_eb_dev, 0, sizeof(double) * (size_t)plan->nalm * Gout * 8, ctx->stream));
     const long total = plan->nalm * nfields;
-    long blocks = (total + 255) / 256;
-    const long cap = (long)ctx->num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(spin2_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, alm6_dev, G6, plan->d_polc,
+    hipLaunchKernelGGL(spin2_combine_kernel, dim3(grid_blocks(ctx, total)), dim3(256), 0, ctx->stream, alm6_dev, G6, plan->d_polc,
                        plan->lmax, nfields, Gout, alm_eb_dev);
     LAUNCH_CHECK();
     return 0;

@@ -159,11 +159,6 @@ cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double 
         }
 }
 
-inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 extern "C" {
@@ -173,7 +168,7 @@ int corahip_alm_cross_spectra(corahip_ctx *ctx, const double *alm_a, int nx, con
     ARG_CHECK(ctx && alm_a && out && nx >= 1 && ny >= 1 && lmax >= 0);
     const bool sym = alm_b == nullptr || alm_b == alm_a;
     ARG_CHECK(!sym || ny == nx);
-    ARG_CHECK(((uintptr_t)alm_a & 15) == 0 && ((uintptr_t)alm_b & 15) == 0 && ((uintptr_t)out & 7) == 0);
+    ARG_CHECK(is_aligned(alm_a, 16) && is_aligned(alm_b, 16) && is_aligned(out, 8));
     const int Ga = (nx + 3) / 4, Gb = (ny + 3) / 4;
     const size_t nalm = (size_t)nalm_of(lmax), obytes = (size_t)(lmax + 1) * (size_t)nx * (size_t)ny * 8;
     ARG_CHECK(!overlaps(out, obytes, alm_a, nalm * Ga * 64));

@@ -35,7 +35,7 @@ def _fields(nside, nchi, seed, pix_shift=1.0):
     return psi, delta_bias, delta_m, chi
 
 
-@pytest.mark.parametrize("nside", [1, 16, 1024])
+@pytest.mark.parametrize("nside", [1, 3, 6, 16, 1024])     # 3, 6: not a power of two
 def test_device_neighbours_match_host(ctx, nside):
     from cora_amd.util import hputil
 
@@ -92,7 +92,7 @@ def test_edge_cases_small_nside(ctx):
     non-default sigma_chi and the smallest maps: every target off the LDS tile goes to the global path."""
     from cora_amd.signal import lss
 
-    for nside, nchi, shift in ((1, 3, 0.5), (2, 5, 2.0), (4, 9, 4.0), (16, 11, 6.0)):
+    for nside, nchi, shift in ((1, 3, 0.5), (2, 5, 2.0), (3, 5, 3.0), (4, 9, 4.0), (16, 11, 6.0)):
         psi, db, dm, chi = _fields(nside, nchi, 100 + nside, pix_shift=shift)
         psi[0, 0] -= 40.0
         psi[0, -1] += 40.0
