@@ -146,6 +146,17 @@ static inline unsigned grid_blocks(const corahip_ctx *ctx, long n, int per_cu = 
     return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
+// an ordered two-pass sum over `count` elements: the number of block partials nb (at most 4096, ~8192 elements each) and
+// the elements per partial, rounded up to a multiple of `round` (1 or 2) - a function of count alone
+static inline void partials_split(long count, int round, int *nb, long *per) {
+    long b = (count + 8191) / 8192;
+    if (b > 4096) b = 4096;
+    long pr = (count + b - 1) / b;
+    pr = (pr + round - 1) & ~(long)(round - 1);
+    *nb = (int)((count + pr - 1) / pr);
+    *per = pr;
+}
+
 // do the byte ranges [a, a + na) and [b, b + nb) share a byte?  A null pointer (an optional argument left out) overlaps
 // nothing.  The guard changes no accepted call of the entry points that used to test without it: a null b "overlapped"
 // only an a below nb, and a real device pointer is never smaller than a buffer length.
@@ -171,3 +182,18 @@ __host__ __device__ static inline long alm_idx(int l, int m, int lmax) {
 }
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
+
+// sums of 256 threads' (a, b) in a fixed order, returned to every thread: lanes by halving __shfl_down from 32 to 1,
+// then ((w0 + w1) + w2) + w3 over the four waves through red[8] (LDS)
+__device__ static inline void block_sum2(double &a, double &b, double *red) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        a += __shfl_down(a, o, 64);
+        b += __shfl_down(b, o, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[2 * wave] = a, red[2 * wave + 1] = b;
+    __syncthreads();
+    a = ((red[0] + red[2]) + red[4]) + red[6];
+    b = ((red[1] + red[3]) + red[5]) + red[7];
+}

@@ -5,8 +5,9 @@
 //
 //   xi_table_kernel      [mu][i][j >= i]: radial-bin average of the spline at r(mu, x_i + a, x_j + b)
 //   legendre_matrix      lm[l][m] = weight_m P_l(mu_m) by the three-term recurrence (one thread per node)
-//   dgemm_nn_kernel      C[L x N] = A[L x M] B[M x N] on FP64 MFMA, 128 x 128 tiles, LDS-staged 16-deep K chunks
+//   dgemm_nn_kernel      C[L x N] = A[L x M] B[M x N] on FP64 MFMA: gemm_nn_128 of mfma_tile.h as it is
 #include "common.h"
+#include "mfma_tile.h"
 
 #include "rng_dev.h"   // fast_log01, fast_sqrt_pos (both hold their accuracy over every positive normal argument met here)
 
@@ -174,92 +175,13 @@ __global__ void legendre_matrix_kernel(const double *__restrict__ mu, const doub
     }
 }
 
-// C[Mr x N] = A[Mr x K] B[K x N], row-major (lda, ldb, ldc), K a multiple of 16 (callers pad with zeros).
-// Workgroup = 4 waves = 128 x 128 tile of C; wave = 64 x 64 = 4 x 4 MFMA tiles (128 accumulator VGPRs).
-// K runs in 16-deep chunks through a double-buffered LDS stage: As[128][17] (row i, k), Bs[16][132] (k, col).
-#define GM_T 128
-#define GM_K 16
+// C[Mr x N] = A[Mr x K] B[K x N], row-major (lda, ldb, ldc), K a multiple of 16 (callers pad with zeros): the plain case
+// of gemm_nn_128 (mfma_tile.h), one workgroup per 128 x 128 tile of C.
 __global__ void __launch_bounds__(256)
 dgemm_nn_kernel(const double *__restrict__ A, int lda, const double *__restrict__ B, int ldb, double *__restrict__ C,
                 int ldc, int Mr, int N, int K) {
-    constexpr int AS = GM_K + 1, BS = GM_T + 4;
-    __shared__ double As[2][GM_T * AS];
-    __shared__ double Bs[2][GM_K * BS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ri = lane & 15, kq = lane >> 4;
-    const int row0 = blockIdx.y * GM_T, col0 = blockIdx.x * GM_T;
-    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;   // wave's 64 x 64 sub-tile
-    d4_t acc[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) acc[u][v] = (d4_t){0.0, 0.0, 0.0, 0.0};
-
-    // global -> registers -> LDS, split so that the loads of chunk c+1 are in flight while chunk c is multiplied
-    double ra[GM_T * GM_K / 256], rb[GM_K * GM_T / 256];
-    auto gload = [&](int kc) {
-#pragma unroll
-        for (int u = 0; u < GM_T * GM_K / 256; u++) {
-            const int e = tid + 256 * u;
-            const int r = e / GM_K, k = e % GM_K;     // A tile: 128 rows x 16 k (128-byte runs per row)
-            const int gr = row0 + r;
-            ra[u] = gr < Mr ? A[(size_t)gr * lda + kc + k] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < GM_K * GM_T / 256; u++) {
-            const int e = tid + 256 * u;
-            const int k = e / GM_T, c = e % GM_T;     // B tile: 16 k x 128 columns (coalesced along the columns)
-            const int gc = col0 + c;
-            rb[u] = gc < N ? B[(size_t)(kc + k) * ldb + gc] : 0.0;
-        }
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < GM_T * GM_K / 256; u++) {
-            const int e = tid + 256 * u;
-            As[buf][(e / GM_K) * AS + e % GM_K] = ra[u];
-        }
-#pragma unroll
-        for (int u = 0; u < GM_K * GM_T / 256; u++) {
-            const int e = tid + 256 * u;
-            Bs[buf][(e / GM_T) * BS + e % GM_T] = rb[u];
-        }
-    };
-    const int nchunk = K / GM_K;
-    gload(0);
-    lstore(0);
-    __syncthreads();
-    for (int c = 0; c < nchunk; c++) {
-        const int buf = c & 1;
-        if (c + 1 < nchunk) gload((c + 1) * GM_K);
-        const double *as = As[buf], *bs = Bs[buf];
-#pragma unroll
-        for (int ks = 0; ks < GM_K / 4; ks++) {
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) a[u] = as[(wr + 16 * u + ri) * AS + 4 * ks + kq];
-#pragma unroll
-            for (int v = 0; v < 4; v++) b[v] = bs[(4 * ks + kq) * BS + wc + 16 * v + ri];
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-#pragma unroll
-                for (int v = 0; v < 4; v++) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[v], acc[u][v], 0, 0, 0);
-        }
-        if (c + 1 < nchunk) lstore(buf ^ 1);   // the other buffer was last read before the previous barrier
-        __syncthreads();
-    }
-    // C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const int gc = col0 + wc + 16 * v + ri;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int gr = row0 + wr + 16 * u + kq + 4 * r;
-                if (gr < Mr && gc < N) C[(size_t)gr * ldc + gc] = acc[u][v][r];
-            }
-        }
+    gemm_nn_128<false, false, int>(A, lda, B, ldb, C, ldc, blockIdx.y * GT_T, blockIdx.x * GT_T, Mr, N, K, 0, K / GT_K,
+                              nullptr, nullptr, 0);
 }
 
 // LDS of xi_table_kernel per knot: xs, ys, y2, 1/h, h^2/6 (5 doubles) and the 4 look-up cells (4 ints)
@@ -310,14 +232,14 @@ int corahip_legendre_project(corahip_ctx *ctx, const double *mu, const double *w
     ARG_CHECK(ctx != nullptr && mu && wt && xi && out && nm >= 1 && lmax >= 0 && ncol >= 1);
     StageTimer t(ctx, "legendre_project");
     const int L = lmax + 1;
-    const int Kp = (nm + GM_K - 1) / GM_K * GM_K;       // the GEMM runs K in chunks of 16: lm gets zero columns up to Kp
+    const int Kp = (nm + GT_K - 1) / GT_K * GT_K;       // the GEMM runs K in chunks of 16: lm gets zero columns up to Kp
     double *lm = nullptr;
     int rc = corahip_ctx_scratch(ctx, 4, sizeof(double) * (size_t)L * Kp, (void **)&lm);
     if (rc) return rc;
     legendre_matrix_kernel<<<(Kp + 255) / 256, 256, 0, ctx->stream>>>(mu, wt, nm, lmax, Kp, lm);
     LAUNCH_CHECK();
     ARG_CHECK(ncol <= 0x7fffffffL);
-    dim3 grid((unsigned)((ncol + GM_T - 1) / GM_T), (L + GM_T - 1) / GM_T);
+    dim3 grid((unsigned)((ncol + GT_T - 1) / GT_T), (L + GT_T - 1) / GT_T);
     const double *Bop = xi;
     if (Kp != nm) {
         // rows nm..Kp-1 of the B operand must exist (and be zero): zero-padded copy of xi

@@ -7,12 +7,13 @@
 //                          FP64 MFMA (v_mfma_f64_16x16x4_f64): M = channel, N = column, K = depth; the complex product
 //                          is four real MFMAs per step on (re, im) operand planes, -Im A formed in a register.
 //                          A workgroup owns 128 channels x 64 columns (4 waves of 64 x 32: 64 accumulator doubles per
-//                          lane); depth goes through a double-buffered LDS tile in chunks of 8 (chunks of 16 with
-//                          their staging registers spill).  The weight is formed in the kernel: the thread that
-//                          stages y[p, phi] multiplies it by e[p, phi] on the way to LDS (operand prologue) and keeps
-//                          the running sum of its e; the normaliser W[p] does not depend on the summation index, so
-//                          it is applied with `scale` in the epilogue, where the saturation and the product with the
-//                          intensity are done on the accumulators.  Nothing of the size of y is written.  The channel blocks of a column tile are neighbours in the grid, so for
+//                          lane; acc_tile, complex_mma and staged_k_loop of mfma_tile.h); depth goes through LDS in
+//                          chunks of 8 (chunks of 16 with their staging registers spill).  The weight is formed in the
+//                          kernel: the thread that stages y[p, phi] multiplies it by e[p, phi] on the way to LDS
+//                          (operand prologue) and keeps the running sum of its e; the normaliser W[p] does not depend
+//                          on the summation index, so it is applied with `scale` in the epilogue, where the saturation
+//                          and the product with the intensity are done on the accumulators.  Nothing of the size of y
+//                          is written.  The channel blocks of a column tile are neighbours in the grid, so for
 //                          nfreq > 128 the re-reads of y are served by the L2.  A [nfreq, nphi] comes from the L2.
 //                          No atomics; the order of every sum is fixed by the shape alone.
 //   cvar_*                 mean and variance of a complex array: block partials, one ordered final pass (twice: the
@@ -20,6 +21,7 @@
 //   faraday_pack_kernel    [R, npix] -> y[p, off + r]: LDS tile transpose, coalesced on both sides.
 // All element offsets are 64-bit.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -43,13 +45,12 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
     __shared__ double Ars[2][FM_BM * FM_LS], Ais[2][FM_BM * FM_LS];
     __shared__ double Brs[2][FM_BN * FM_LS], Bis[2][FM_BN * FM_LS];
     __shared__ double Wn[FM_BN];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ri = lane & 15, kq = lane >> 4;
+    const wave_roles<4, 2> w;                                       // a wave owns 64 channels x 32 columns
+    const int tid = w.tid, ri = w.ri, kq = w.kq, wr = w.wr, wc = w.wc;
     const int fb = (int)(blockIdx.x % (unsigned)nfb);
     const long cb = (long)(blockIdx.x / (unsigned)nfb);
     const int f0 = fb * FM_BM;
     const long col0 = cb * FM_BN;
-    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 32;
 
     // staging: element e = tid + 256 u is (row e / 8, depth e % 8): 8 lanes read one 128-byte run
     constexpr int SR = FM_NT / FM_KC;     // rows per staging step
@@ -63,8 +64,8 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
     }
     double2 ra[FM_NA], rb[FM_NB];
     double rphi = 0.0;
-    auto gload = [&](int kc) {
-        const int k = kc + sk;
+    auto gload = [&](int c) {
+        const int k = c * FM_KC + sk;
         const bool kin = k < nphi;
         rphi = kin ? phi[k] : 0.0;
 #pragma unroll
@@ -79,9 +80,9 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
         }
     };
     // operand prologue: y e on its way to LDS; the staging thread keeps the sum of its e (depths sk, sk + 8, ...)
-    auto lstore = [&](int buf, int kc) {
+    auto lstore = [&](int buf, int c) {
         double *Ar = Ars[buf], *Ai = Ais[buf], *Br = Brs[buf], *Bi = Bis[buf];
-        const bool kin = kc + sk < nphi;
+        const bool kin = c * FM_KC + sk < nphi;
 #pragma unroll
         for (int u = 0; u < FM_NA; u++) {
             Ar[(sr + SR * u) * FM_LS + sk] = ra[u].x;
@@ -97,23 +98,14 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
         }
     };
 
-    d4_t accr[4][2], acci[4][2];
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-        for (int v = 0; v < 2; v++) accr[u][v] = acci[u][v] = (d4_t){0.0, 0.0, 0.0, 0.0};
-
-    const int nchunk = (nphi + FM_KC - 1) / FM_KC;
-    gload(0);
-    lstore(0, 0);
-    __syncthreads();
-    for (int c = 0; c < nchunk; c++) {
-        const int buf = c & 1;
-        if (c + 1 < nchunk) gload((c + 1) * FM_KC);     // in flight while this chunk is multiplied
+    acc_tile<4, 2> accr, acci;
+    accr.zero();
+    acci.zero();
+    auto compute = [&](int, int buf) {
         const double *Ar = Ars[buf], *Ai = Ais[buf], *Br = Brs[buf], *Bi = Bis[buf];
 #pragma unroll
         for (int ks = 0; ks < FM_KC / 4; ks++) {
-            double br[2], bi[2];
+            double ar[4], ai[4], br[2], bi[2];
 #pragma unroll
             for (int v = 0; v < 2; v++) {
                 br[v] = Br[(wc + 16 * v + ri) * FM_LS + 4 * ks + kq];
@@ -121,21 +113,13 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                const double ar = Ar[(wr + 16 * u + ri) * FM_LS + 4 * ks + kq];
-                const double ai = Ai[(wr + 16 * u + ri) * FM_LS + 4 * ks + kq];
-                const double nai = -ai;
-#pragma unroll
-                for (int v = 0; v < 2; v++) {
-                    accr[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, br[v], accr[u][v], 0, 0, 0);
-                    accr[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(nai, bi[v], accr[u][v], 0, 0, 0);
-                    acci[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(ar, bi[v], acci[u][v], 0, 0, 0);
-                    acci[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(ai, br[v], acci[u][v], 0, 0, 0);
-                }
+                ar[u] = Ar[(wr + 16 * u + ri) * FM_LS + 4 * ks + kq];
+                ai[u] = Ai[(wr + 16 * u + ri) * FM_LS + 4 * ks + kq];
             }
+            complex_mma(accr, acci, ar, ai, br, bi);
         }
-        if (c + 1 < nchunk) lstore(buf ^ 1, (c + 1) * FM_KC);   // the other buffer was last read before the previous barrier
-        __syncthreads();
-    }
+    };
+    staged_k_loop((nphi + FM_KC - 1) / FM_KC, gload, lstore, compute);
 
     // normaliser: the 8 staging lanes of a column hold its partial sums; folded in a fixed order
 #pragma unroll
@@ -147,10 +131,11 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
     }
     __syncthreads();
 
-    // epilogue.  C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
+    // epilogue: normaliser and scale, saturation, product with the intensity; column blocks outermost, so that a block
+    // beyond ncol is left before its scale / W is formed
 #pragma unroll
     for (int v = 0; v < 2; v++) {
-        const int lc = wc + 16 * v + ri;
+        const int lc = wc + w.col(v);
         const long gc = col0 + lc;
         if (gc >= ncol) continue;
         const double fac = scale / Wn[lc];
@@ -158,9 +143,9 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
         for (int u = 0; u < 4; u++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const int gf = f0 + wr + 16 * u + kq + 4 * r;
+                const int gf = f0 + wr + w.row(u, r);
                 if (gf >= nfreq) continue;
-                const double zr = accr[u][v][r] * fac, zi = acci[u][v][r] * fac;
+                const double zr = accr.acc[u][v][r] * fac, zi = acci.acc[u][v][r] * fac;
                 const double s = sat_factor(zr, zi);
                 const double pr = zr * s, pi = zi * s;
                 if (MODE == 0) {
@@ -179,31 +164,7 @@ faraday_mix_kernel(const double2 *__restrict__ y, long ncol, int nphi, const dou
 
 // ---- complex mean / variance ---------------------------------------------------------------------------------------
 
-constexpr int CV_MAXB = 4096;
-
-// number of partials and elements per partial: a function of count alone
-inline void cvar_split(long count, int *nb, long *per) {
-    long b = (count + 8191) / 8192;
-    if (b > CV_MAXB) b = CV_MAXB;
-    if (b < 1) b = 1;
-    const long pr = (count + b - 1) / b;
-    *nb = (int)((count + pr - 1) / pr);
-    *per = pr;
-}
-
-// sums of 256 threads' (a, b) in a fixed order: lanes by halving shuffles, then the four waves in order
-__device__ inline void block_sum2(double &a, double &b, double *red) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        a += __shfl_down(a, o, 64);
-        b += __shfl_down(b, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[2 * wave] = a, red[2 * wave + 1] = b;
-    __syncthreads();
-    a = ((red[0] + red[2]) + red[4]) + red[6];
-    b = ((red[1] + red[3]) + red[5]) + red[7];
-}
+constexpr int CV_MAXB = 4096;     // partials_split gives at most this many
 
 // PASS 0: partial sums of (re, im).  PASS 1: partial sums of |y - m|^2 (second slot 0), m = out2[1..2].
 template <int PASS>
@@ -279,7 +240,7 @@ int corahip_complex_variance(corahip_ctx *ctx, const double *y, long count, doub
     ARG_CHECK(!overlaps(out2, 3 * sizeof(double), y, (size_t)count * 16));
     int nb;
     long per;
-    cvar_split(count, &nb, &per);
+    partials_split(count, 1, &nb, &per);
     void *work = nullptr;
     int rc = corahip_ctx_scratch(ctx, 10, (size_t)CV_MAXB * 2 * sizeof(double), &work);
     if (rc != 0) return rc;

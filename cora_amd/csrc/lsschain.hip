@@ -3,11 +3,12 @@
 // (LinearDynamics.process, :862-918), Fingers of God (FingersOfGod.process, :1162-1220) and the map
 // (BiasedLSSToMap.process, :944-993), with lssutil's diff2 and lognormal_transform.
 //
-//   slice_mix_kernel       out = K f, K [n, n]: FP64 MFMA (v_mfma_f64_16x16x4_f64), M = output slice, N = columns,
-//                          K-dimension = input slice.  A workgroup owns 128 output rows x 128 columns (4 waves of
-//                          64 x 64); for n <= 128 every element of f leaves HBM once and every element of out is
-//                          written once; for larger n the row blocks of a column tile are neighbours in the grid, so the
-//                          re-reads of f are served by the L2.  K comes through LDS from the L2.
+//   slice_mix_kernel       out = K f, K [n, n]: gemm_nn_128 of mfma_tile.h with M = output slice, N = columns,
+//                          K-dimension = input slice, the k ranges below and the 16-byte path for the f tile.  A
+//                          workgroup owns 128 output rows x 128 columns; for n <= 128 every element of f leaves HBM
+//                          once and every element of out is written once; for larger n the row blocks of a column tile
+//                          are neighbours in the grid, so the re-reads of f are served by the L2.  K comes through LDS
+//                          from the L2.
 //                          Skipping: per block of 16 output rows the host gives the range [klo, khi) of input slices
 //                          (multiples of the MFMA depth 4) whose K entries are not all exactly zero; MFMAs outside it
 //                          are not issued and chunks of 16 input slices outside the union of the workgroup's ranges
@@ -26,35 +27,24 @@
 
 #include "common.h"
 #include "glibc_exp.h"
+#include "mfma_tile.h"
 
 namespace {
 
-constexpr int SM_WAVES = 4;            // waves per workgroup
-constexpr int SM_T = 128, SM_K = 16;   // slice_mix: output tile edge, input slices per LDS chunk
-constexpr int SM_NT = 64 * SM_WAVES;   // threads per workgroup
-constexpr int SM_UT = 16 / SM_WAVES;   // 16-row tiles per wave: a wave owns 16 SM_UT rows x 64 columns
-
 // vec: ncol even and f 16-byte aligned, so that the f tile can be read 16 bytes per lane
-__global__ void __launch_bounds__(SM_NT, SM_WAVES / 2)
+__global__ void __launch_bounds__(GT_NT, 2)
 slice_mix_kernel(const double *__restrict__ K, const double *__restrict__ f, const int *__restrict__ rng, int n, long ncol,
                  int nrb, int vec, double *__restrict__ out) {
-    constexpr int AS = SM_K + 1, BS = SM_T + 4;
-    constexpr int NA = SM_T * SM_K / SM_NT, NB = SM_K * SM_T / SM_NT;
-    __shared__ double As[2][SM_T * AS];
-    __shared__ __attribute__((aligned(16))) double Bs[2][SM_K * BS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ri = lane & 15, kq = lane >> 4;
     const int rb = (int)(blockIdx.x % (unsigned)nrb);
     const long cb = (long)(blockIdx.x / (unsigned)nrb);
-    const int row0 = rb * SM_T;
-    const long col0 = cb * SM_T;
-    const int wr = (wave >> 1) * (16 * SM_UT), wc = (wave & 1) * 64;   // the wave's sub-tile
+    const int row0 = rb * GT_T;
+    const int wr = wave_roles<4, 4>().wr;
     const int n4 = (n + 3) & ~3;
 
     // ranges of the wave's 16-row tiles (wave-uniform) and their union over the workgroup's eight
-    int klo[SM_UT], khi[SM_UT], blo = n4, bhi = 0;
+    int klo[4], khi[4], blo = n4, bhi = 0;
 #pragma unroll
-    for (int t = 0; t < SM_T / 16; t++) {
+    for (int t = 0; t < GT_T / 16; t++) {
         const int r16 = row0 + 16 * t;
         int lo = 0, hi = 0;
         if (r16 < n) {
@@ -65,118 +55,18 @@ slice_mix_kernel(const double *__restrict__ K, const double *__restrict__ f, con
             if (hi > lo) blo = min(blo, lo), bhi = max(bhi, hi);
         }
 #pragma unroll
-        for (int u = 0; u < SM_UT; u++)
+        for (int u = 0; u < 4; u++)
             if (t == (wr >> 4) + u) klo[u] = lo, khi[u] = hi;
     }
 #pragma unroll
-    for (int u = 0; u < SM_UT; u++) {
+    for (int u = 0; u < 4; u++) {
         klo[u] = __builtin_amdgcn_readfirstlane(klo[u]);
         khi[u] = __builtin_amdgcn_readfirstlane(khi[u]);
     }
-    d4_t acc[SM_UT][4];
-#pragma unroll
-    for (int u = 0; u < SM_UT; u++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) acc[u][v] = (d4_t){0.0, 0.0, 0.0, 0.0};
-
-    // global -> registers -> LDS, split so that the loads of chunk c+1 are in flight while chunk c is multiplied
-    double ra[NA], rb0[NB];
-    auto gload_a = [&](int kc) {
-#pragma unroll
-        for (int u = 0; u < NA; u++) {
-            const int e = tid + SM_NT * u;
-            const int r = e / SM_K, k = e % SM_K;     // K tile: 128 rows x 16 input slices (128-byte runs per row)
-            const int gr = row0 + r;
-            ra[u] = (gr < n && kc + k < n) ? K[(size_t)gr * n + kc + k] : 0.0;
-        }
-    };
-    auto gload_b = [&](double(&rbv)[NB], int kc) {
-        if (vec) {
-#pragma unroll
-            for (int u = 0; u < NB / 2; u++) {
-                const int e = tid + SM_NT * u;
-                const int k = e / (SM_T / 2), c = 2 * (e % (SM_T / 2));     // f tile: 16 input slices x 64 column pairs
-                const long gc = col0 + c;                                   // even, ncol even: the pair is inside or outside
-                double2 x = make_double2(0.0, 0.0);
-                if (kc + k < n && gc < ncol) x = *reinterpret_cast<const double2 *>(f + (size_t)(kc + k) * (size_t)ncol + (size_t)gc);
-                rbv[2 * u] = x.x, rbv[2 * u + 1] = x.y;
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < NB; u++) {
-                const int e = tid + SM_NT * u;
-                const int k = e / SM_T, c = e % SM_T;     // f tile: 16 input slices x 128 columns (coalesced along the columns)
-                const long gc = col0 + c;
-                rbv[u] = (kc + k < n && gc < ncol) ? f[(size_t)(kc + k) * (size_t)ncol + (size_t)gc] : 0.0;
-            }
-        }
-    };
-    auto lstore = [&](int buf, const double(&rbv)[NB]) {
-#pragma unroll
-        for (int u = 0; u < NA; u++) {
-            const int e = tid + SM_NT * u;
-            As[buf][(e / SM_K) * AS + e % SM_K] = ra[u];
-        }
-        if (vec) {
-#pragma unroll
-            for (int u = 0; u < NB / 2; u++) {
-                const int e = tid + SM_NT * u;
-                *reinterpret_cast<double2 *>(&Bs[buf][(e / (SM_T / 2)) * BS + 2 * (e % (SM_T / 2))]) =
-                    make_double2(rbv[2 * u], rbv[2 * u + 1]);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < NB; u++) {
-                const int e = tid + SM_NT * u;
-                Bs[buf][(e / SM_T) * BS + e % SM_T] = rbv[u];
-            }
-        }
-    };
-    const int kbeg = blo / SM_K * SM_K;
-    const int nchunk = bhi > blo ? (bhi - kbeg + SM_K - 1) / SM_K : 0;
-    if (nchunk > 0) {
-        gload_a(kbeg);
-        gload_b(rb0, kbeg);
-        lstore(0, rb0);
-    }
-    __syncthreads();
-    for (int c = 0; c < nchunk; c++) {
-        const int buf = c & 1, kc = kbeg + c * SM_K;
-        if (c + 1 < nchunk) {
-            gload_a(kc + SM_K);
-            gload_b(rb0, kc + SM_K);
-        }
-        const double *as = As[buf], *bs = Bs[buf];
-#pragma unroll
-        for (int ks = 0; ks < SM_K / 4; ks++) {
-            const int k4 = kc + 4 * ks;
-            double b[4];
-#pragma unroll
-            for (int v = 0; v < 4; v++) b[v] = bs[(4 * ks + kq) * BS + wc + 16 * v + ri];
-#pragma unroll
-            for (int u = 0; u < SM_UT; u++) {
-                if (k4 >= klo[u] && k4 < khi[u]) {        // wave-uniform
-                    const double a = as[(wr + 16 * u + ri) * AS + 4 * ks + kq];
-#pragma unroll
-                    for (int v = 0; v < 4; v++) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[v], acc[u][v], 0, 0, 0);
-                }
-            }
-        }
-        if (c + 1 < nchunk) lstore(buf ^ 1, rb0);   // the other buffer was last read before the previous barrier
-        __syncthreads();
-    }
-    // C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
-#pragma unroll
-    for (int u = 0; u < SM_UT; u++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const long gc = col0 + wc + 16 * v + ri;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int gr = row0 + wr + 16 * u + kq + 4 * r;
-                if (gr < n && gc < ncol) out[(size_t)gr * (size_t)ncol + (size_t)gc] = acc[u][v][r];
-            }
-        }
+    // chunks of 16 input slices outside the union are not loaded
+    const int kbeg = blo / GT_K * GT_K;
+    const int nchunk = bhi > blo ? (bhi - kbeg + GT_K - 1) / GT_K : 0;
+    gemm_nn_128<true, true, long>(K, n, f, ncol, out, ncol, row0, cb * GT_T, n, ncol, n, kbeg, nchunk, klo, khi, vec);
 }
 
 template <int V> struct vec_of { typedef double type; };
@@ -249,7 +139,7 @@ slice_diff2_kernel(const double *__restrict__ f, const double *__restrict__ coef
 }
 
 // partial sums of row i over the columns [b per, (b + 1) per): work[(i nb + b) 2 + (0, 1)] = sum (f - c), sum (f - c)^2.
-// Fixed order: a thread adds its strided elements in sequence, lanes fold by shuffles, waves through LDS.
+// Fixed order: a thread adds its strided elements in sequence, then block_sum2.
 template <int V>
 __global__ void __launch_bounds__(256)
 slice_moments_partial_kernel(const double *__restrict__ f, long ld, const double *__restrict__ c, int n, long ncol, int nb,
@@ -275,19 +165,9 @@ slice_moments_partial_kernel(const double *__restrict__ f, long ld, const double
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_down(s1, o, 64);
-        s2 += __shfl_down(s2, o, 64);
-    }
     __shared__ double red[8];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[2 * wave] = s1, red[2 * wave + 1] = s2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        work[(size_t)blockIdx.x * 2] = ((red[0] + red[2]) + red[4]) + red[6];
-        work[(size_t)blockIdx.x * 2 + 1] = ((red[1] + red[3]) + red[5]) + red[7];
-    }
+    block_sum2(s1, s2, red);
+    if (threadIdx.x == 0) work[(size_t)blockIdx.x * 2] = s1, work[(size_t)blockIdx.x * 2 + 1] = s2;
 }
 
 __global__ void __launch_bounds__(256)
@@ -365,16 +245,6 @@ lognormal_kernel(const double *f, const double *__restrict__ hv, const double *_
     }
 }
 
-// nb (partials per row) and per (columns per partial, even) of slice_moments
-inline void moments_split(long ncol, int *nb, long *per) {
-    long b = (ncol + 8191) / 8192;
-    if (b > 4096) b = 4096;
-    long pr = (ncol + b - 1) / b;
-    pr = (pr + 1) & ~1L;
-    *nb = (int)((ncol + pr - 1) / pr);
-    *per = pr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -386,11 +256,11 @@ int corahip_slice_mix(corahip_ctx *ctx, const double *K, const double *f, const 
     ARG_CHECK(ranges == nullptr || is_aligned(ranges, 4));
     const size_t nbytes = (size_t)n * (size_t)ncol * 8;
     ARG_CHECK(!overlaps(out, nbytes, f, nbytes) && !overlaps(out, nbytes, K, (size_t)n * n * 8));
-    const long nrb = (n + SM_T - 1) / SM_T, ncb = (ncol + SM_T - 1) / SM_T;
+    const long nrb = (n + GT_T - 1) / GT_T, ncb = (ncol + GT_T - 1) / GT_T;
     ARG_CHECK(nrb * ncb <= 0x7fffffffL);
     StageTimer t(ctx, "slice_mix");
     const int vec = (ncol & 1) == 0 && is_aligned(f, 16);
-    hipLaunchKernelGGL(slice_mix_kernel, dim3((unsigned)(nrb * ncb)), dim3(SM_NT), 0, ctx->stream, K, f, ranges, n, ncol,
+    hipLaunchKernelGGL(slice_mix_kernel, dim3((unsigned)(nrb * ncb)), dim3(GT_NT), 0, ctx->stream, K, f, ranges, n, ncol,
                        (int)nrb, vec, out);
     LAUNCH_CHECK();
     return 0;
@@ -424,7 +294,7 @@ int corahip_slice_moments_workspace_bytes(int n, long ncol, size_t *bytes) {
     ARG_CHECK(bytes && n >= 1 && ncol >= 1);
     int nb;
     long per;
-    moments_split(ncol, &nb, &per);
+    partials_split(ncol, 2, &nb, &per);     // per even: the 16-byte path reads pairs
     *bytes = (size_t)n * nb * 2 * sizeof(double);
     return 0;
 }
@@ -435,7 +305,7 @@ int corahip_slice_moments(corahip_ctx *ctx, const double *f, long ld, const doub
     ARG_CHECK(is_aligned(f, 8) && is_aligned(work, 8));
     int nb;
     long per;
-    moments_split(ncol, &nb, &per);
+    partials_split(ncol, 2, &nb, &per);     // per even: the 16-byte path reads pairs
     ARG_CHECK(work_bytes >= (size_t)n * nb * 2 * sizeof(double));
     ARG_CHECK((long)n * nb <= 0x7fffffffL);
     StageTimer t(ctx, "slice_moments");

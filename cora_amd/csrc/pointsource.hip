@@ -38,21 +38,6 @@ constexpr uint32_t PS_DOMAIN = 0x50535243u;     // "PSRC": counter word 3 of eve
 constexpr int PS_UD_MAXK = 6;                   // ud_grade degrades by at most 2^6 in nside: one thread walks the 4^k children
 constexpr int PS_LONG = 16;                     // pixels with more sources than this are summed by the wave
 
-__device__ inline void philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t key, uint32_t (&out)[4]) {
-    uint32_t c[4] = {c0, c1, c2, c3};
-    uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c[0];
-    out[1] = c[1];
-    out[2] = c[2];
-    out[3] = c[3];
-}
-
 __device__ inline double uniform53(uint32_t hi, uint32_t lo) {
     return (double)(((uint64_t)hi << 21) | (uint64_t)(lo >> 11)) * 0x1p-53;     // < 2^53: the conversion is exact
 }
@@ -66,8 +51,8 @@ __global__ __launch_bounds__(256) void ps_population_kernel(uint64_t seed, long 
 #pragma clang fp contract(off)
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         uint32_t a[4], b[4];
-        philox4((uint32_t)i, (uint32_t)((uint64_t)i >> 32), 0u, PS_DOMAIN, seed, a);
-        philox4((uint32_t)i, (uint32_t)((uint64_t)i >> 32), 1u, PS_DOMAIN, seed, b);
+        philox4x32_10((uint32_t)i, (uint32_t)((uint64_t)i >> 32), 0u, PS_DOMAIN, seed, a);
+        philox4x32_10((uint32_t)i, (uint32_t)((uint64_t)i >> 32), 1u, PS_DOMAIN, seed, b);
         const double u1 = uniform53(a[0], a[1]), u2 = uniform53(a[2], a[3]);
         const double z = rng_boxmuller_bits(b).x;
         // xs[lo] <= u1 < xs[hi]: xs[0] = 0 and xs[nk - 1] = 1 bracket every u1 in [0, 1)

@@ -25,8 +25,8 @@ __device__ static inline void philox_round(uint32_t (&c)[4], uint32_t k0, uint32
     c[3] = n3;
 }
 
-__device__ static inline void philox4x32_10(uint64_t counter, uint64_t key, uint32_t (&out)[4]) {
-    uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), 0u, 0u};
+__device__ static inline void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t key, uint32_t (&out)[4]) {
+    uint32_t c[4] = {c0, c1, c2, c3};
     uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
 #pragma unroll
     for (int r = 0; r < 10; r++) {
@@ -38,6 +38,10 @@ __device__ static inline void philox4x32_10(uint64_t counter, uint64_t key, uint
     out[1] = c[1];
     out[2] = c[2];
     out[3] = c[3];
+}
+// a 64-bit counter: words (lo, hi, 0, 0)
+__device__ static inline void philox4x32_10(uint64_t counter, uint64_t key, uint32_t (&out)[4]) {
+    philox4x32_10((uint32_t)counter, (uint32_t)(counter >> 32), 0u, 0u, key, out);
 }
 
 // Box-Muller in FP64 with short, branch-free kernels (the generic libm log/sincospi cost ~130 DP instructions

@@ -9,10 +9,10 @@
 //                          or ny are not multiplied.  Every (l, m) element of an operand is one contiguous row of 8 G
 //                          doubles [G][2][4]; the 128 channels of a tile are 256 contiguous doubles of it, staged as they
 //                          are: 16-byte loads (128 lanes cover the 2 KiB of a row), 16-byte LDS stores, CS_KM rows of m
-//                          per chunk, LDS and registers double-buffered so that the loads of chunk c+1 are in flight
-//                          while chunk c is multiplied.  LDS pitch 256 doubles, no padding: a fragment read
-//                          (ds_read_b64) of lanes 0-31 = (16 channels) x (Re, Im) covers 32 consecutive doubles = all 64
-//                          banks once, lanes 32-63 the same in the next row (tools/lds_bank_sim.py spectra).
+//                          per chunk, on the schedule and the accumulator tile of mfma_tile.h.  LDS pitch 256 doubles,
+//                          no padding: a fragment read (ds_read_b64) of lanes 0-31 = (16 channels) x (Re, Im) covers 32
+//                          consecutive doubles = all 64 banks once, lanes 32-63 the same in the next row
+//                          (tools/lds_bank_sim.py spectra).
 //                          c_m: the chunks run over m = 1 .. l first, then every accumulator is doubled (exact), then one
 //                          last MFMA adds m = 0 - no operand is scaled, so the symmetric case needs one staged operand on
 //                          diagonal tiles.  1 / (2l+1): one correctly rounded division per output in the epilogue.
@@ -27,6 +27,7 @@
 //                          >= n of the MFMA result, which are not stored.  Groups beyond G are staged as zeros.
 // All element offsets are 64-bit (nalm * 8 G exceeds 2^31 at 256 channels, lmax 2048).
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace {
 
@@ -42,9 +43,13 @@ cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double 
                      int sym, int nty, int ntiles, double *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) double As[2][CS_KM * CS_P];
     __shared__ __attribute__((aligned(16))) double Bs[2][CS_KM * CS_P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ri = lane & 15, kq = lane >> 4;
-    const int l = lmax - (int)(blockIdx.x / (unsigned)ntiles);      // descending l
+    const wave_roles<4, 4> w;                                       // a wave owns 64 x 64 of the tile
+    const int tid = w.tid, ri = w.ri, kq = w.kq, wr = w.wr, wc = w.wc;
+    // descending l.  The quotient comes out of the VALU; the chunk loop it bounds is controlled by the SALU only if l is
+    // in an SGPR.  __builtin_amdgcn_readfirstlane does not get it there: l is provably uniform, the compiler folds the
+    // call away and then keeps l in a VGPR (v_cmp loop control, 6 more VGPRs).  The register constraint cannot be folded.
+    int l = lmax - (int)(blockIdx.x / (unsigned)ntiles);
+    asm("" : "+s"(l));
     int t = (int)(blockIdx.x % (unsigned)ntiles), ti, tj;
     if (sym) {
         ti = 0;
@@ -55,15 +60,11 @@ cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double 
     }
     const bool diag = sym && ti == tj;
     const int row0 = ti * CS_T, col0 = tj * CS_T;
-    const int wr = (wave >> 1) * 64, wc = (wave & 1) * 64;          // the wave's sub-tile
     const bool active = !(diag && wr < wc);                         // above the diagonal: mirrored from (wc, wr)
     const bool mirror = sym && (!diag || wr > wc);
 
-    d4_t acc[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-        for (int v = 0; v < 4; v++) acc[u][v] = (d4_t){0.0, 0.0, 0.0, 0.0};
+    acc_tile<4, 4> acc;
+    acc.zero();
     int msk = 0;                                                    // 16-blocks inside the operands: bits 0-3 rows, 4-7 columns
 #pragma unroll
     for (int u = 0; u < 4; u++) {
@@ -79,7 +80,7 @@ cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double 
     const int nch = (l + CS_KM - 1) / CS_KM, ntot = nch + 1;
     const int sr = tid >> 7, sq = 2 * (tid & 127);                  // staging: row (+ 2 u), double offset in the row
     double2 ra[CS_NV], rb[CS_NV];
-    auto gload = [&](double2(&rv)[CS_NV], const double *__restrict__ X, int G, int x0, int c) {
+    auto gload1 = [&](double2(&rv)[CS_NV], const double *__restrict__ X, int G, int x0, int c) {
         const int d = 2 * x0 + sq;                                  // offset in the (l, m) row of 8 G doubles
 #pragma unroll
         for (int u = 0; u < CS_NV; u++) {
@@ -91,54 +92,37 @@ cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double 
             rv[u] = x;
         }
     };
-    auto lstore = [&](double *S, const double2(&rv)[CS_NV]) {
+    auto lstore1 = [&](double *S, const double2(&rv)[CS_NV]) {
 #pragma unroll
         for (int u = 0; u < CS_NV; u++) *reinterpret_cast<double2 *>(&S[(sr + 2 * u) * CS_P + sq]) = rv[u];
     };
-    gload(ra, A, Ga, row0, 0);
-    lstore(As[0], ra);
-    if (!diag) {
-        gload(rb, B, Gb, col0, 0);
-        lstore(Bs[0], rb);
-    }
-    __syncthreads();
+    // a diagonal tile stages one operand and reads both fragments from it
+    auto gload = [&](int c) {
+        gload1(ra, A, Ga, row0, c);
+        if (!diag) gload1(rb, B, Gb, col0, c);
+    };
+    auto lstore = [&](int buf, int) {
+        lstore1(As[buf], ra);
+        if (!diag) lstore1(Bs[buf], rb);
+    };
     // fragment position of channel c of the tile, value (Re, Im) = kq & 1: 8 (c / 4) + 4 (kq & 1) + c % 4
     const int fo = 8 * (ri >> 2) + 4 * (kq & 1) + (ri & 3) + (kq >> 1) * CS_P;
-    for (int c = 0; c < ntot; c++) {
-        const int buf = c & 1;
-        if (c + 1 < ntot) {
-            gload(ra, A, Ga, row0, c + 1);
-            if (!diag) gload(rb, B, Gb, col0, c + 1);
-        }
+    auto compute = [&](int c, int buf) {
         const double *as = As[buf], *bs = diag ? As[buf] : Bs[buf];
-        if (c == nch) {                                             // c_m = 2 of everything added so far
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-#pragma unroll
-                for (int v = 0; v < 4; v++) acc[u][v] = acc[u][v] * 2.0;
-        }
-        auto step = [&](int ks) {
+        if (c == nch) acc.scale(2.0);                               // c_m = 2 of everything added so far
+        const int nks = c == nch ? 1 : CS_KM / 2;                   // m = 0: one step (row 1 of that chunk is zero)
+        for (int ks = 0; ks < nks; ks++) {                          // (not unrolled: 4 steps of fragments do not fit beside 128 accumulators)
             double a[4], b[4];
 #pragma unroll
             for (int v = 0; v < 4; v++) {
                 a[v] = as[2 * ks * CS_P + 2 * (wr + 16 * v) + fo];
                 b[v] = bs[2 * ks * CS_P + 2 * (wc + 16 * v) + fo];
             }
-#pragma unroll
-            for (int u = 0; u < 4; u++)
-#pragma unroll
-                for (int v = 0; v < 4; v++)
-                    if (ua[u] && va[v]) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[v], acc[u][v], 0, 0, 0);
-        };
-        const int nks = c == nch ? 1 : CS_KM / 2;                   // m = 0: one step (row 1 of that chunk is zero)
-        for (int ks = 0; ks < nks; ks++) step(ks);                  // (not unrolled: 4 steps of fragments do not fit beside 128 accumulators)
-        if (c + 1 < ntot) {                                         // the other buffer was last read before the previous barrier
-            lstore(As[buf ^ 1], ra);
-            if (!diag) lstore(Bs[buf ^ 1], rb);
+            acc.mma_if(a, b, ua, va);
         }
-        __syncthreads();
-    }
-    // C/D layout: column = lane & 15, row = (lane >> 4) + 4 r
+    };
+    staged_k_loop(ntot, gload, lstore, compute);
+
     const double dl = (double)(2 * l + 1);
     double *ol = out + (size_t)l * (size_t)nx * (size_t)ny;
 #pragma unroll
@@ -146,12 +130,12 @@ cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double 
 #pragma unroll
         for (int v = 0; v < 4; v++) {
             if (!(ua[u] && va[v])) continue;
-            const int gc = col0 + wc + 16 * v + ri;
+            const int gc = col0 + wc + w.col(v);
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const int gr = row0 + wr + 16 * u + kq + 4 * r;
+                const int gr = row0 + wr + w.row(u, r);
                 if (gr < nx && gc < ny) {
-                    const double x = acc[u][v][r] / dl;
+                    const double x = acc.acc[u][v][r] / dl;
                     ol[(size_t)gr * (size_t)ny + (size_t)gc] = x;
                     if (mirror) ol[(size_t)gc * (size_t)ny + (size_t)gr] = x;
                 }
