@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/corahip.h"
@@ -182,6 +183,15 @@ __host__ __device__ static inline long alm_idx(int l, int m, int lmax) {
 }
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>), in order
+template <int N, int J = 0, class Fn>
+__device__ static inline void static_for(Fn &&f) {
+    if constexpr (J < N) {
+        f(std::integral_constant<int, J>{});
+        static_for<N, J + 1>(f);
+    }
+}
 
 // sums of 256 threads' (a, b) in a fixed order, returned to every thread: lanes by halving __shfl_down from 32 to 1,
 // then ((w0 + w1) + w2) + w3 over the four waves through red[8] (LDS)

@@ -177,15 +177,6 @@ __device__ unsigned long long g_draw_stamps[8];
 #define DSTAMP(k)
 #endif
 
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>), in order
-template <int N, int J = 0, class Fn>
-__device__ static inline void draw_static_for(Fn &&f) {
-    if constexpr (J < N) {
-        f(std::integral_constant<int, J>{});
-        draw_static_for<N, J + 1>(f);
-    }
-}
-
 #define DRAW_WAVES 8                 // waves per workgroup of the fused-RNG kernel
 #define DRAW_MB (16 * DRAW_WAVES)    // m per work item
 #define DRAW_NBUF 3                  // stages in the LDS ring
@@ -425,7 +416,7 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
             }
             DSTAMP(3);                       // generator + MFMAs of the chunk
         }
-        draw_static_for<(NC + DRAW_KC - 1) / DRAW_KC>([&](auto jc) {
+        static_for<(NC + DRAW_KC - 1) / DRAW_KC>([&](auto jc) {
             constexpr int J = decltype(jc)::value;
             if (c >= nchunk) return;         // (uniform; also the dense / unaligned case, where c == nchunk here)
             chunk_begin(c);

@@ -113,6 +113,29 @@ static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 #define LEG_NBUF 2     // LDS stage ring: one being read + one in flight
 #endif
 
+// LDS stage ring of the two K4 kernels, for the kernel and its launcher: NT 16-column tiles, KT rows of l per stage,
+// NBUF stages, XROWS doubles per coefficient row beyond the recurrence pair (0 scalar, 4 spin 2: its g table)
+template <int NT, int KT, int NBUF, int XROWS>
+struct leg_geom {
+    static constexpr int TCOLS = 16 * NT;          // columns of a block
+    static constexpr int STRIDE = TCOLS + 8;       // LDS row stride (doubles): 2 rows apart = 128 B mod 256
+    static constexpr int CROWS = KT + 8;           // coefficient rows per stage (staggered lanes look 6 ahead)
+    static constexpr int STAGE = KT * STRIDE + (2 + XROWS) * CROWS;   // doubles per stage: a_lm rows + coefficient rows
+    static constexpr size_t LDS_BYTES = sizeof(double) * NBUF * STAGE + 16;   // dynamic LDS: the ring + the next-item slots behind it
+};
+
+// min / max over the wave, wave-uniform (an SGPR): tests on it are scalar compares
+__device__ static inline int wave_min(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ static inline int wave_max(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
 // LDS-DMA issued from inline asm: hipcc does not count it, so it does not drain the DMA with a
 // vmcnt(0) in front of every later ds_read (which it does for the builtin: the DMA is a pending LDS
 // write it cannot disambiguate).  The kernel waits itself: s_waitcnt vmcnt(0) before the stage barrier.

@@ -2,13 +2,6 @@
 // spin-2 (legendre_pol_kernel) forms, and their launchers.  See sht_internal.h.
 #include "sht_internal.h"
 
-#ifndef LEG_ST_UNROLL
-#define LEG_ST_UNROLL 1   // unroll factor of the stage loop (3 would make the LDS ring offsets immediates)
-#endif
-#ifndef LEG_MS_UNROLL
-#define LEG_MS_UNROLL 7   // (= LEG_KT / 8 at the shipped stage length; only the rolled head / tail stages use it) macro-step loop of a stage fully unrolled (loop counters and pointer increments become immediates): 71.0 -> 69.5 ms; factors 2 and 3: no change
-#endif
-
 #ifndef LEG_STAMPS
 #define LEG_STAMPS 0      // diagnostic build (make ab ... DEFS=-DLEG_STAMPS=1): s_memtime per phase of the item loop, summed over the workgroups' first waves
 #endif
@@ -52,10 +45,8 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
                 const double2 *__restrict__ seed, const int2 *__restrict__ items, int nitems,
                 const double *__restrict__ alm, const double *__restrict__ zeros, double *__restrict__ inter,
                 unsigned *__restrict__ queue) {
-    constexpr int TCOLS = 16 * NT;          // columns of this block
-    constexpr int STRIDE = TCOLS + 8;       // LDS row stride (doubles): 2 rows apart = 128 B mod 256
-    constexpr int CROWS = LEG_KT + 8;       // coefficient rows per stage (staggered lanes look 6 ahead)
-    constexpr int STAGE = LEG_KT * STRIDE + 2 * CROWS;  // doubles per stage: a_lm rows + (A,B) pairs
+    using geom = leg_geom<NT, LEG_KT, LEG_NBUF, 0>;
+    constexpr int TCOLS = geom::TCOLS, STRIDE = geom::STRIDE, CROWS = geom::CROWS, STAGE = geom::STAGE;
     constexpr int RPW = LEG_KT / LEG_WAVES;             // a_lm rows each wave moves per stage
     constexpr int PIECES = RPW + 1;                     // LDS-DMA pieces per wave per stage (+ coefficients)
     constexpr int TRINGS = LEG_RINGS * RT;              // ring pairs per workgroup
@@ -233,16 +224,10 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
             }
             // wave-uniform bounds of the start rows: the skip tests of the macro-step loop become scalar compares
             // (every vector instruction there costs issue time next to the MFMAs)
-            int ws_min = ls_min, ws_maxinj = -1;
+            int maxinj = -1;
 #pragma unroll
-            for (int q = 0; q < RT; q++) ws_maxinj = max(ws_maxinj, inj_l[q] == 0x7fffffff ? -1 : inj_l[q]);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                ws_min = min(ws_min, __shfl_xor(ws_min, o));
-                ws_maxinj = max(ws_maxinj, __shfl_xor(ws_maxinj, o));
-            }
-            ws_min = __builtin_amdgcn_readfirstlane(ws_min);
-            ws_maxinj = __builtin_amdgcn_readfirstlane(ws_maxinj);
+            for (int q = 0; q < RT; q++) maxinj = max(maxinj, inj_l[q] == 0x7fffffff ? -1 : inj_l[q]);
+            const int ws_min = wave_min(ls_min), ws_maxinj = wave_max(maxinj);
             // The ring's loads (z, first row, seed pair) are CONSUMED here.  Left to the compiler, the wait for the seed pair
             // lands at its only use - the injection branch inside the macro-step loop - and where its registers are
             // reused in the epilogue, as an s_waitcnt vmcnt(0): vmcnt is in order, so that wait also drains every LDS-DMA
@@ -250,7 +235,7 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
 #pragma unroll
             for (int q = 0; q < RT; q++) asm volatile("" ::"v"(x[q]), "v"(sd[q].x), "v"(sd[q].y), "v"(my_ls[q]));
 
-            // Stage loop in three consecutive pieces (same body, leg_stage_body.inc): the head stages in which rings of
+            // Stage loop in three consecutive pieces (same body, `stage` below): the head stages in which rings of
             // the wave still start, the steady-state stages - every ring runs, none starts, every row <= lmax - whose
             // macro-steps carry no tests at all and are fully unrolled (every scalar compare / branch / loop increment
             // costs issue time next to the MFMAs), and the tail stage that overhangs lmax.
@@ -265,40 +250,115 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
             int st_hi = min(min((lmax - w.l_begin + 1) / LEG_KT, (w.row_limit + 1) / LEG_KT - LEG_NBUF + 1),
                             w.nstage - LEG_NBUF + 1);
             st_hi = __builtin_amdgcn_readfirstlane(st_hi);
+            // One stage = LEG_KT rows of l.  CLEAN: 1 steady-state stages (no tests at all), 2 head stages whose rows all
+            // exist (unrolled like the steady-state ones, fast refill pieces, but rings of the wave may still enter: the
+            // wave-uniform skip tests and the entry select stay), 0 the rolled generic form (tail stages, and heads of
+            // items too short for the fast pieces).
+            auto stage = [&](auto clean, const int st) __attribute__((always_inline)) {
+                constexpr int CLEAN = decltype(clean)::value;
+                // own pieces of stage st have landed when at most the pieces of the (up to LEG_NBUF-2) younger
+                // stages are still in flight (anything younger than those only makes the wait stricter)
+                if (LEG_NBUF >= 4 && st + 2 < w.nstage) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PIECES) : "memory");
+                else if (LEG_NBUF >= 3 && st + 1 < w.nstage) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();  // everyone's pieces of stage st landed; everyone is done reading stage st-1
+#if LEG_STAMPS
+                if constexpr (!CLEAN) LEG_STAMP(t_tbar);
+#endif
+                const bool refill = CLEAN ? true : (st + LEG_NBUF - 1 < w.nstage);   // (the clean loops only take refilling stages)
+                if (refill) issue_coef(w, st + LEG_NBUF - 1);
+                const int ls = w.l_begin + st * LEG_KT;
+                const double *sb = lds + (st % LEG_NBUF) * STAGE;
+                const double2 *sc = reinterpret_cast<const double2 *>(sb + LEG_KT * STRIDE) + d;
+                // per-stage scalars of the fast refill pieces (CLEAN stages only)
+                const char *const rsrc = reinterpret_cast<const char *>(w.src0) +
+                                         (unsigned)(((st + LEG_NBUF - 1) * LEG_KT + wv) * ncols) * 8u;
+                const unsigned rdst = __builtin_amdgcn_readfirstlane(
+                    lds_base_bytes + (unsigned)((((st + LEG_NBUF - 1) % LEG_NBUF) * STAGE + wv * STRIDE) * sizeof(double)));
+                // One macro-step (8 consecutive l, 16 MFMAs in the <8,1> shape).  `ms` is its index inside the stage: an
+                // integral_constant in the CLEAN stages, so that every LDS offset and the LDS-DMA destination of the
+                // refill piece are immediates, and the loop variable in the rolled stages.
+                auto macro_step = [&](auto ms) __attribute__((always_inline)) {
+                    // one a_lm piece of the stage being refilled per macro-step: spreads the LDS-DMA issue
+                    // over the MFMA work instead of an 8-wave burst behind the barrier (measured 7 % of time)
+                    if constexpr (CLEAN != 0) {
+                        static_for<RPM>([&](auto r) {
+                            constexpr int P = decltype(ms)::value * RPM + decltype(r)::value;
+                            issue_row_fast(rsrc, rdst, std::integral_constant<int, P>{});
+                        });
+                    } else if (refill) {
+#pragma unroll
+                        for (int r = 0; r < RPM; r++) issue_row(w, st + LEG_NBUF - 1, ms * RPM + r);
+                    }
+                    const int l0 = ls + 8 * ms;
+                    if (!CLEAN && l0 > lmax) return;
+                    // nothing of this wave starts before l0+14: skip the macro-step entirely
+                    if (CLEAN != 1 && ws_min > l0 + 13) return;
+                    double ae[RT], ao[RT];
+                    double2 c[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) c[j] = sc[8 * ms + j];
+                    if (CLEAN != 1 && ws_maxinj >= l0) {   // (scalar) some ring of the wave may still enter at or after this macro-step
+                        const int lf = l0 + d;             // entry rows are window starts of the lane (plan: d_seed4)
+#pragma unroll
+                        for (int q = 0; q < RT; q++) {
+                            const bool inj = (inj_l[q] == lf);
+                            p0[q] = inj ? sd[q].x : p0[q];
+                            p1[q] = inj ? sd[q].y : p1[q];
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+#pragma unroll
+                        for (int q = 0; q < RT; q++) {
+                            const double vv = fma(c[j].x * x[q], p1[q], -p0[q]);
+                            p0[q] = p1[q];
+                            p1[q] = vv;
+                            if (j == 0) ae[q] = vv * c[0].y;      // lambda = s mu
+                            if (j == 1) ao[q] = vv * c[1].y;
+                        }
+                    }
+                    if (CLEAN != 1 && ws_min > l0 + 7) return;  // all A operands of this macro-step are zero
+#if LEG_STAMPS
+                    if constexpr (!CLEAN) n_tail_ms++;
+#endif
+                    const double *be = sb + (8 * ms + d) * STRIDE + ri;
+                    const double *bo = be + STRIDE;
+#pragma unroll
+                    for (int t = 0; t < NT; t++) {
+                        const double bev = be[16 * t], bov = bo[16 * t];
+#pragma unroll
+                        for (int q = 0; q < RT; q++) {
+                            acce[q][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[q], bev, acce[q][t], 0, 0, 0);
+                            acco[q][t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ao[q], bov, acco[q][t], 0, 0, 0);
+                        }
+                    }
+                };
+                // the macro-step loop of a CLEAN stage fully unrolled (loop counters and pointer increments become
+                // immediates): 71.0 -> 69.5 ms; factors 2 and 3: no change
+                if constexpr (CLEAN != 0) {
+                    static_for<LEG_KT / 8>(macro_step);
+                } else {
+#pragma unroll 1
+                    for (int ms = 0; ms < LEG_KT / 8; ms++) macro_step(ms);
+                }
+            };
             int st = 0;
             LEG_STAMP(t_pro);
 #if LEG_STAMPS
             int st_mark = 0;
 #endif
-#define LEG_CLEAN 2
-#define LEG_MS_PRAGMA _Pragma("unroll")
-            for (; st < st_hi && !stage_lo(st); st++) {
-#include "leg_stage_body.inc"
-            }
-#undef LEG_CLEAN
-#undef LEG_MS_PRAGMA
+            for (; st < st_hi && !stage_lo(st); st++) stage(std::integral_constant<int, 2>{}, st);
             LEG_STAMP(t_head);
 #if LEG_STAMPS
             n_head += st - st_mark, st_mark = st;
 #endif
-#define LEG_CLEAN 1
-#define LEG_MS_PRAGMA _Pragma("unroll")
-            for (; st < st_hi; st++) {
-#include "leg_stage_body.inc"
-            }
-#undef LEG_CLEAN
-#undef LEG_MS_PRAGMA
+            for (; st < st_hi; st++) stage(std::integral_constant<int, 1>{}, st);
             LEG_STAMP(t_clean);
 #if LEG_STAMPS
             n_clean += st - st_mark, st_mark = st;
 #endif
-#define LEG_CLEAN 0
-#define LEG_MS_PRAGMA _Pragma("unroll 1")
-            for (; st < w.nstage; st++) {
-#include "leg_stage_body.inc"
-            }
-#undef LEG_CLEAN
-#undef LEG_MS_PRAGMA
+            for (; st < w.nstage; st++) stage(std::integral_constant<int, 0>{}, st);
             LEG_STAMP(t_tail);
 #if LEG_STAMPS
             n_tail += st - st_mark, n_items++;
@@ -389,6 +449,10 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
 //     Re Q = -(S_W[ReE] + S_X[ImB]),  Im Q = -(S_W[ImE] - S_X[ReB]),  Re U = -(S_W[ReB] - S_X[ImE]),  Im U = -(S_W[ImB] + S_X[ReE])
 // is a lane-xor-5 exchange in the epilogue; Q_f, U_f leave in the cell positions of E_f, B_f.  W has the parity
 // (-1)^{l+m} of lambda under theta -> pi - theta, X the opposite: north = (W_e + W_o, X_e + X_o), south = (W_e - W_o, X_o - X_e).
+#define LEGP_KT 32     // l rows per stage (the 4 accumulator sets leave room for NT = 4 only)
+#define LEGP_NBUF 3
+template <int NT>
+using leg_pol_geom = leg_geom<NT, LEGP_KT, LEGP_NBUF, 4>;   // a_lm rows + (A, B) pairs + (g1..g4) rows
 template <int NT>
 __global__ void __launch_bounds__(64 * LEG_WAVES)
 legendre_pol_kernel(int lmax, int npair, int nring, int ncols, const double *__restrict__ z,
@@ -397,12 +461,9 @@ legendre_pol_kernel(int lmax, int npair, int nring, int ncols, const double *__r
                     const double2 *__restrict__ seed, const int32_t *__restrict__ lmin_tab,
                     const double *__restrict__ alm, const double *__restrict__ zeros, double *__restrict__ inter,
                     unsigned *__restrict__ queue) {
-    constexpr int KT = 32;                  // l rows per stage (the 4 accumulator sets leave room for NT = 4 only)
-    constexpr int NBUF = 3;
-    constexpr int TCOLS = 16 * NT;
-    constexpr int STRIDE = TCOLS + 8;
-    constexpr int CROWS = KT + 8;
-    constexpr int STAGE = KT * STRIDE + 2 * CROWS + 4 * CROWS;   // a_lm rows + (A, B) pairs + (g1..g4) rows
+    using geom = leg_pol_geom<NT>;
+    constexpr int KT = LEGP_KT, NBUF = LEGP_NBUF;
+    constexpr int TCOLS = geom::TCOLS, STRIDE = geom::STRIDE, CROWS = geom::CROWS, STAGE = geom::STAGE;
     constexpr int RPW = KT / LEG_WAVES;
     constexpr int PIECES = RPW + 3;         // a_lm rows + the (A, B) piece + two pieces of the g table (see issue_coef)
     constexpr int TRINGS = LEG_RINGS;
@@ -506,10 +567,7 @@ legendre_pol_kernel(int lmax, int npair, int nring, int ncols, const double *__r
                 my_ls = lstart[o];
                 sd = seed[o];
             }
-            int ls_min = my_ls;                  // wave-uniform below: the skip tests become scalar compares
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ls_min = min(ls_min, __shfl_xor(ls_min, o));
-            ls_min = __builtin_amdgcn_readfirstlane(ls_min);
+            const int ls_min = wave_min(my_ls);  // wave-uniform: the skip tests become scalar compares
             int inj_l = my_ls;
             const double2 *cf = coef + w.base_m;
             {
@@ -526,37 +584,96 @@ legendre_pol_kernel(int lmax, int npair, int nring, int ncols, const double *__r
                     inj_l = 0x7fffffff;
                 }
             }
-            int ws_maxinj = inj_l == 0x7fffffff ? -1 : inj_l;   // wave-uniform: last row at which a ring of the wave starts
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ws_maxinj = max(ws_maxinj, __shfl_xor(ws_maxinj, o));
-            ws_maxinj = __builtin_amdgcn_readfirstlane(ws_maxinj);
+            const int ws_maxinj = wave_max(inj_l == 0x7fffffff ? -1 : inj_l);   // wave-uniform: last row at which a ring of the wave starts
             asm volatile("" ::"v"(x), "v"(sd.x), "v"(sd.y), "v"(my_ls), "v"(r1), "v"(r2));   // (the ring's loads are consumed here: see legendre_kernel)
             auto stage_clean = [&](int st) {
                 const int ls = w.l_begin + st * KT;
                 return (ls + KT - 1 <= lmax) && (ls_min <= ls) && (ws_maxinj < ls);
             };
+            // One stage = KT rows of l, as in legendre_kernel: CLEAN = 1 for the steady-state stages (no tests, always
+            // refilling, macro-steps unrolled), 0 otherwise (rolled).
+            auto stage = [&](auto clean, const int st) __attribute__((always_inline)) {
+                constexpr bool CLEAN = decltype(clean)::value != 0;
+                if (st + 1 < w.nstage) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                const bool refill = CLEAN ? true : (st + NBUF - 1 < w.nstage);
+                if (refill) issue_stage(w, st + NBUF - 1);
+                const int ls = w.l_begin + st * KT;
+                const double *sb = lds + (st % NBUF) * STAGE;
+                const double2 *sc = reinterpret_cast<const double2 *>(sb + KT * STRIDE) + d;
+                const double *sg = sb + KT * STRIDE + 2 * CROWS + 4 * d;
+                auto macro_step = [&](const int ms) __attribute__((always_inline)) {
+                    const int l0 = ls + 8 * ms;
+                    if (!CLEAN && l0 > lmax) return;
+                    if (!CLEAN && ls_min > l0 + 13) return;
+                    double2 c[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) c[j] = sc[8 * ms + j];
+                    const int lf = l0 + d;
+                    // lambda at lf-1, lf (even l-m slot of this lane), lf+1 (odd slot); then 6 more steps
+                    double lm1 = p1, le = 0.0, lo = 0.0;
+                    double lem1, lom1;
+                    if (!CLEAN && ws_maxinj >= l0 && __any(inj_l >= lf && inj_l < lf + 8)) {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) {
+                            double vv = fma(c[j].x * x, p1, -(c[j].y * p0));
+                            const bool inj = (lf + j == inj_l);
+                            vv = inj ? sd.y : vv;
+                            p0 = inj ? sd.x : p1;
+                            p1 = vv;
+                            if (j == 0) {
+                                le = vv;
+                                lm1 = p0;      // lambda_{lf-1} as the recurrence sees it (the seed if injected here)
+                            }
+                            if (j == 1) lo = vv;
+                        }
+                        lem1 = lm1, lom1 = le;
+                        if (lf + 1 == inj_l) lom1 = sd.x;
+                    } else {
+                        // no ring of the wave starts inside this macro-step: plain recurrence (the compare and the
+                        // three 64-bit selects per step were two thirds of the VALU instructions of the loop)
+#pragma unroll
+                        for (int j = 0; j < 8; j++) {
+                            const double vv = fma(c[j].x * x, p1, -(c[j].y * p0));
+                            p0 = p1;
+                            p1 = vv;
+                            if (j == 0) le = vv;
+                            if (j == 1) lo = vv;
+                        }
+                        lem1 = lm1, lom1 = le;
+                    }
+                    if (!CLEAN && ls_min > l0 + 7) return;
+                    // W, X at the two l of this lane
+                    const double4 ge = *reinterpret_cast<const double4 *>(sg + 4 * (8 * ms));
+                    const double4 go = *reinterpret_cast<const double4 *>(sg + 4 * (8 * ms + 1));
+                    const double We = fma(fma(ge.x, r1, ge.y), le, (ge.z * r2) * lem1);
+                    const double Xe = fma(ge.w * r2, le, -((mval * ge.z) * r1) * lem1);
+                    const double Wo = fma(fma(go.x, r1, go.y), lo, (go.z * r2) * lom1);
+                    const double Xo = fma(go.w * r2, lo, -((mval * go.z) * r1) * lom1);
+                    const double *be = sb + (8 * ms + d) * STRIDE + ri;
+                    const double *bo = be + STRIDE;
+#pragma unroll
+                    for (int t = 0; t < NT; t++) {
+                        const double bev = be[16 * t], bov = bo[16 * t];
+                        awe[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(We, bev, awe[t], 0, 0, 0);
+                        awo[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Wo, bov, awo[t], 0, 0, 0);
+                        axe[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Xe, bev, axe[t], 0, 0, 0);
+                        axo[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(Xo, bov, axo[t], 0, 0, 0);
+                    }
+                };
+                if constexpr (CLEAN) {
+#pragma unroll
+                    for (int ms = 0; ms < KT / 8; ms++) macro_step(ms);
+                } else {
+#pragma unroll 1
+                    for (int ms = 0; ms < KT / 8; ms++) macro_step(ms);
+                }
+            };
             int st = 0;
-#define LEGP_CLEAN 0
-#define LEGP_MS_PRAGMA _Pragma("unroll 1")
-            for (; st < w.nstage && !stage_clean(st); st++) {
-#include "legpol_stage_body.inc"
-            }
-#undef LEGP_CLEAN
-#undef LEGP_MS_PRAGMA
-#define LEGP_CLEAN 1
-#define LEGP_MS_PRAGMA _Pragma("unroll")
-            for (; st + NBUF - 1 < w.nstage && stage_clean(st); st++) {
-#include "legpol_stage_body.inc"
-            }
-#undef LEGP_CLEAN
-#undef LEGP_MS_PRAGMA
-#define LEGP_CLEAN 0
-#define LEGP_MS_PRAGMA _Pragma("unroll 1")
-            for (; st < w.nstage; st++) {
-#include "legpol_stage_body.inc"
-            }
-#undef LEGP_CLEAN
-#undef LEGP_MS_PRAGMA
+            for (; st < w.nstage && !stage_clean(st); st++) stage(std::false_type{}, st);
+            for (; st + NBUF - 1 < w.nstage && stage_clean(st); st++) stage(std::true_type{}, st);
+            for (; st < w.nstage; st++) stage(std::false_type{}, st);
         }
 
         const int cur_rtile = w.rtile, cur_cg = w.cg, cur_m = w.m, cur_nstage = w.nstage;
@@ -597,8 +714,9 @@ legendre_pol_kernel(int lmax, int npair, int nring, int ncols, const double *__r
 }
 template <int NT, int RT>
 static int launch_legendre(corahip_ctx *ctx, const corahip_sht_plan *p, int ncols, const double *alm, double *inter) {
-    constexpr int STRIDE = 16 * NT + 8;
-    const size_t shm = sizeof(double) * LEG_NBUF * (LEG_KT * STRIDE + 2 * (LEG_KT + 8)) + 16;
+    constexpr size_t shm = leg_geom<NT, LEG_KT, LEG_NBUF, 0>::LDS_BYTES;
+    static_assert(LEG_KT != 56 || LEG_NBUF != 2 || shm == (NT == 8 ? 123920 : NT == 4 ? 66576 : NT == 2 ? 37904 : 23568),
+                  "dynamic LDS of the shipped shapes");
     HIP_TRY(hipFuncSetAttribute((const void *)legendre_kernel<NT, RT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)shm));
     const int2 *d_items = nullptr;
@@ -665,8 +783,8 @@ static int ensure_polc(corahip_ctx *ctx, corahip_sht_plan *p) {
 
 template <int NT>
 static int launch_legendre_pol(corahip_ctx *ctx, const corahip_sht_plan *p, int ncols, const double *alm, double *inter) {
-    constexpr int STRIDE = 16 * NT + 8;
-    const size_t shm = sizeof(double) * 3 * (32 * STRIDE + 6 * (32 + 8)) + 16;
+    constexpr size_t shm = leg_pol_geom<NT>::LDS_BYTES;
+    static_assert(shm == (NT == 4 ? 61072 : NT == 2 ? 36496 : 24208), "dynamic LDS of the shipped shapes");
     HIP_TRY(hipFuncSetAttribute((const void *)legendre_pol_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)shm));
     const int ntile = (p->npair + LEG_RINGS - 1) / LEG_RINGS;

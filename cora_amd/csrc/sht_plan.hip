@@ -229,7 +229,7 @@ __global__ void lmin_kernel(int lmax, int npair, int ntile, const int32_t *__res
     lmin_tab[m * ntile + t] = v;
 }
 // FP64 MFMA instructions legendre_kernel<NT, RT> ISSUES for one column group, summed over (m, ring tile, wave): the
-// kernel's own skip logic restated (sht_legendre.hip / leg_stage_body.inc) - an item starts at
+// kernel's own skip logic restated (sht_legendre.hip: legendre_kernel's macro_step) - an item starts at
 // l_begin = m + ((lmin - m) & ~7) with lmin the tile's first contributing l; wave w of the workgroup owns the rings
 // tile * 128 RT + 8 j + w (j < 16 RT) and executes the 2 NT RT MFMAs of the macro-step at l0 = l_begin + 8 k iff
 // l0 <= lmax and ws_min <= l0 + 7 (ws_min = first contributing l of the wave's rings).  Thread = (m, tile, wave);

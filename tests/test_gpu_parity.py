@@ -86,7 +86,9 @@ def test_lambda_from_the_lane_group_entry_states(ctx, nside, lmax, m, pair):
 
 # ------------------------------------------------------------------ K4 + K5
 @pytest.mark.parametrize("nside,lmax,nnu", [(1, 2, 1), (2, 5, 3), (4, 11, 8), (8, 16, 4), (8, 23, 9), (16, 32, 16),
-                                            (32, 95, 5), (64, 128, 24)])
+                                            (32, 95, 5), (64, 128, 24),
+                                            # legendre_kernel<1,2>, <2,2>, <4,2>, <8,1> with head, steady-state and tail stages
+                                            (64, 191, 8), (64, 191, 16), (64, 191, 32), (64, 191, 64)])
 def test_alm2map_vs_oracle(ctx, nside, lmax, nnu):
     import torch
     from oracle import sht
@@ -1625,7 +1627,9 @@ def test_small_and_ragged_sizes_next_rows(ctx):
 
 
 # ------------------------------------------------------------------ n4: polarised (spin-2) synthesis
-@pytest.mark.parametrize("nside,lmax,nfreq", [(4, 8, 1), (8, 20, 3), (16, 47, 4), (32, 64, 8), (64, 150, 2)])
+@pytest.mark.parametrize("nside,lmax,nfreq", [(4, 8, 1), (8, 20, 3), (16, 47, 4), (32, 64, 8), (64, 150, 2),
+                                              # legendre_pol_kernel<2>, <4> with steady-state stages
+                                              (64, 150, 8), (64, 150, 16)])
 def test_alm2map_spin2_vs_oracle(ctx, nside, lmax, nfreq):
     """(E, B) -> (Q, U) on the GPU (legendre_pol_kernel + the ring FFT) against the CPU oracle, through the C ABI."""
     import torch
