@@ -1,5 +1,10 @@
 // fft_ct.h - the compile-time FFT passes shared by the ring transforms (sht_ringfft_ct.hip) and the flat-sky line
-// transforms (flatsky_ct.hip): LDS padding, pass schedules, register butterflies, twiddle application, one in-LDS pass.
+// transforms (flatsky_ct.hip): LDS padding, pass schedules, register butterflies, twiddle application, one in-LDS pass
+// (ct_pass), the per-thread twiddles (pass_twiddles, hermitian_twiddles), the digit map of the fused first / last pass
+// (fused_digits, fused_slot), the real-transform split (real_split), the last-pass pieces of the Bluestein convolution
+// (blu_last_butterfly, blu_out_chirps), the plan-time filter transform (blu_filter_transform) and the host-side launch
+// geometry (ct_launch_geom).  The Hermitian pass 1 and the inner Bluestein stages are NOT here: moved into functions
+// they compile to other fused multiply-adds (other bits) - HISTORY.md, "one set of Hermitian and Bluestein passes".
 #pragma once
 #include "sht_internal.h"
 
@@ -360,4 +365,98 @@ __device__ __forceinline__ static void pass_twiddles(const int tid0, double2 &wA
     const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
     sincospi(2.0 * (double)j0 / (double)N, &wA.y, &wA.x);
     sincospi(2.0 * (double)j1 / (double)Q0, &wB.y, &wB.x);
+}
+
+// wH = e^{i pi j0 / N}, the Hermitian-step twiddle of pass 1 of a half-complex -> real transform (ringfft_direct_ct,
+// linec2r_ct), with the two pass twiddles.  (Not pass_twiddles plus one: wH shares (double)j0 with wA, and the code the compiler makes of
+// ringfft_direct_ct / linec2r_ct depends on that)
+template <int N, int Q0, int R1>
+__device__ __forceinline__ static void hermitian_twiddles(const int tid0, double2 &wH, double2 &wA, double2 &wB) {
+    const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
+    double s, c;
+    sincospi((double)j0 / (double)N, &s, &c);
+    wH = make_double2(c, s);
+    sincospi(2.0 * (double)j0 / (double)N, &s, &c);
+    wA = make_double2(c, s);
+    sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
+    wB = make_double2(c, s);
+}
+
+// ---- the fused last / first pass of the R0 x 16 x R2 schedules (R0 = 16 or 12): butterfly q < 16 R0 of the radix-R2
+// pass on contiguous elements holds the natural indices k0 + R0 k1 + 16 R0 r and sits at LDS slot fused_slot(k0, k1).
+// R0 = 16: lane bits 0-2 = k0 low, 3-5 = k1 low, 6 = k0 high, 7 = k1 high - eight consecutive lanes touch 128 contiguous
+// bytes of HBM (the LDS accesses are 2-way conflicted); R0 = 12: lanes along k0.
+template <int R0>
+__device__ __forceinline__ static void fused_digits(const int q, int &k0, int &k1) {
+    k0 = R0 == 16 ? ((q & 7) | ((q >> 3) & 8)) : q % R0;
+    k1 = R0 == 16 ? (((q >> 3) & 7) | ((q >> 4) & 8)) : q / R0;
+}
+// (the 16 is R1: every caller asserts R1 == 16 for its schedule; PK is what the fpad macro reads)
+template <int PK, int R2>
+__device__ __forceinline__ static int fused_slot(const int k0, const int k1) {
+    constexpr int R1 = 16;
+    return fpk<PK>((k0 * R1 + k1) * R2);
+}
+
+// the split of a real transform of length 2 N done as a complex one of length N:
+// X_m = 1/2 [(Z_m + conj Z_{N-m}) - i w (Z_m - conj Z_{N-m})], za = Z_m, zb = Z_{N-m}, w = e^{-i pi m / N}
+__device__ __forceinline__ static double2 real_split(const double2 za, const double2 zb, const double2 w) {
+    const double2 sum = make_double2(za.x + zb.x, za.y - zb.y);
+    const double2 dif = make_double2(za.x - zb.x, za.y + zb.y);
+    const double2 t = cmul(dif, w);
+    return make_double2(0.5 * (sum.x + t.y), 0.5 * (sum.y - t.x));
+}
+
+// ---- pieces of the last inverse pass (sign +, radix R0, stride Q0 = P / R0) of a Bluestein convolution of length
+// P = R0 x R1 x R2.  The other stages stay written out in the kernels (ringfft_blu_ct, ringana_blu_ct, blu_core of
+// flatsky_ct.hip): as shared functions they compiled to other fused multiply-adds in the ring kernels - other bits.
+// The butterfly at p = buffer + fpad(j0) (the lineblu_*_ct kernels): of its outputs only x[r], r < R0 / 2 (positions
+// j0 + r Q0 in the non-padded half) mean anything; the caller's epilogue takes them.
+template <int PK, int P>
+__device__ __forceinline__ static void blu_last_butterfly(const double2 *p, const double2 wA, double2 (&x)[Sch<P>::R0]) {
+    constexpr int R0 = Sch<P>::R0, Q0 = P / R0;
+#pragma unroll
+    for (int r = 0; r < R0; r++) x[r] = p[fpc(r * Q0)];
+    tw_apply<R0>(x, wA);
+    DftR<R0, 1>::run(x);
+}
+// chirps of those outputs, positions j0 + r Q0 < n (index clamped: lanes past n load a valid slot)
+template <int P>
+__device__ __forceinline__ static void blu_out_chirps(double2 (&ob)[Sch<P>::R0 / 2], const double2 *chirp, const int j0, const int n) {
+    constexpr int R0 = Sch<P>::R0, Q0 = P / R0;
+#pragma unroll
+    for (int r = 0; r < R0 / 2; r++) ob[r] = chirp[min(j0 + r * Q0, n - 1)];
+}
+
+// plan time: the forward transform (sign -) of the P values at sm[fpad(j)] on T threads, result in the storage order of
+// the convolution's forward passes.  Starts and ends with a barrier.
+template <int PK, int P, int BS, int T>
+__device__ __forceinline__ static void blu_filter_transform(double2 *sm, const int tid) {
+    constexpr int R0 = Sch<P>::R0, R1 = Sch<P>::R1, R2 = Sch<P>::R2, Q0 = P / R0;
+    double2 wA, wB;
+    pass_twiddles<P, Q0, R1>(tid, wA, wB);
+    __syncthreads();
+    ct_pass<PK, P, 1, BS, P, R0, -1, false, T>(sm, wA, tid);
+    __syncthreads();
+    ct_pass<PK, P, 1, BS, Q0, R1, -1, false, T>(sm, wB, tid);
+    __syncthreads();
+    if constexpr (R2 > 1) {
+        ct_pass<PK, P, 1, BS, R2, R2, -1, false, T>(sm, wB, tid);   // (stride 1: no twiddles)
+        __syncthreads();
+    }
+}
+
+// ---- host: dynamic-LDS bytes and grid of a persistent compile-time FFT kernel that keeps nch buffers of bs elements
+// (and `extra` more elements) in LDS: as many workgroups per CU as the 160 KB hold, at most wg_cap (0: no other limit),
+// on cu_limit CUs, never more workgroups than items
+struct ct_geom {
+    size_t shm;
+    dim3 grid;
+};
+static inline ct_geom ct_launch_geom(int nch, int bs, int extra, long wg_cap, long items, int cu_limit) {
+    const size_t shm = sizeof(double2) * ((size_t)nch * bs + extra);
+    long per_cu = (long)((160 * 1024) / shm);
+    if (wg_cap > 0) per_cu = std::min(per_cu, wg_cap);
+    per_cu = std::max<long>(1, per_cu);
+    return {shm, dim3((unsigned)std::min<long>(items, (long)cu_limit * per_cu))};
 }

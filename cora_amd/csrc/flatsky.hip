@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "flatsky_ct.h"
 #include "rng_dev.h"
 #include "tile_walk.h"
 

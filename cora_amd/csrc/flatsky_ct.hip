@@ -6,12 +6,21 @@
 //                                generated where it is committed (corahip_randomfield_irfftn)
 //   lineblu_c2c_ct / _c2r_ct / _r2c_ct   every other length n <= 2048: Bluestein at a length out of {2, 3, 5} x 2^k >= 2 n - 1,
 //                                filter made at plan time by flat_blu_filter_kernel (flat_blu_plan)
-// flatsky.hip calls flat_c2r_ct / flat_r2c_ct / flat_c2c_ct / flat_blu_c2c_ct / flat_blu_real_ct first and keeps its
-// generic line kernel (radix-4 LDS stages, power-of-two Bluestein) for what they decline: odd real lengths, lengths
-// below 17 or above 2048, contiguous complex transforms; CORAHIP_FLAT_GENERIC=1 forces it (A/B, tests/test_flatsky.py).
+// flatsky.hip calls flat_c2r_ct / flat_r2c_ct / flat_c2c_ct / flat_blu_c2c_ct / flat_blu_real_ct (flatsky_ct.h) first and
+// keeps its generic line kernel (radix-4 LDS stages, power-of-two Bluestein) for what they decline: odd real lengths,
+// lengths below 17 or above 2048, contiguous complex transforms; CORAHIP_FLAT_GENERIC=1 forces it (flat_ct_off: read once
+// per process; A/B, tests/test_flatsky.py).  Pass 1 of linec2r_ct and the stages of blu_core mirror ringfft_direct_ct /
+// ringfft_blu_ct and stay written out: see the header of sht_ringfft_ct.hip.
 #include "fft_ct.h"
+#include "flatsky_ct.h"
 #include "rng_dev.h"
 #include "tile_walk.h"
+
+// CORAHIP_FLAT_GENERIC set (to anything): every entry point below declines; read once per process
+static bool flat_ct_off() {
+    static const bool off = getenv("CORAHIP_FLAT_GENERIC") != nullptr;
+    return off;
+}
 
 // ------------------------------------------------------------------------------------
 // Flat-sky fields (cora/core/gaussianfield.py:102-120, numpy.fft.irfftn's last axis): the half-complex -> real transform
@@ -36,16 +45,7 @@ linec2r_ct(const double2 *in, double *out, long nlines, double scale) {
     const long nitems = (nlines + NCH - 1) / NCH;
 
     double2 wH, wA, wB;     // e^{i pi j0 / N}, e^{2 pi i j0 / N}, e^{2 pi i j1 / (N / R0)}
-    {   // (pass_twiddles written out: wH shares (double)j0 with wA, and the code the compiler makes of this kernel depends on that)
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
-        double s, c;
-        sincospi((double)j0 / (double)N, &s, &c);
-        wH = make_double2(c, s);
-        sincospi(2.0 * (double)j0 / (double)N, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
+    hermitian_twiddles<N, Q0, R1>(tid0, wH, wA, wB);
     double2 pf[U], pfn;
     auto prefetch = [&](long item, int tid) {
         const long line0 = item * NCH;
@@ -116,9 +116,7 @@ linec2r_ct(const double2 *in, double *out, long nlines, double scale) {
         __syncthreads();
         ct_pass<PK, N, NCH, BS, Q0, R1, 1, false, T>(sm, wB, tid);
         __syncthreads();
-        // ---- last pass (radix R2 on contiguous elements) with the store: butterfly t = 16 k0 + k1 holds the natural
-        //      indices k0 + R0 k1 + 16 R0 r; R0 = 16: eight consecutive lanes store 128 contiguous bytes (lane bits as in
-        //      ringfft_direct_ct), R0 = 12: lanes along k0
+        // ---- last pass (radix R2 on contiguous elements) with the store in the order of fused_digits
         {
             constexpr int NB2 = R0 * R1;                  // butterflies per line
             constexpr int TOT = NCH * NB2;
@@ -127,10 +125,10 @@ linec2r_ct(const double2 *in, double *out, long nlines, double scale) {
             for (int it = 0; it < IT; it++) {
                 const int idx = tid + it * T;
                 if ((TOT % T) != 0 && idx >= TOT) break;
-                const int ch = idx / NB2, q = idx - ch * NB2;
-                const int k0 = R0 == 16 ? ((q & 7) | ((q >> 3) & 8)) : q % R0;
-                const int k1 = R0 == 16 ? (((q >> 3) & 7) | ((q >> 4) & 8)) : q / R0;
-                const double2 *p = sm + ch * BS + fpad((k0 * 16 + k1) * R2);
+                const int ch = idx / NB2;
+                int k0, k1;
+                fused_digits<R0>(idx - ch * NB2, k0, k1);
+                const double2 *p = sm + ch * BS + fused_slot<PK, R2>(k0, k1);
                 double2 x[R2];
 #pragma unroll
                 for (int r = 0; r < R2; r++) x[r] = p[fpc(r)];
@@ -378,14 +376,11 @@ static int launch_linec2c(corahip_ctx *ctx, const double *in, double *out, long 
                           uint64_t seed) {
     constexpr int PK = 1;
     constexpr int BS = fpc(H2 ? N / 2 : N) + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * ((size_t)NCH * BS + (gen ? 513 : 0));
-    const long ntiles = nouter * ((inner + NCH - 1) / NCH);
-    const long per_cu = H2 ? 1 : std::max<long>(1, std::min<long>((160 * 1024) / shm, 2048 / T));
-    dim3 grid((unsigned)std::min<long>(ntiles, (long)ctx->num_cu * per_cu));
+    const ct_geom g = ct_launch_geom(NCH, BS, gen ? 513 : 0, H2 ? 1 : 2048 / T, nouter * ((inner + NCH - 1) / NCH), ctx->num_cu);
     double2 *o2 = reinterpret_cast<double2 *>(out);
     auto launch = [&](auto kernel) {
         HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        kernel<<<grid, T, shm, ctx->stream>>>(in, o2, nouter, inner, scale, seed);
+        kernel<<<g.grid, T, g.shm, ctx->stream>>>(in, o2, nouter, inner, scale, seed);
         LAUNCH_CHECK();
         return 0;
     };
@@ -398,9 +393,8 @@ static int launch_linec2c(corahip_ctx *ctx, const double *in, double *out, long 
 // the generic line kernel takes it
 int flat_c2c_ct(corahip_ctx *ctx, const double *in, double *out, long nouter, int n, long inner, int inverse, double scale, bool gen,
                 uint64_t seed, bool *took) {
-    static const bool off = getenv("CORAHIP_FLAT_GENERIC") != nullptr;
     *took = false;
-    if (off || nouter < 1 || inner < 2) return 0;
+    if (flat_ct_off() || nouter < 1 || inner < 2) return 0;
     int rc;
     if (n == 256 && inner >= 16) rc = launch_linec2c<256, 16, 256>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
     else if (n == 512 && inner >= 16) rc = launch_linec2c<512, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
@@ -450,9 +444,9 @@ liner2c_ct(const double *in, double2 *out, long nlines) {
 #pragma unroll
         for (int it = 0; it < IT0; it++) {
             const int idx = min(tid + it * T, TOT0 - 1);
-            const int ch = idx / NB2, q = idx - ch * NB2;
-            const int k0 = R0 == 16 ? ((q & 7) | ((q >> 3) & 8)) : q % R0;
-            const int k1 = R0 == 16 ? (((q >> 3) & 7) | ((q >> 4) & 8)) : q / R0;
+            const int ch = idx / NB2;
+            int k0, k1;
+            fused_digits<R0>(idx - ch * NB2, k0, k1);
             const double *src = in + min(line0 + ch, nlines - 1) * (2L * N) + 2 * (k0 + R0 * k1);
 #pragma unroll
             for (int r = 0; r < R2; r++) pf[it * R2 + r] = *reinterpret_cast<const double2 *>(src + 2 * NB2 * r);
@@ -469,10 +463,10 @@ liner2c_ct(const double *in, double2 *out, long nlines) {
         for (int it = 0; it < IT0; it++) {
             const int idx = tid + it * T;
             if ((TOT0 % T) != 0 && idx >= TOT0) break;
-            const int ch = idx / NB2, q = idx - ch * NB2;
-            const int k0 = R0 == 16 ? ((q & 7) | ((q >> 3) & 8)) : q % R0;
-            const int k1 = R0 == 16 ? (((q >> 3) & 7) | ((q >> 4) & 8)) : q / R0;
-            double2 *p = sm + ch * BS + fpad((k0 * 16 + k1) * R2);
+            const int ch = idx / NB2;
+            int k0, k1;
+            fused_digits<R0>(idx - ch * NB2, k0, k1);
+            double2 *p = sm + ch * BS + fused_slot<PK, R2>(k0, k1);
             double2 x[R2];
 #pragma unroll
             for (int r = 0; r < R2; r++) x[r] = pf[it * R2 + r];
@@ -489,11 +483,8 @@ liner2c_ct(const double *in, double2 *out, long nlines) {
         auto emit = [&](int c, int k, const double2 w) {       // w = e^{-i pi k / N}
             const int ka = k == N ? 0 : k;                     // Z_N := Z_0
             const int kb = k == 0 ? 0 : N - k;
-            const double2 za = sm[c * BS + fpad(ka)], zb = sm[c * BS + fpad(kb)];
-            const double2 sum = make_double2(za.x + zb.x, za.y - zb.y);
-            const double2 dif = make_double2(za.x - zb.x, za.y + zb.y);
-            const double2 t = cmul(dif, w);
-            if (line0 + c < nlines) out[(line0 + c) * (N + 1L) + k] = make_double2(0.5 * (sum.x + t.y), 0.5 * (sum.y - t.x));
+            const double2 X = real_split(sm[c * BS + fpad(ka)], sm[c * BS + fpad(kb)], w);
+            if (line0 + c < nlines) out[(line0 + c) * (N + 1L) + k] = X;
         };
         // element e = tid + u T is bin k = e mod N of line e / N: the twiddle follows by one rotation per step and a sign
         // per wrap (e^{-i pi (k - N) / N} = -e^{-i pi k / N})
@@ -520,10 +511,7 @@ template <int N, int NCH, int T>
 static int launch_liner2c(corahip_ctx *ctx, const double *in, double *spec, long nlines) {
     constexpr int PK = 1;
     constexpr int BS = fpc(N) + 1 + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * (size_t)NCH * BS;
-    const long nitems = (nlines + NCH - 1) / NCH;
-    const long per_cu = std::max<long>(1, std::min<long>((160 * 1024) / shm, 2048 / T));
-    dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 2048 / T, (nlines + NCH - 1) / NCH, ctx->num_cu);
     HIP_TRY(hipFuncSetAttribute((const void *)liner2c_ct<N, NCH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     liner2c_ct<N, NCH, T><<<grid, T, shm, ctx->stream>>>(in, reinterpret_cast<double2 *>(spec), nlines);
     LAUNCH_CHECK();
@@ -531,9 +519,8 @@ static int launch_liner2c(corahip_ctx *ctx, const double *in, double *spec, long
 }
 // the contiguous real -> half-complex pass of corahip_rfftn (real length 2 h); *took = false: the generic kernel takes it
 int flat_r2c_ct(corahip_ctx *ctx, const double *in, double *spec, long nlines, int h, bool *took) {
-    static const bool off = getenv("CORAHIP_FLAT_GENERIC") != nullptr;
     *took = false;
-    if (off || nlines < 1) return 0;
+    if (flat_ct_off() || nlines < 1) return 0;
     int rc;
     if (h == 256) rc = launch_liner2c<256, 16, 512>(ctx, in, spec, nlines);
     else if (h == 512) rc = launch_liner2c<512, 16, 512>(ctx, in, spec, nlines);
@@ -553,10 +540,7 @@ template <int N, int NCH, int T>
 static int launch_linec2r(corahip_ctx *ctx, const double *spec, double *out, long nlines, double scale) {
     constexpr int PK = 1;
     constexpr int BS = fpc(N) + 1 + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * (size_t)NCH * BS;
-    const long nitems = (nlines + NCH - 1) / NCH;
-    const long per_cu = std::max<long>(1, std::min<long>((160 * 1024) / shm, 2048 / T));
-    dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 2048 / T, (nlines + NCH - 1) / NCH, ctx->num_cu);
     HIP_TRY(hipFuncSetAttribute((const void *)linec2r_ct<N, NCH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     linec2r_ct<N, NCH, T><<<grid, T, shm, ctx->stream>>>(reinterpret_cast<const double2 *>(spec), out, nlines, scale);
     LAUNCH_CHECK();
@@ -565,9 +549,8 @@ static int launch_linec2r(corahip_ctx *ctx, const double *spec, double *out, lon
 // the contiguous half-complex -> real pass of corahip_irfftn for the complex lengths that have a compile-time schedule;
 // *took = false: the generic line kernel takes it
 int flat_c2r_ct(corahip_ctx *ctx, const double *spec, double *out, long nlines, int h, double scale, bool *took) {
-    static const bool off = getenv("CORAHIP_FLAT_GENERIC") != nullptr;
     *took = false;
-    if (off || nlines < 1) return 0;
+    if (flat_ct_off() || nlines < 1) return 0;
     int rc;
     if (h == 256) rc = launch_linec2r<256, 16, 256>(ctx, spec, out, nlines, scale);
     else if (h == 512) rc = launch_linec2r<512, 16, 512>(ctx, spec, out, nlines, scale);
@@ -597,8 +580,6 @@ template <int P, int T>
 __global__ void __launch_bounds__(T)
 flat_blu_filter_kernel(int n, const double2 *__restrict__ chirp, double2 *__restrict__ filt) {
     constexpr int PK = 1;
-    constexpr int R0 = Sch<P>::R0, R1 = Sch<P>::R1, R2 = Sch<P>::R2;
-    constexpr int Q0 = P / R0;
     constexpr int BS = fpc(P) + 1;
     extern __shared__ __attribute__((aligned(16))) double2 sm[];
     const int tid = threadIdx.x;
@@ -608,24 +589,7 @@ flat_blu_filter_kernel(int n, const double2 *__restrict__ chirp, double2 *__rest
         else if (P - m < n) v = cconj(chirp[P - m]);
         sm[fpad(m)] = v;
     }
-    double2 wA, wB;
-    {
-        const int j0 = tid & (Q0 - 1), j1 = tid & (Q0 / R1 - 1);
-        double s, c;
-        sincospi(2.0 * (double)j0 / (double)P, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
-    __syncthreads();
-    ct_pass<PK, P, 1, BS, P, R0, -1, false, T>(sm, wA, tid);
-    __syncthreads();
-    ct_pass<PK, P, 1, BS, Q0, R1, -1, false, T>(sm, wB, tid);
-    __syncthreads();
-    if constexpr (R2 > 1) {
-        ct_pass<PK, P, 1, BS, R2, R2, -1, false, T>(sm, make_double2(1.0, 0.0), tid);
-        __syncthreads();
-    }
+    blu_filter_transform<PK, P, BS, T>(sm, tid);
     const double invP = 1.0 / (double)P;
     for (int m = tid; m < P; m += T) {
         const double2 v = sm[fpad(m)];
@@ -636,7 +600,7 @@ flat_blu_filter_kernel(int n, const double2 *__restrict__ chirp, double2 *__rest
 // the inner stages of the convolution on NCH lines of P points in LDS (line c at sm + c BS, BS = fpc(P) + 1): forward pass
 // 1 (sign -; the inputs r >= R0 / 2 are the zero padding and are not read), forward pass 2, last forward pass + filter +
 // first inverse pass in registers (fl: the filter values of this thread's butterfly t = tid mod (P / R2)), inverse pass
-// 2.  Starts behind the caller's barrier, ends with one; the caller runs the last inverse pass (radix R0, stride P / R0).
+// 2.  Starts behind the caller's barrier, ends with one; the caller runs the last inverse pass (blu_last_butterfly).
 // `hook` runs in front of inverse pass 2: loads that are needed behind the last pass and have no registers to live in
 // across all of the passes (the output chirps) are requested there.
 struct blu_no_hook {
@@ -708,7 +672,7 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
     constexpr int U = (NCH * HALF + T - 1) / T;  // input elements per thread
     constexpr int NB = P / R2;                   // middle-stage butterflies per line
     static_assert(NB <= T, "one middle-stage butterfly per thread and line group");
-    constexpr int TOTL = NCH * Q0, ITL = 1;      // first / last pass butterflies: one per thread
+    constexpr int TOTL = NCH * Q0;               // first / last pass butterflies: one per thread
     static_assert(TOTL <= T && (T / NCH) % Q0 == 0, "one first / last pass butterfly per thread");
     extern __shared__ __attribute__((aligned(16))) double2 sm[];
     double2 *lg_l = sm + NCH * BS, *sc_l = lg_l + 257;
@@ -732,11 +696,8 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
     double2 fl[R2];
 #pragma unroll
     for (int r = 0; r < R2; r++) fl[r] = filt[(size_t)(tid0 % NB) * R2 + r];
-    double2 ob[ITL][R0 / 2];
-#pragma unroll
-    for (int it = 0; it < ITL; it++)
-#pragma unroll
-        for (int r = 0; r < R0 / 2; r++) ob[it][r] = chirp[min((tid0 + it * T) / NCH % Q0 + r * Q0, n - 1)];
+    double2 ob[R0 / 2];
+    blu_out_chirps<P>(ob, chirp, tid0 / NCH % Q0, n);
     tiles.pair_xcds(ntiles);
     double2 R[U];
     auto prefetch = [&](const tile_t &tl, int tid) {
@@ -782,28 +743,19 @@ lineblu_c2c_ct(const double *in, double2 *out, long nouter, long inner, int n, d
         blu_core<P, NCH, T>(sm, tid, wA, wB, fl);
         // ---- last inverse pass (sign +) with the store: the outputs k = j0 + r Q0 < n, times c_k; the lines of a row in
         //      consecutive lanes (16 NCH contiguous bytes)
-        {
+        if (TOTL == T || tid < TOTL) {
+            const int ch = tid & (NCH - 1), j0 = (tid / NCH) & (Q0 - 1);
+            double2 x[R0];
+            blu_last_butterfly<PK, P>(sm + ch * BS + fpad(j0), wL, x);
+            if (ch < cur.teff) {
+                double2 *o = out + cur.base + ch;
 #pragma unroll
-            for (int it = 0; it < ITL; it++) {
-                const int idx = tid + it * T;
-                if ((TOTL % T) != 0 && idx >= TOTL) break;
-                const int ch = idx & (NCH - 1), j0 = (idx / NCH) & (Q0 - 1);
-                const double2 *p = sm + ch * BS + fpad(j0);
-                double2 x[R0];
-#pragma unroll
-                for (int r = 0; r < R0; r++) x[r] = p[fpc(r * Q0)];
-                tw_apply<R0>(x, wL);
-                DftR<R0, 1>::run(x);
-                if (ch < cur.teff) {
-                    double2 *o = out + cur.base + ch;
-#pragma unroll
-                    for (int r = 0; r < R0 / 2; r++) {
-                        const int k = j0 + r * Q0;
-                        if (k < n) {
-                            double2 v = cmul(x[r], ob[it][r]);
-                            if (inverse) v.y = -v.y;
-                            o[(long)k * inner] = make_double2(v.x * scale, v.y * scale);
-                        }
+                for (int r = 0; r < R0 / 2; r++) {
+                    const int k = j0 + r * Q0;
+                    if (k < n) {
+                        double2 v = cmul(x[r], ob[r]);
+                        if (inverse) v.y = -v.y;
+                        o[(long)k * inner] = make_double2(v.x * scale, v.y * scale);
                     }
                 }
             }
@@ -916,18 +868,11 @@ lineblu_c2r_ct(const double2 *in, double2 *out, long nlines, int h, double scale
             for (int c = 0; c < NCH; c++) sm[c * BS + fpad(j)] = make_double2(0.0, 0.0);
         __syncthreads();
         double2 ob[R0 / 2];     // chirps of the outputs this thread forms
-        blu_core<P, NCH, T>(sm, tid, wA, wB, fl, [&]() {
-#pragma unroll
-            for (int r = 0; r < R0 / 2; r++) ob[r] = chirp[min((tid & (Q0 - 1)) + r * Q0, h - 1)];
-        });
+        blu_core<P, NCH, T>(sm, tid, wA, wB, fl, [&]() { blu_out_chirps<P>(ob, chirp, tid & (Q0 - 1), h); });
         if (TOTL == T || tid < TOTL) {
             const int ch = tid / Q0, j0 = tid & (Q0 - 1);
-            const double2 *p = sm + ch * BS + fpad(j0);
             double2 x[R0];
-#pragma unroll
-            for (int r = 0; r < R0; r++) x[r] = p[fpc(r * Q0)];
-            tw_apply<R0>(x, wA);
-            DftR<R0, 1>::run(x);
+            blu_last_butterfly<PK, P>(sm + ch * BS + fpad(j0), wA, x);
             if (line0 + ch < nlines) {
                 double2 *o = out + (line0 + ch) * (long)h;
 #pragma unroll
@@ -1015,19 +960,13 @@ lineblu_r2c_ct(const double2 *in, double2 *out, long nlines, int h, const double
         prefetch(min(vitem + (long)gridDim.x, nitems - 1), tid);
         __syncthreads();
         double2 ob[R0 / 2];
-        blu_core<P, NCH, T>(sm, tid, wA, wB, fl, [&]() {
-#pragma unroll
-            for (int r = 0; r < R0 / 2; r++) ob[r] = chirp[min((tid & (Q0 - 1)) + r * Q0, h - 1)];
-        });
+        blu_core<P, NCH, T>(sm, tid, wA, wB, fl, [&]() { blu_out_chirps<P>(ob, chirp, tid & (Q0 - 1), h); });
         // ---- last inverse pass: Z_k = c_k conv_k, k < h, back to position k
         if (TOTL == T || tid < TOTL) {
             const int ch = tid / Q0, j0 = tid & (Q0 - 1);
             double2 *p = sm + ch * BS + fpad(j0);
             double2 x[R0];
-#pragma unroll
-            for (int r = 0; r < R0; r++) x[r] = p[fpc(r * Q0)];
-            tw_apply<R0>(x, wA);
-            DftR<R0, 1>::run(x);
+            blu_last_butterfly<PK, P>(p, wA, x);
 #pragma unroll
             for (int r = 0; r < R0 / 2; r++) p[fpc(r * Q0)] = cmul(x[r], ob[r]);
         }
@@ -1094,10 +1033,7 @@ static int launch_lineblu_c2c(corahip_ctx *ctx, const double *in, double *out, l
                               double scale, bool gen, uint64_t seed, const double2 *chirp, const double2 *filt) {
     constexpr int PK = 1;
     constexpr int BS = fpc(P) + 1;
-    const size_t shm = sizeof(double2) * ((size_t)NCH * BS + (gen ? 513 : 0));
-    const long ntiles = nouter * ((inner + NCH - 1) / NCH);
-    const long per_cu = std::max<long>(1, std::min<long>((160 * 1024) / shm, 2048 / T));
-    dim3 grid((unsigned)std::min<long>(ntiles, (long)ctx->num_cu * per_cu));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, gen ? 513 : 0, 2048 / T, nouter * ((inner + NCH - 1) / NCH), ctx->num_cu);
     double2 *o2 = reinterpret_cast<double2 *>(out);
     if (gen) {
         HIP_TRY(hipFuncSetAttribute((const void *)lineblu_c2c_ct<P, NCH, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1112,9 +1048,8 @@ static int launch_lineblu_c2c(corahip_ctx *ctx, const double *in, double *out, l
 // a strided complex pass of a Bluestein length; Pct / filt_ct from flat_blu_plan.  *took = false: the generic kernel takes it
 int flat_blu_c2c_ct(corahip_ctx *ctx, const double *in, double *out, long nouter, int n, long inner, int inverse, double scale, bool gen,
                     uint64_t seed, int Pct, const double2 *chirp, const double2 *filt_ct, bool *took) {
-    static const bool off = getenv("CORAHIP_FLAT_GENERIC") != nullptr;
     *took = false;
-    if (off || !Pct || !filt_ct || nouter < 1 || inner < 2) return 0;
+    if (flat_ct_off() || !Pct || !filt_ct || nouter < 1 || inner < 2) return 0;
     int rc;
 #define BLU_ARGS ctx, in, out, nouter, inner, n, inverse, scale, gen, seed, chirp, filt_ct
     switch (Pct) {
@@ -1145,10 +1080,7 @@ static int launch_lineblu_real(corahip_ctx *ctx, bool c2r, const double *in, dou
                                const double2 *chirp, const double2 *filt, const double2 *rtw) {
     constexpr int PK = 1;
     constexpr int BS = fpc(P) + 1;
-    const size_t shm = sizeof(double2) * (size_t)NCH * BS;
-    const long nitems = (nlines + NCH - 1) / NCH;
-    const long per_cu = std::max<long>(1, std::min<long>((160 * 1024) / shm, 2048 / T));
-    dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 2048 / T, (nlines + NCH - 1) / NCH, ctx->num_cu);
     const double2 *i2 = reinterpret_cast<const double2 *>(in);
     double2 *o2 = reinterpret_cast<double2 *>(out);
     if (c2r) {
@@ -1165,9 +1097,8 @@ static int launch_lineblu_real(corahip_ctx *ctx, bool c2r, const double *in, dou
 // -> half-complex); Pct / filt_ct / chirp / rtw of the plan of length h.  *took = false: the generic kernel takes it
 int flat_blu_real_ct(corahip_ctx *ctx, bool c2r, const double *in, double *out, long nlines, int h, double scale, int Pct,
                      const double2 *chirp, const double2 *filt_ct, const double2 *rtw, bool *took) {
-    static const bool off = getenv("CORAHIP_FLAT_GENERIC") != nullptr;
     *took = false;
-    if (off || !Pct || !filt_ct || nlines < 1) return 0;
+    if (flat_ct_off() || !Pct || !filt_ct || nlines < 1) return 0;
     int rc;
 #define BLU_ARGS ctx, c2r, in, out, nlines, h, scale, chirp, filt_ct, rtw
     switch (Pct) {

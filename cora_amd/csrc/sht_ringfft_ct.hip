@@ -22,6 +22,12 @@
 //     the buffer is never zero-filled); last forward pass + filter + first inverse pass stay in registers.
 // LDS stores are the expensive operation of these kernels (ds_write_b128: 13 cycles per wave-instruction against
 // 4 for ds_read_b128, MI355X_MICROARCH.md section LDS), hence the count of write passes above.
+// Shared with the flat-sky line kernels through fft_ct.h: schedules, butterflies, ct_pass, the twiddle set-up, the digit
+// map of the fused pixel pass, the real-transform split, the output-chirp load, the filter transform of
+// blu3_filter_kernel and the launch geometry.  Pass 1 with the Hermitian step (also in linec2r_ct) and forward pass 1,
+// middle stage and last butterfly of the convolution (twice here, once in flatsky_ct.hip's blu_core) are written out
+// in each kernel on purpose: as shared functions the compiler contracts their multiply-adds differently, and the maps
+// change in the last bit.  A change to one copy has to be repeated in the others.
 #include "sht_internal.h"
 
 #define CT_T 512
@@ -60,6 +66,20 @@ __device__ __forceinline__ static cell_ct<NCH> load_cell_ct(const double *cell, 
         c.im[0] = cell[m * 8u + 4u];
     }
     return c;
+}
+// its mirror (K5^T): the NCH values of one 64-byte cell, as whole 32- / 16- / 8-byte stores
+template <int NCH>
+__device__ __forceinline__ static void store_cell(double *cell, const double (&re)[NCH], const double (&im)[NCH]) {
+    if (NCH == 4) {
+        *reinterpret_cast<double4 *>(cell) = make_double4(re[0], re[1 % NCH], re[2 % NCH], re[3 % NCH]);
+        *reinterpret_cast<double4 *>(cell + 4) = make_double4(im[0], im[1 % NCH], im[2 % NCH], im[3 % NCH]);
+    } else if (NCH == 2) {
+        *reinterpret_cast<double2 *>(cell) = make_double2(re[0], re[1 % NCH]);
+        *reinterpret_cast<double2 *>(cell + 4) = make_double2(im[0], im[1 % NCH]);
+    } else {
+        cell[0] = re[0];
+        cell[4] = im[0];
+    }
 }
 
 // phase e^{i m phi0} and fold of one cell onto the bins 0..h of the Hermitian spectrum (see ringfft_kernel)
@@ -222,16 +242,7 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
 
     // per-thread twiddles, fixed for the whole kernel
     double2 wH, wA, wB;     // e^{i pi j0 / N}, e^{2 pi i j0 / N}, e^{2 pi i j1 / (N / R0)}
-    {   // (pass_twiddles written out: wH shares (double)j0 with wA, and the code the compiler makes of this kernel depends on that)
-        const int j0 = tid0 & (Q0 - 1), j1 = tid0 & (Q0 / R1 - 1);
-        double s, c;
-        sincospi((double)j0 / (double)N, &s, &c);
-        wH = make_double2(c, s);
-        sincospi(2.0 * (double)j0 / (double)N, &s, &c);
-        wA = make_double2(c, s);
-        sincospi(2.0 * (double)j1 / (double)Q0, &s, &c);
-        wB = make_double2(c, s);
-    }
+    hermitian_twiddles<N, Q0, R1>(tid0, wH, wA, wB);
     auto cell_ptr = [&](int item) {
         const int ring = ring_list[item / ngrp];
         const int ch0 = (item % ngrp) * NCH;
@@ -336,8 +347,7 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
         }
         __syncthreads();
         // ---- last pass (radix R2 on contiguous elements, no twiddles) with the pixel store: butterfly t = 16 k0 + k1
-        //      holds the natural indices k0 + 16 k1 + 256 r.  Lane bits: 0-2 = k0 low, 3-5 = k1 low, 6 = k0 high,
-        //      7 = k1 high: eight consecutive lanes store 128 contiguous bytes; the LDS reads are 2-way conflicted.
+        //      holds the natural indices k0 + 16 k1 + 256 r (fused_digits: eight consecutive lanes store 128 contiguous bytes)
         {
             constexpr int TOT = NCH * 256;
             constexpr int IT = (TOT + T - 1) / T;
@@ -348,9 +358,9 @@ ringfft_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
                 const int idx = tid + it * T;
                 if ((TOT % T) != 0 && idx >= TOT) break;
                 const int ch = idx >> 8;
-                const int k0 = (idx & 7) | ((idx >> 3) & 8);
-                const int k1 = ((idx >> 3) & 7) | ((idx >> 4) & 8);
-                const double2 *p = sm + ch * BS + fpad((k0 * 16 + k1) * R2);
+                int k0, k1;
+                fused_digits<R0>(idx & 255, k0, k1);
+                const double2 *p = sm + ch * BS + fused_slot<PK, R2>(k0, k1);
                 double2 x[R2];
 #pragma unroll
                 for (int r = 0; r < R2; r++) x[r] = p[fpc(r)];
@@ -592,12 +602,8 @@ ringfft_blu_ct(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
         // chirp of the outputs this thread forms in the last pass: j0 + r Q0 < h, r < R0 / 2 (requested two passes ahead;
         // the radix-32 / 24 kernels have no registers to hold 16 of them across the passes and read them at the store)
         constexpr bool OB_EARLY = R0 <= 16;
-        double2 ob[OB_EARLY ? R0 / 2 : 1];
-        if constexpr (OB_EARLY) {
-            const int j0 = tid & (Q0 - 1);
-#pragma unroll
-            for (int r = 0; r < R0 / 2; r++) ob[r] = bch[min(j0 + r * Q0, h - 1)];
-        }
+        double2 ob[R0 / 2];
+        if constexpr (OB_EARLY) blu_out_chirps<P>(ob, bch, tid & (Q0 - 1), h);
         __syncthreads();
         CTSTAMP(6);
         ct_pass<PK, P, NCH, BS, Q0, R1, 1, true, T>(sm, wB, tid);
@@ -624,7 +630,7 @@ ringfft_blu_ct(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
                     for (int r = 0; r < R0 / 2; r++) {
                         const int jj = j0 + r * Q0;
                         if (jj < h) {
-                            double2 zv = cmul(x[r], OB_EARLY ? ob[OB_EARLY ? r : 0] : bch[jj]);
+                            double2 zv = cmul(x[r], OB_EARLY ? ob[r] : bch[jj]);
                             zv.x *= invP;
                             zv.y *= invP;
                             *reinterpret_cast<double2 *>(out + 2 * jj) = zv;
@@ -697,8 +703,8 @@ ringana_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
         for (int it = 0; it < IT0; it++) {
             const int idx = tid + it * T;
             const int ch = idx >> 8;
-            const int k0 = (idx & 7) | ((idx >> 3) & 8);
-            const int k1 = ((idx >> 3) & 7) | ((idx >> 4) & 8);
+            int k0, k1;
+            fused_digits<R0>(idx & 255, k0, k1);
             // (a padding channel reads the last valid one: the loads stay unconditional, its cells are zeroed at the store)
             const int chv = min(ch0 + ch, nvalid - 1);
             const double *src = maps + (size_t)chv * npix + start + 2 * (k0 + 16 * k1);
@@ -723,9 +729,9 @@ ringana_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
         for (int it = 0; it < IT0; it++) {
             const int idx = tid + it * T;
             const int ch = idx >> 8;
-            const int k0 = (idx & 7) | ((idx >> 3) & 8);
-            const int k1 = ((idx >> 3) & 7) | ((idx >> 4) & 8);
-            double2 *p = sm + ch * BS + fpad((k0 * 16 + k1) * R2);
+            int k0, k1;
+            fused_digits<R0>(idx & 255, k0, k1);
+            double2 *p = sm + ch * BS + fused_slot<PK, R2>(k0, k1);
             DftR<R2, -1>::run(pf[it]);
 #pragma unroll
             for (int r = 0; r < R2; r++) p[fpc(r)] = pf[it][r];
@@ -749,27 +755,13 @@ ringana_direct_ct(const int32_t *__restrict__ ring_list, int nlist, int lmax, in
                 double re[NCH], im[NCH];
 #pragma unroll
                 for (int c = 0; c < NCH; c++) {
-                    const double2 za = sm[c * BS + fpad(ka)], zb = sm[c * BS + fpad(kb)];
-                    const double2 sum = make_double2(za.x + zb.x, za.y - zb.y);
-                    const double2 dif = make_double2(za.x - zb.x, za.y + zb.y);
-                    const double2 t = cmul(dif, wm);
-                    const double2 X = make_double2(0.5 * (sum.x + t.y), 0.5 * (sum.y - t.x));
+                    const double2 X = real_split(sm[c * BS + fpad(ka)], sm[c * BS + fpad(kb)], wm);
                     const double2 g = cmul(X, make_double2(phm.x * wr, phm.y * wr));
                     const bool live = ch0 + c < nvalid;
                     re[c] = live ? g.x : 0.0;
                     im[c] = live ? g.y : 0.0;
                 }
-                double *cell = cell0 + (size_t)m * 8;
-                if (NCH == 4) {
-                    *reinterpret_cast<double4 *>(cell) = make_double4(re[0], re[1 % NCH], re[2 % NCH], re[3 % NCH]);
-                    *reinterpret_cast<double4 *>(cell + 4) = make_double4(im[0], im[1 % NCH], im[2 % NCH], im[3 % NCH]);
-                } else if (NCH == 2) {
-                    *reinterpret_cast<double2 *>(cell) = make_double2(re[0], re[1 % NCH]);
-                    *reinterpret_cast<double2 *>(cell + 4) = make_double2(im[0], im[1 % NCH]);
-                } else {
-                    cell[0] = re[0];
-                    cell[4] = im[0];
-                }
+                store_cell<NCH>(cell0 + (size_t)m * 8, re, im);
             };
 #pragma unroll
             for (int u = 0; u < MO; u++) {
@@ -792,10 +784,8 @@ static int launch_direct(corahip_ctx *ctx, hipStream_t stream, const corahip_sht
                          const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps, int cu_limit) {
     constexpr int PK = K5_PK_DIRECT;
     constexpr int BS = fpc(N) + 1 + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu + NCH - 1) / NCH);
-    const int per_cu = std::max<int>(1, (int)((160 * 1024) / shm));
-    dim3 grid((unsigned)std::min<long>(nitems, (long)cu_limit * per_cu));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 0, nitems, cu_limit);
     if (!ctx->k5_tickets) {
         corahip_set_error("ring FFT: the ticket counters of the context are missing");
         return CORAHIP_ESTATE;
@@ -819,10 +809,8 @@ static int launch_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_pl
     }
     constexpr int PK = K5_PK_BLU;
     constexpr int BS = fpc(P) + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu + NCH - 1) / NCH);
-    const int per_cu = std::max<int>(1, (int)((160 * 1024) / shm));
-    dim3 grid((unsigned)std::min<long>(nitems, (long)cu_limit * per_cu));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 0, nitems, cu_limit);
     HIP_TRY(hipFuncSetAttribute((const void *)ringfft_blu_ct<P, NCH, MC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024));
     ringfft_blu_ct<P, NCH, MC, T><<<grid, T, shm, stream>>>(c.d_list, c.count, p->nside, p->lmax, G, nnu, p->npix, p->d_nphi,
@@ -1011,11 +999,7 @@ ringana_blu_ct(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
         }
         // chirp of the outputs this thread forms in the last pass: j0 + r Q0 < h, r < R0 / 2
         double2 ob[R0 / 2];
-        {
-            const int j0 = tid & (Q0 - 1);
-#pragma unroll
-            for (int r = 0; r < R0 / 2; r++) ob[r] = bch[min(j0 + r * Q0, h - 1)];
-        }
+        blu_out_chirps<P>(ob, bch, tid & (Q0 - 1), h);
         __syncthreads();
         ct_pass<PK, P, NCH, BS, Q0, R1, 1, true, T>(sm, wB, tid);
         __syncthreads();
@@ -1062,28 +1046,14 @@ ringana_blu_ct(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
                 double re[NCH], im[NCH];
 #pragma unroll
                 for (int c = 0; c < NCH; c++) {
-                    const double2 za = sm[c * BS + fpad(ka)], zb = sm[c * BS + fpad(kb)];
-                    const double2 sum = make_double2(za.x + zb.x, za.y - zb.y);
-                    const double2 dif = make_double2(za.x - zb.x, za.y + zb.y);
-                    const double2 t = cmul(dif, wm);
-                    double2 X = make_double2(0.5 * (sum.x + t.y), 0.5 * (sum.y - t.x));
+                    double2 X = real_split(sm[c * BS + fpad(ka)], sm[c * BS + fpad(kb)], wm);
                     if (cj) X.y = -X.y;
                     const double2 g = cmul(X, phm);
                     const bool live = ch0 + c < nvalid;
                     re[c] = live ? g.x : 0.0;
                     im[c] = live ? g.y : 0.0;
                 }
-                double *cell = cell0 + (size_t)m * 8;
-                if (NCH == 4) {
-                    *reinterpret_cast<double4 *>(cell) = make_double4(re[0], re[1 % NCH], re[2 % NCH], re[3 % NCH]);
-                    *reinterpret_cast<double4 *>(cell + 4) = make_double4(im[0], im[1 % NCH], im[2 % NCH], im[3 % NCH]);
-                } else if (NCH == 2) {
-                    *reinterpret_cast<double2 *>(cell) = make_double2(re[0], re[1 % NCH]);
-                    *reinterpret_cast<double2 *>(cell + 4) = make_double2(im[0], im[1 % NCH]);
-                } else {
-                    cell[0] = re[0];
-                    cell[4] = im[0];
-                }
+                store_cell<NCH>(cell0 + (size_t)m * 8, re, im);
             }
         }
     }
@@ -1095,9 +1065,8 @@ static int launch_ana_direct(corahip_ctx *ctx, hipStream_t stream, const corahip
                              const double *maps, int nvalid, int nnu_pad, const double *ring_w, int G, double *inter) {
     constexpr int PK = K5_PK_DIRECT;
     constexpr int BS = fpc(N) + 1 + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu_pad + NCH - 1) / NCH);
-    dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * std::max<int>(1, (int)((160 * 1024) / shm))));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 0, nitems, ctx->num_cu);
     HIP_TRY(hipFuncSetAttribute((const void *)ringana_direct_ct<N, NCH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     ringana_direct_ct<N, NCH, T><<<grid, T, shm, stream>>>(c.d_list, c.count, p->lmax, G, nnu_pad, nvalid, p->npix, p->d_start, p->d_phi0,
                                                            maps, inter, p->d_mcut, ring_w, 4 * p->nside - 1);
@@ -1109,9 +1078,8 @@ static int launch_ana_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sh
                           const double *maps, int nvalid, int nnu_pad, const double *ring_w, int G, double *inter, bool blu3) {
     constexpr int PK = K5_PK_BLU;
     constexpr int BS = fpc(P) + K5_CH_SKEW;
-    const size_t shm = sizeof(double2) * (size_t)NCH * BS;
     const long nitems = (long)c.count * ((nnu_pad + NCH - 1) / NCH);
-    dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * std::max<int>(1, (int)((160 * 1024) / shm))));
+    const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 0, nitems, ctx->num_cu);
     HIP_TRY(hipFuncSetAttribute((const void *)ringana_blu_ct<P, NCH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     ringana_blu_ct<P, NCH, T><<<grid, T, shm, stream>>>(c.d_list, c.count, p->nside, p->lmax, G, nnu_pad, nvalid, p->npix, p->d_nphi,
                                                         p->d_start, maps, inter, p->d_blu_boff, blu3 ? p->d_blu3_foff : p->d_blu_foff,
@@ -1192,8 +1160,7 @@ __global__ void __launch_bounds__(CT_T)
 blu3_filter_kernel(int nside, const int32_t *__restrict__ p3_of, const int64_t *__restrict__ boff, const int64_t *__restrict__ foff3,
                    const double2 *__restrict__ chirp, double2 *__restrict__ filt3) {
     constexpr int PK = K5_PK_BLU;
-    constexpr int R0 = Sch<P>::R0, R1 = Sch<P>::R1, R2 = Sch<P>::R2;
-    constexpr int Q0 = P / R0, BS = fpc(P) + K5_CH_SKEW;
+    constexpr int BS = fpc(P) + K5_CH_SKEW;
     extern __shared__ __attribute__((aligned(16))) double2 sm[];
     const int i = blockIdx.x + 1;
     if (p3_of[i - 1] != P) return;
@@ -1206,21 +1173,7 @@ blu3_filter_kernel(int nside, const int32_t *__restrict__ p3_of, const int64_t *
         else if (P - j < h) v = cconj(b[P - j]);
         sm[fpad(j)] = v;
     }
-    __syncthreads();
-    double2 wA, wB;
-    {
-        double sv, cv;
-        sincospi(2.0 * (double)(tid & (Q0 - 1)) / (double)P, &sv, &cv);
-        wA = make_double2(cv, sv);
-        sincospi(2.0 * (double)(tid & (Q0 / R1 - 1)) / (double)Q0, &sv, &cv);
-        wB = make_double2(cv, sv);
-    }
-    ct_pass<PK, P, 1, BS, P, R0, -1, false, CT_T>(sm, wA, tid);
-    __syncthreads();
-    ct_pass<PK, P, 1, BS, Q0, R1, -1, false, CT_T>(sm, wB, tid);
-    __syncthreads();
-    ct_pass<PK, P, 1, BS, Q0 / R1, R2, -1, false, CT_T>(sm, wB, tid);   // (stride 1: no twiddles)
-    __syncthreads();
+    blu_filter_transform<PK, P, BS, CT_T>(sm, tid);
     double2 *f = filt3 + foff3[i - 1];
     for (int j = tid; j < P; j += CT_T) f[j] = sm[fpad(j)];
 }

@@ -86,7 +86,9 @@ def test_host_kweight_and_geometry_match_reference(fsg):
 
 # ------------------------------------------------------------------ GPU: line-FFT engine
 LENGTHS = [1, 2, 3, 4, 5, 7, 8, 12, 16, 31, 32, 64, 100, 128, 256, 257, 384, 512, 768, 1000, 1024, 1265, 1700, 2000, 2048, 3000, 4095,
-           4096]
+           4096,
+           # Bluestein on the compile-time passes at the convolution lengths 384, 512, 768, 1024, 1536 (lineblu_c2c_ct)
+           180, 250, 350, 500, 700]
 
 
 @pytest.mark.gpu
@@ -95,7 +97,10 @@ def test_fft_c2c_every_axis_position_vs_numpy(ctx, n):
     import torch
 
     rng = np.random.default_rng(n)
-    for shape, axis in (((3, n), 1), ((n, 5), 0), ((2, n, 37), 1)):
+    cases = [((3, n), 1), ((n, 5), 0), ((2, n, 37), 1)]
+    if n == 1024:
+        cases.append(((2, n, 12), 1))       # strided length 1024 with 8 <= inner < 16: linec2c_ct<1024, 8, 512>
+    for shape, axis in cases:
         x = rng.standard_normal(shape) + 1j * rng.standard_normal(shape)
         for inverse, ref in ((False, np.fft.fft), (True, np.fft.ifft)):
             d = torch.from_numpy(x.copy()).to(ctx.device)
@@ -117,7 +122,9 @@ def test_fft_c2c_every_axis_position_vs_numpy(ctx, n):
                                    # (P = 320, 640, 1024, 2048, 768, 512), and one line more than the lines per item
                                    (7, 316), (5, 9, 628), (4, 1000), (6, 1800), (5, 700), (17, 500), (2500,),
                                    # convolution lengths 2560 .. 4096 (two lines per item)
-                                   (3, 2600), (5, 4000), (1265, 12), (1500, 3, 6), (3, 3300)])
+                                   (3, 2600), (5, 4000), (1265, 12), (1500, 3, 6), (3, 3300),
+                                   # the contiguous Bluestein passes at the convolution lengths 384, 1280, 1536
+                                   (3, 360), (3, 1200), (3, 1400)])
 def test_rfftn_irfftn_vs_numpy(ctx, shape):
     import torch
 
