@@ -136,6 +136,10 @@ SIGNATURES = {
     "corahip_healpix_block_variance": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, c_int, PTR]),
     "corahip_alm_scale_l": (c_int, [c_void_p, PTR, c_int, c_int, PTR, PTR]),
     "corahip_galaxy_combine": (c_int, [c_void_p, PTR, PTR, PTR, PTR, PTR, c_double, PTR, c_int, c_int, ctypes.c_long, PTR]),
+    "corahip_eig_top_max_f": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "corahip_eig_top_batched": (c_int, [c_void_p, PTR, c_int, c_int, c_int, c_int, PTR, PTR, PTR]),
+    "corahip_constrained_weights": (c_int, [c_void_p, PTR, c_int, c_int, c_int, PTR, PTR, PTR]),
+    "corahip_alm_mix_l": (c_int, [c_void_p, PTR, c_int, c_int, PTR, c_int, PTR]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -1781,6 +1785,110 @@ class Context:
         lnrd = self.to_device(lnr)
         _check(self.lib.corahip_galaxy_combine(self.h, self._f64(fg), self._f64(fgs), self._f64(haslam), self._f64(sc),
                                                self._f64(am), 1.0 / mv, self._f64(lnrd), nchan, skip, npix, self._f64(out)))
+        return out
+
+    # -- mkconstrained (csrc/constrained.hip) ------------------------------------------------------------------------------
+    EIG_TOP_MAX_K = 8
+
+    def _stack3(self, t, name, last=None):
+        """A contiguous float64 device tensor [n, F, last]: (n, F, last)."""
+        torch = _torch()
+        if (not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float64 or t.device != self.device
+                or not t.is_contiguous() or min(t.shape) < 1 or (last is not None and t.shape[2] != last)):
+            raise ValueError("%s must be a contiguous float64 [n, F, %s] tensor on %s (got %r)"
+                             % (name, "F" if last is None else last, self.device, tuple(getattr(t, "shape", ()))))
+        return tuple(int(s) for s in t.shape)
+
+    def eig_top_max_f(self):
+        """Most channels ``eig_top_batched`` takes: its two F x 16 blocks live in the LDS of one workgroup."""
+        n = c_int(0)
+        _check(self.lib.corahip_eig_top_max_f(self.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def eig_top_batched(self, C, k, max_iter=None, out=None):
+        """The ``k`` algebraically largest eigenpairs of every symmetric ``C[l]`` (device [L, F, F], lower triangle read):
+        ``(V, theta, info)`` with V [L, F, k] as ``scipy.linalg.eigh(C[l])[1][:, -k:]`` up to the signs of the columns,
+        theta [L, k] ascending, info [L] int32: 0 = block orthogonal iteration, 1 = full Jacobi decomposition (a block
+        that has not met the stop rule ``|C v - theta v| <= 8 F u |C|_inf`` after ``max_iter`` products; default: the
+        library's).  ``1 <= k <= min(8, F)``, ``F <= eig_top_max_f()``.  ``out``: optional ``(V, theta, info)`` to fill."""
+        torch = _torch()
+        L, F, F2 = self._stack3(C, "C")
+        if F2 != F:
+            raise ValueError("C must be [L, F, F] (got %r)" % (tuple(C.shape),))
+        k = int(k)
+        if not 1 <= k <= min(self.EIG_TOP_MAX_K, F):
+            raise ValueError("eig_top_batched: k must be in 1 .. min(%d, F = %d) (got %d)" % (self.EIG_TOP_MAX_K, F, k))
+        max_iter = 0 if max_iter is None else int(max_iter)
+        if max_iter < 0:
+            raise ValueError("eig_top_batched: max_iter must be positive (got %d)" % max_iter)
+        if out is None:
+            V, theta = self.empty((L, F, k)), self.empty((L, k))
+            info = torch.empty((L,), dtype=torch.int32, device=self.device)
+        else:
+            V, theta, info = out
+            V, theta = self._out_like(V, (L, F, k), "eig_top_batched"), self._out_like(theta, (L, k), "eig_top_batched")
+            if (not isinstance(info, torch.Tensor) or tuple(info.shape) != (L,) or info.dtype != torch.int32
+                    or info.device != self.device or not info.is_contiguous()):
+                raise ValueError("eig_top_batched: info must be a contiguous int32 [%d] tensor on %s" % (L, self.device))
+            ts = ((C, "C"), (V, "V"), (theta, "theta"), (info, "info"))
+            for i in range(1, 4):
+                for j in range(i):
+                    a, b = ts[i][0], ts[j][0]
+                    if self._overlap(a, a.numel() * a.element_size(), b, b.numel() * b.element_size()):
+                        raise ValueError("eig_top_batched: %s overlaps %s" % (ts[i][1], ts[j][1]))
+        fmax = self.eig_top_max_f()
+        if F > fmax:
+            raise ValueError("eig_top_batched: F = %d channels exceed the limit of %d" % (F, fmax))
+        _check(self.lib.corahip_eig_top_batched(self.h, self._f64(C), L, F, k, max_iter, self._f64(V), self._f64(theta),
+                                                self._p(info)))
+        return V, theta, info
+
+    def constrained_weights(self, V, f_ind):
+        """``W[l] = V[l] (V[l][f_ind, :])^-1`` for device V [L, F, k] (``eig_top_batched``) and the ``k`` constrained
+        channels ``f_ind`` (host integers): W [L, F, k], the weights that carry the constraint a_lm to all channels
+        (cora/core/skysim.py:180-194).  ``W[0] = 0`` whatever ``V[0]`` holds.  A singular ``V[l][f_ind, :]`` (an exactly
+        zero pivot; always when ``f_ind`` repeats a channel) raises ``numpy.linalg.LinAlgError`` naming the first such l."""
+        torch = _torch()
+        L, F, k = self._stack3(V, "V")
+        if not k <= min(self.EIG_TOP_MAX_K, F):
+            raise ValueError("constrained_weights: k must be in 1 .. min(%d, F = %d) (got %d)" % (self.EIG_TOP_MAX_K, F, k))
+        f_ind = np.asarray(f_ind)
+        if f_ind.shape != (k,) or f_ind.dtype.kind not in "iu":
+            raise ValueError("f_ind must hold %d integer channel indices (got %r)" % (k, f_ind))
+        if f_ind.min() < 0 or f_ind.max() >= F:
+            raise ValueError("f_ind must lie in 0 .. %d (got %r)" % (F - 1, f_ind.tolist()))
+        fi = np.ascontiguousarray(f_ind, dtype=np.int32)
+        W = self.empty((L, F, k))
+        info = torch.empty((L,), dtype=torch.int32, device=self.device)
+        _check(self.lib.corahip_constrained_weights(self.h, self._f64(V), L, F, k, fi.ctypes.data_as(c_void_p), self._f64(W),
+                                                    self._p(info)))
+        bad = torch.nonzero(info == 2)
+        if bad.numel():
+            raise np.linalg.LinAlgError("constrained_weights: the constrained rows of the eigenvectors are singular at l = %d"
+                                        % int(bad[0, 0]))
+        return W
+
+    def alm_mix_l(self, alm, lmax, W, out=None):
+        """``out[f, lm] = sum_j W[l, f, j] alm[j, lm]`` for a_lm in the device layout: ``alm`` [nalm, ceil(k / 4), 2, 4],
+        ``W`` [lmax + 1, F, k] on the device, result [nalm, ceil(F / 4), 2, 4].  j is summed in ascending order; the padding
+        channels of ``alm`` are not used and those of the result are zero.  ``out`` must not overlap an input."""
+        torch = _torch()
+        lmax = int(lmax)
+        nalm = (lmax + 1) * (lmax + 2) // 2
+        if (not isinstance(alm, torch.Tensor) or alm.dim() != 4 or alm.shape[0] != nalm or tuple(alm.shape[2:]) != (2, 4)
+                or alm.dtype != torch.float64 or alm.device != self.device or not alm.is_contiguous() or alm.shape[1] < 1):
+            raise ValueError("alm must be a contiguous float64 [%d, G, 2, 4] tensor on %s" % (nalm, self.device))
+        G = int(alm.shape[1])
+        L, F, k = self._stack3(W, "W")
+        if L != lmax + 1 or not 4 * (G - 1) < k <= 4 * G:
+            raise ValueError("W must be [lmax + 1, F, k] with %d < k <= %d (got %r)" % (4 * (G - 1), 4 * G, tuple(W.shape)))
+        out = self._out_like(out, (nalm, (F + 3) // 4, 2, 4), "alm_mix_l")
+        for t, name in ((alm, "alm"), (W, "W")):
+            if self._overlap(out, out.numel() * 8, t, t.numel() * 8):
+                raise ValueError("alm_mix_l: out overlaps %s" % name)
+        if out.data_ptr() % 32 or alm.data_ptr() % 32:
+            raise ValueError("alm_mix_l: alm and out must be 32-byte aligned")
+        _check(self.lib.corahip_alm_mix_l(self.h, self._f64(alm), lmax, k, self._f64(W), F, self._f64(out)))
         return out
 
     def sht_rings(self, nside, lmax):

@@ -545,15 +545,89 @@ def clarray_from_maps(maps, lmax=None, niter=None, use_weights=None):
     return cl.cpu().numpy()
 
 
+def constrained_weights_device(corr, f_ind, max_iter=None):
+    """The weights of :func:`mkconstrained` on the device: ``(W, info)`` with ``W[l] = V_k (V_k[f_ind, :])^-1`` [L, F, k],
+    ``V_k`` the eigenvectors of the ``k = len(f_ind)`` largest eigenvalues of ``corr[l]`` (cora/core/skysim.py:180-194), so
+    that the constrained a_lm of channel f are ``sum_j W[l, f, j] c_j(l, m)``.  ``W[0] = 0`` and ``corr[0]`` is not read.
+    ``W`` depends on the invariant subspace alone, not on the signs or the basis the eigensolver returns.
+
+    corr : ndarray or device tensor [L, F, F].  ``info`` [L] int32: the route ``Context.eig_top_batched`` took for each l
+    (0 = block iteration, 1 = full decomposition; ``max_iter`` as there).  A singular ``V_k[f_ind, :]`` raises
+    ``numpy.linalg.LinAlgError`` as the reference's ``solve`` does."""
+    import torch
+
+    ctx = _lib.get_context()
+    if not isinstance(corr, torch.Tensor):
+        corr = ctx.to_device(corr)
+    if corr.dim() != 3 or corr.shape[2] != corr.shape[1]:
+        raise Exception("Correlation matrix is incorrect shape.")
+    f_ind = [int(f) for f in f_ind]
+    L, F, k = int(corr.shape[0]), int(corr.shape[1]), len(f_ind)
+    if k > ctx.EIG_TOP_MAX_K:
+        raise ValueError("mkconstrained on the device takes at most %d constraints (got %d)" % (ctx.EIG_TOP_MAX_K, k))
+    V = torch.zeros((L, F, k), dtype=torch.float64, device=ctx.device)
+    theta = torch.zeros((L, k), dtype=torch.float64, device=ctx.device)
+    info = torch.zeros((L,), dtype=torch.int32, device=ctx.device)
+    if L > 1:
+        ctx.eig_top_batched(corr[1:].contiguous(), k, max_iter=max_iter, out=(V[1:], theta[1:], info[1:]))
+    return ctx.constrained_weights(V, f_ind), info
+
+
+def mkconstrained_device(corr, constraints, nside):
+    """:func:`mkconstrained` with every step on the device: returns a device tensor [numz, npix].
+
+    The constraint maps (device tensors or arrays, one nside) are analysed as in the host route
+    (``map2alm_device(use_weights=False, niter=3)``), mixed into all channels by ``Context.alm_mix_l`` with the weights
+    of :func:`constrained_weights_device`, and synthesised by ``Context.alm2map``.  The a_lm of the channels exist only
+    in the device layout; apart from the constrained indices nothing crosses to or from the host."""
+    import torch
+
+    from ..util import hputil
+
+    ctx = _lib.get_context()
+    nmodes = len(constraints)
+    if nmodes > ctx.EIG_TOP_MAX_K:
+        raise ValueError("mkconstrained on the device takes at most %d constraints (got %d)" % (ctx.EIG_TOP_MAX_K, nmodes))
+    if corr.shape[2] != corr.shape[1]:
+        raise Exception("Correlation matrix is incorrect shape.")
+    numz = int(corr.shape[1])
+    maxl = int(corr.shape[0]) - 1
+    f_ind = [int(c[0]) for c in constraints]
+    cons = torch.stack([c[1] if isinstance(c[1], torch.Tensor) else ctx.to_device(np.asarray(c[1], dtype=np.float64))
+                        for c in constraints]).to(device=ctx.device, dtype=torch.float64).contiguous()
+    ns_c = int(round(np.sqrt(cons.shape[1] / 12.0)))
+    W, _ = constrained_weights_device(corr, f_ind)
+    calm = hputil.map2alm_device(cons, ns_c, maxl, use_weights=False, niter=3)
+    alm = ctx.alm_mix_l(calm, maxl, W)
+    return ctx.alm2map(alm, int(nside), maxl, numz)
+
+
 def mkconstrained(corr, constraints, nside):
     """Maps satisfying given constraints on some frequency slices, built from the lowest eigenmodes
     (cora/core/skysim.py:139-205).
 
     corr [lmax+1, numz, numz]; constraints = [[frequency_index, healpix map], ...]; returns [numz, npix].
-    The per-l symmetric eigenproblems and the nmodes x nmodes solves stay on the host (scipy, as the
-    reference); the two transforms the reference takes from healpy - ``map2alm(cons, lmax=maxl)`` with
-    healpy's defaults (iter=3, no ring weights) and ``alm2map`` of every channel - run on the GPU in
-    one batch each."""
+    Constraint maps given as device tensors take :func:`mkconstrained_device` and a device tensor comes back (``corr`` an
+    array or a tensor; at most 8 constraints).  With numpy maps the per-l symmetric eigenproblems and the nmodes x nmodes
+    solves stay on the host (scipy, as the reference); the two transforms the reference takes from healpy -
+    ``map2alm(cons, lmax=maxl)`` with healpy's defaults (iter=3, no ring weights) and ``alm2map`` of every channel - run
+    on the GPU in one batch each."""
+    import torch
+
+    on_dev = [isinstance(c[1], torch.Tensor) for c in constraints]
+    if any(on_dev):
+        if not all(on_dev):
+            raise ValueError("mkconstrained: the constraint maps must be all device tensors or all arrays")
+        if len(constraints) > 8:
+            raise ValueError("mkconstrained on the device takes at most 8 constraints (got %d): pass numpy maps for the "
+                             "host route" % len(constraints))
+        return mkconstrained_device(corr, constraints, nside)
+    if isinstance(corr, torch.Tensor):
+        corr = corr.cpu().numpy()
+    return _mkconstrained_host(corr, constraints, nside)
+
+
+def _mkconstrained_host(corr, constraints, nside):
     import scipy.linalg as la
     import torch
 

@@ -170,6 +170,16 @@ __host__ __device__ static inline long alm_idx(int l, int m, int lmax) {
     return (long)m * (2 * lmax + 1 - m) / 2 + l;
 }
 
+// l of packed index idx: m is the last one whose first entry (l = m), at m (2 lmax + 3 - m) / 2, is not beyond idx
+__device__ static inline long alm_l_of_idx(long idx, int lmax) {
+    const double b = 2.0 * lmax + 3.0;
+    long m = (long)((b - sqrt(b * b - 8.0 * (double)idx)) * 0.5);
+    m = m < 0 ? 0 : (m > lmax ? lmax : m);
+    while (m > 0 && m * (2L * lmax + 3 - m) / 2 > idx) m--;
+    while (m < lmax && (m + 1) * (2L * lmax + 2 - m) / 2 <= idx) m++;
+    return idx - m * (2L * lmax + 1 - m) / 2;
+}
+
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N-1>), in order

@@ -101,13 +101,7 @@ __global__ __launch_bounds__(256) void gx_alm_scale_kernel(const double *alm, in
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (long)gridDim.x * blockDim.x) {
         const long idx = q / G;
         const int g = (int)(q - idx * G);
-        // m: the last one whose first entry (l = m), at m (2 lmax + 3 - m) / 2, is not beyond idx
-        const double b = 2.0 * lmax + 3.0;
-        long m = (long)((b - sqrt(b * b - 8.0 * (double)idx)) * 0.5);
-        m = m < 0 ? 0 : (m > lmax ? lmax : m);
-        while (m > 0 && m * (2L * lmax + 3 - m) / 2 > idx) m--;
-        while (m < lmax && (m + 1) * (2L * lmax + 2 - m) / 2 <= idx) m++;
-        const long l = idx - m * (2L * lmax + 1 - m) / 2;
+        const long l = alm_l_of_idx(idx, lmax);
         const d4_t re = *reinterpret_cast<const d4_t *>(alm + q * 8), im = *reinterpret_cast<const d4_t *>(alm + q * 8 + 4);
         d4_t ore, oim;
 #pragma unroll

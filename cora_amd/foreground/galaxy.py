@@ -5,7 +5,7 @@ of the galactic synchrotron emission.
 ``ConstrainedGalaxy.getsky`` runs on the device: the Gaussian maps (``skysim.mkfullsky_device``), the three beam
 smoothings in one batch (``hputil.smoothing_device``), the variance chain (``Context.healpix_block_variance``), the
 last third of the routine in one streaming launch (``Context.galaxy_combine``) and the rotation into celestial
-co-ordinates; ``skysim.mkconstrained`` keeps its per-l eigenproblems on the host.  ``getpolsky`` multiplies that sky by
+co-ordinates; ``skysim.mkconstrained`` takes the smoothed maps as device tensors and stays on the device (csrc/constrained.hip).  ``getpolsky`` multiplies that sky by
 the polarised fraction of :func:`polarised_fraction_device` (galaxy.py:209-344; csrc/faraday.hip).  The sky data
 (``skydata.npz``: Haslam map, spectral-index maps, Faraday map) is not part of this package: the class takes the file's
 path or the arrays."""
@@ -366,7 +366,7 @@ class ConstrainedGalaxy(maps.Sky3d):
         efreq = np.concatenate((np.array([408.0, 1420.0]), np.asarray(self.nu_pixels, dtype=np.float64)))
 
         # the random fluctuations
-        cla = skysim.clarray(syn.angular_powerspectrum, lmax, efreq, zromb=0)
+        cla = skysim.clarray_device(syn.angular_powerspectrum, lmax, efreq, zromb=0)
         fg = skysim.mkfullsky_device(cla, nside, rng=rng)
 
         # the three smoothings of galaxy.py:160-161 and :176 in one batch: fg[0] at fwhm 1 deg, fg[1] at fwhm 5.8 deg,
@@ -376,9 +376,9 @@ class ConstrainedGalaxy(maps.Sky3d):
         sm = hputil.smoothing_device(fg[[0, 1, 0]], fl=beams)
 
         # maps constrained to the smoothed ones: at both frequencies (GSM) or at the Haslam frequency alone
-        sub = ctx.to_host(sm[:2])
-        cons = [(0, sub[0]), (1, sub[1])] if self.spectral_map == "gsm" else [(0, sub[0])]
-        fgs = ctx.to_device(skysim.mkconstrained(cla, cons, nside))
+        # (device tensors: mkconstrained stays on the device and returns a device tensor)
+        cons = [(0, sm[0]), (1, sm[1])] if self.spectral_map == "gsm" else [(0, sm[0])]
+        fgs = skysim.mkconstrained(cla, cons, nside)
 
         haslam = hputil.ud_grade(ctx.to_device(self._haslam), nside)
         sc = hputil.ud_grade(ctx.to_device(spectral), nside)

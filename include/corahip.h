@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -700,6 +700,30 @@ int corahip_healpix_block_variance(corahip_ctx *ctx, const double *maps, long nm
 int corahip_alm_scale_l(corahip_ctx *ctx, const double *alm, int lmax, int nnu, const double *fl, double *out);
 int corahip_galaxy_combine(corahip_ctx *ctx, const double *fg, const double *fgs, const double *haslam, const double *sc,
                            const double *am, double inv_mv, const double *lnr, int nchan, int skip, long npix, double *out);
+
+/* ---- mkconstrained (cora/core/skysim.py:139-201; csrc/constrained.hip) -------------------------------------------------
+ * All FP64, no atomics, fixed reduction orders: the same bits from call to call.
+ * eig_top_batched: the k algebraically largest eigenpairs of every symmetric C[l] (C [nl, F, F], the lower triangle is
+ *            read): V [nl, F, k] with orthonormal columns in ascending eigenvalue order, as scipy.linalg.eigh(C[l])[1][:, -k:],
+ *            theta [nl, k] their eigenvalues, info [nl]: 0 = block orthogonal iteration (16 columns, FP64 MFMA products,
+ *            Rayleigh-Ritz by Jacobi in LDS), 1 = full Jacobi decomposition.  The iteration stops when every one of the k
+ *            pairs has |C v - theta v|_2 <= 8 F 2^-53 |C|_inf; a block that has not got there after max_iter products
+ *            (max_iter <= 0: the library's default), or whose negative eigenvalues outweigh the wanted ones, takes the
+ *            full decomposition.  1 <= k <= min(8, F); F up to the limit eig_top_max_f reports (two F x 16 blocks in the
+ *            LDS of a workgroup), EINVAL beyond.  The outputs must not overlap C or each other.  Synchronises the stream.
+ * constrained_weights: W[l] = V[l] (V[l][f_ind, :])^-1 ([nl, F, k]) by LU with partial pivoting; W[0] = 0 and V[0] is not
+ *            read (:191-192).  f_ind: k HOST indices into 0 .. F - 1 (EINVAL outside).  info [nl]: 0, or 2 where a pivot is
+ *            exactly zero (scipy's solve raises there) - for every l >= 1 when f_ind names a channel twice; W[l] is NaN then.
+ * alm_mix_l: alm_out[f, lm] = sum_j W[l, f, j] alm_in[j, lm], j ascending, for a_lm in the device layout
+ *            [nalm][ceil(n / 4)][re, im][4] (n = k channels in, F out; packed index m (2 lmax + 1 - m) / 2 + l) and
+ *            W [lmax + 1, F, k].  The padding channels of the input are not used, those of the output are written as 0.
+ *            alm_out must not overlap an input; both a_lm pointers 32-byte aligned.                                    */
+int corahip_eig_top_max_f(corahip_ctx *ctx, int *max_f);
+int corahip_eig_top_batched(corahip_ctx *ctx, const double *C, int nl, int F, int k, int max_iter, double *V, double *theta,
+                            int32_t *info);
+int corahip_constrained_weights(corahip_ctx *ctx, const double *V, int nl, int F, int k, const int32_t *f_ind, double *W,
+                                int32_t *info);
+int corahip_alm_mix_l(corahip_ctx *ctx, const double *alm_in, int lmax, int k, const double *W, int F, double *alm_out);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,

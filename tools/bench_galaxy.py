@@ -10,8 +10,11 @@ channels; prints one JSON line.
         the children, a gather back (the reference's two reordered copies);
   (iii) one batched ``smoothing_device`` of three maps;
   (iv)  the stages of one ``ConstrainedGalaxy.getsky_device`` call, timed one by one on the host clock with a device
-        synchronisation after each: clarray, mkfullsky, smoothing, the host part of mkconstrained (with its two
-        transforms), the upload, the variance chain, combine, rotation.
+        synchronisation after each: clarray, mkfullsky, smoothing, mkconstrained, the variance chain, combine, rotation.
+        ``mkconstrained`` is timed on both routes with the same inputs, run alternately ``--reps`` times (median reported):
+        ``mkconstrained_host`` (numpy maps: download, per-l ``eigh`` on the host, the square ``cv`` array, upload) and
+        ``mkconstrained_device`` (tensor maps: ``eig_top_batched``, ``constrained_weights``, ``alm_mix_l``); the share of l
+        that take the full decomposition is reported for the synchrotron C_l and for a 21cm ``clarray`` of the same shape.
 
 Method: one warm-up call per item, then ``--reps`` (>= 5) timed calls with device events around the call
 (ctx.timer_begin / timer_end); the fused and the torch form alternate in one loop; median, minimum and maximum are
@@ -175,7 +178,39 @@ if not a.no_getsky:
     fg = stage("mkfullsky", lambda: skysim.mkfullsky_device(cla, nside, rng=DeviceRNG(1)))
     sm = stage("smoothing", lambda: hputil.smoothing_device(fg[[0, 1, 0]], fl=beams))
     sub = stage("download", lambda: ctx.to_host(sm[:2]))
-    fgs_h = stage("mkconstrained_host", lambda: skysim.mkconstrained(cla, [(0, sub[0])], nside))
+    # mkconstrained: the host route (numpy maps: per-l eigh, the square cv array) and the device route (tensor maps:
+    # eig_top_batched, constrained_weights, alm_mix_l) on the same inputs, run alternately; the median of each
+    cla_d = ctx.to_device(cla)
+    t_h, t_d = [], []
+    for rep in range(a.reps):
+        for name, ts, fn in (("mkconstrained_host", t_h, lambda: skysim.mkconstrained(cla, [(0, sub[0])], nside)),
+                             ("mkconstrained_device", t_d, lambda: skysim.mkconstrained(cla_d, [(0, sm[0])], nside))):
+            before = stages.get(name, 0.0)
+            res = stage(name, fn)
+            ts.append(stages[name] - before)
+            if name == "mkconstrained_host":
+                fgs_h = res
+            else:
+                fgs_d = res
+            print("mkconstrained rep %d %s %.1f ms" % (rep, name, ts[-1]), file=sys.stderr, flush=True)
+    stages["mkconstrained_host"] = round(float(np.median(t_h)), 3)
+    stages["mkconstrained_device"] = round(float(np.median(t_d)), 3)
+    mk = dict(host_ms=ms3((np.median(t_h), min(t_h), max(t_h))), device_ms=ms3((np.median(t_d), min(t_d), max(t_d))),
+              host_over_device=round(float(np.median(t_h) / np.median(t_d)), 2),
+              max_abs_difference_over_rms=float(np.abs(fgs_d.cpu().numpy() - fgs_h).max() / fgs_h.std()))
+    # the share of l that take the full decomposition: the synchrotron C_l of this run, and a 21cm clarray of the same shape
+    mk["fallback_share_synchrotron"] = float((skysim.constrained_weights_device(cla_d, [0])[1][1:] != 0).double().mean())
+    try:
+        from cora_amd.signal import corr21cm
+
+        c21 = skysim.clarray_device(corr21cm.Corr21cm().angular_powerspectrum, lmax, efreq[2:].copy(), zromb=0)
+        i21 = skysim.constrained_weights_device(c21, [0])[1]
+        mk["fallback_share_21cm"] = float((i21[1:] != 0).double().mean())
+        del c21
+    except Exception as e:      # (the 21cm tables need their data file)
+        mk["fallback_share_21cm"] = "not measured: %s" % type(e).__name__
+    line["mkconstrained"] = mk
+    del fgs_d, cla_d
     fgs = stage("upload", lambda: ctx.to_device(fgs_h))
     hs, scs, ams = stage("ud_grade", lambda: tuple(hputil.ud_grade(ctx.to_device(m) if isinstance(m, np.ndarray) else m, nside)
                                                    for m in (gal._haslam, gal._sp_ind["md"], gal._amp_map)))
@@ -185,7 +220,12 @@ if not a.no_getsky:
     del fg, fgs
     stage("rotation", lambda: hputil.rotate_map_device(fgt, hputil.coord_matrix("C", "G")))
     del fgt
+    # totals of the two routes: the host route has the download, the host stage and the upload, the device route its stage
+    dev_ms = stages.pop("mkconstrained_device")
     total = sum(stages.values())
-    line["getsky_stages_ms"] = dict(stages, total=round(total, 3), init_amp_map=init_ms,
-                                    mkconstrained_host_fraction=round(stages["mkconstrained_host"] / total, 3))
+    total_dev = total - stages["download"] - stages["mkconstrained_host"] - stages["upload"] + dev_ms
+    line["getsky_stages_ms"] = dict(stages, mkconstrained_device=dev_ms, total=round(total, 3), total_device_route=round(total_dev, 3),
+                                    init_amp_map=init_ms,
+                                    mkconstrained_host_fraction=round(stages["mkconstrained_host"] / total, 3),
+                                    mkconstrained_device_fraction=round(dev_ms / total_dev, 3))
 print(json.dumps(line))
