@@ -140,6 +140,10 @@ SIGNATURES = {
     "corahip_eig_top_batched": (c_int, [c_void_p, PTR, c_int, c_int, c_int, c_int, PTR, PTR, PTR]),
     "corahip_constrained_weights": (c_int, [c_void_p, PTR, c_int, c_int, c_int, PTR, PTR, PTR]),
     "corahip_alm_mix_l": (c_int, [c_void_p, PTR, c_int, c_int, PTR, c_int, PTR]),
+    "corahip_sinc_romb": (c_int, [c_void_p, PTR, PTR, c_int, c_double, PTR, c_int, PTR]),
+    "corahip_fftlog_phase": (c_int, [c_void_p, c_double, c_double, ctypes.c_int64, PTR]),
+    "corahip_logconv": (c_int, [c_void_p, PTR, PTR, ctypes.c_int64, c_int, c_int]),
+    "corahip_logconv_split": (c_int, [ctypes.c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
@@ -1261,6 +1265,84 @@ class Context:
         _check(self.lib.corahip_legendre_project(self.h, self._f64(mu), self._f64(wt), nm, lmax, self._f64(xi),
                                                  ncol, self._f64(out)))
         return out
+
+    # -- P(k) -> xi(r) (csrc/pk2xi.hip) --------------------------------------------------
+    LOGCONV_MAX_LINE = 4096      # longest line of the FFT passes behind ``logconv``
+
+    def _dev1d(self, t, name, n=None, dtype=None):
+        """A contiguous 1-D device tensor of ``dtype`` (default float64) and, if given, length ``n``: its length."""
+        torch = _torch()
+        dtype = dtype or torch.float64
+        if (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != dtype or t.device != self.device
+                or not t.is_contiguous() or (n is not None and t.numel() != n)):
+            raise ValueError("%s must be a contiguous %s [%s] tensor on %s (got %r)"
+                             % (name, str(dtype).replace("torch.", ""), "n" if n is None else n, self.device,
+                                tuple(getattr(t, "shape", ()))))
+        return int(t.numel())
+
+    def sinc_romb(self, g, ka, dlk, r, out=None):
+        """``out[j] = dlk * scipy.integrate.romb(g * sinc(ka * r[j]))`` (sinc(x) = sin x / x, 1 at 0) for ``g`` and ``ka``
+        of ``2^k + 1`` samples, 1 <= k <= 24, and separations ``r`` [nr], all on the device.  With
+        ``g = P(ka) ka^3 / 2 pi^2`` and ``dlk`` the logarithmic step of ``ka`` this is the reference's ``_corr_direct``.
+        The summation order is fixed: the same call returns the same bits."""
+        n = self._dev1d(g, "g")
+        k = (n - 1).bit_length() - 1
+        if n < 3 or n != (1 << k) + 1 or k > 24:
+            raise ValueError("sinc_romb: g must have 2^k + 1 samples with 1 <= k <= 24 (got %d)" % n)
+        self._dev1d(ka, "ka", n)
+        nr = self._dev1d(r, "r")
+        out = self._out_like(out, (nr,), "sinc_romb")
+        for t, name in ((g, "g"), (ka, "ka"), (r, "r")):
+            if self._overlap(out, nr * 8, t, t.numel() * 8):
+                raise ValueError("sinc_romb: out overlaps %s" % name)
+        _check(self.lib.corahip_sinc_romb(self.h, self._f64(g), self._f64(ka), k, float(dlk), self._f64(r), nr,
+                                          self._f64(out)))
+        return out
+
+    def fftlog_phase(self, mu, L, N, out=None):
+        """``U_m = exp(i (eta ln 2 + 2 Im lnGamma((mu + 1 + i eta) / 2)))``, ``eta = 2 pi m / L``, m = 0 .. N // 2: the
+        unit-modulus FFTLog kernel at bias q = 0 as a complex128 device tensor [N // 2 + 1]."""
+        torch = _torch()
+        N, mu, L = int(N), float(mu), float(L)
+        if N < 1 or not mu > -1.0 or not L > 0.0:
+            raise ValueError("fftlog_phase needs N >= 1, mu > -1 and L > 0 (got N = %d, mu = %r, L = %r)" % (N, mu, L))
+        if out is None:
+            out = self.empty((N // 2 + 1,), dtype=torch.complex128)
+        self._dev1d(out, "fftlog_phase: out", N // 2 + 1, torch.complex128)
+        _check(self.lib.corahip_fftlog_phase(self.h, mu, L, N, self._c128(out)))
+        return out
+
+    @staticmethod
+    def logconv_split(N):
+        """``(N1, N2)`` with ``N1 * N2 == N`` that ``logconv`` takes: ``(N, 1)`` up to 4096 points, else the cheapest pair
+        of divisors that are both at most 4096.  ValueError when N has none.  Needs no GPU."""
+        N = int(N)
+        if N < 1:
+            raise ValueError("logconv_split: N must be positive (got %d)" % N)
+        n1, n2 = c_int(0), c_int(0)
+        if load().corahip_logconv_split(N, ctypes.byref(n1), ctypes.byref(n2)) != 0:
+            raise ValueError("logconv: N = %d cannot be written as N1 * N2 with both factors <= %d (it has a prime factor "
+                             "above %d or exceeds %d^2): choose samples_per_decade and the pads so that it can"
+                             % (N, Context.LOGCONV_MAX_LINE, Context.LOGCONV_MAX_LINE, Context.LOGCONV_MAX_LINE))
+        return int(n1.value), int(n2.value)
+
+    def logconv(self, data, u, split=None):
+        """In place ``data <- irfft(rfft(data.real) * u)``: the circular convolution of a real signal, held as a complex128
+        device tensor [N] with zero imaginary parts, with the kernel whose half spectrum is ``u`` [N // 2 + 1].  On return
+        the real parts are the result (natural order) and the imaginary parts rounding residue.  ``split`` = (N1, N2)
+        chooses the four-step factorisation (default ``logconv_split(N)``); a unit factor means a single line transform."""
+        torch = _torch()
+        N = self._dev1d(data, "data", None, torch.complex128)
+        if N < 1:
+            raise ValueError("logconv: data is empty")
+        self._dev1d(u, "u", N // 2 + 1, torch.complex128)
+        n1, n2 = self.logconv_split(N) if split is None else (int(split[0]), int(split[1]))
+        if n1 < 1 or n2 < 1 or n1 * n2 != N or max(n1, n2) > self.LOGCONV_MAX_LINE:
+            raise ValueError("logconv: split %r does not factor N = %d into factors <= %d" % ((n1, n2), N, self.LOGCONV_MAX_LINE))
+        if self._overlap(data, N * 16, u, u.numel() * 16):
+            raise ValueError("logconv: data overlaps u")
+        _check(self.lib.corahip_logconv(self.h, self._c128(data), self._c128(u), N, n1, n2))
+        return data
 
     # -- n4: flat-sky fields -----------------------------------------------------------
     def _c128(self, t):

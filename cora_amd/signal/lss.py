@@ -399,6 +399,34 @@ def biased_lss_to_map(delta, lognormal=False, map_prefactor=1.0, T_b=None, polar
     return ctx.to_host(biased_lss_to_map_device(ctx.to_device(delta), lognormal, map_prefactor, T_b, polarisation))
 
 
+def calculate_correlations(ps, minlogr=-1, maxlogr=5, switchlogr=1, samples_per_decade=1000, ksmooth=None,
+                           logkcut_low=-4, logkcut_high=4):
+    """The density, cross and potential correlation functions of a power spectrum: the body of
+    ``CalculateCorrelations.process`` (lss.py:106-179) -> ``{"corr0", "corr2", "corr4"}``, each a
+    ``cubicspline.SinhInterpolater`` ready for ``corrfunc.corr_to_clarray``.
+
+    ps : P(k) at z = 0, a vectorised callable (the reference's ``powerspectrum(k, 0.0)``).  It is regularised by power-law
+    cut-offs at ``logkcut_low`` / ``logkcut_high`` and a Gaussian of width ``ksmooth`` (None: none) and transformed with
+    ``corrfunc.ps_to_corr`` (pads 4 / 6, nine Richardson levels) as P, P / k^2 and P / k^4.  ``ps`` is evaluated on the
+    host, once per wavenumber grid: the three transforms share the samples."""
+    from ..util import cubicspline
+    from . import corrfunc
+
+    ks = 1e10 if ksmooth is None else ksmooth
+    plan = corrfunc._CorrPlan(minlogr, maxlogr, switchlogr, samples_per_decade, pad_low=4, pad_high=6, richardson_n=9)
+
+    def _ps(k):
+        return np.reshape(lssutil.cutoff(k, logkcut_low, 1, 0.5, 6) * lssutil.cutoff(k, logkcut_high, -1, 0.5, 4)
+                          * np.exp(-0.5 * (k / ks) ** 2) * ps(k), -1)
+
+    pd, pf = _ps(plan.kdirect), _ps(plan.kfine)
+    out = {}
+    for n, f_t in ((0, 1e-3), (2, 1e-6), (4, 1e2)):
+        c = plan.run(pd * plan.kdirect**-n, pf * plan.kfine**-n).cpu().numpy()
+        out["corr%d" % n] = cubicspline.SinhInterpolater(np.column_stack([plan.r, c]), x_t=plan.r[1], f_t=f_t)
+    return out
+
+
 def tracer_map_device(phi, delta, chi, D, f, b1, b2=None, sigmaP=None, dynamics="zeldovich", lognormal=False,
                       lightcone=True, redshift_space=True, fog_D=None, alpha_FoG=1.0, band_cut=None,
                       map_lognormal=False, map_prefactor=1.0, T_b=None, polarisation=True, sigma_chi=None, lmax=None,

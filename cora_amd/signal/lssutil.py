@@ -165,6 +165,16 @@ def calculate_width(centres):
     return np.abs(widths)
 
 
+def cutoff(x, cut, sign, width, index):
+    """Roughly one, then a power-law drop-off (lssutil.py:264-290): ``(0.5 (1 + tanh(sign (log10 x - cut) / width)))^index``.
+
+    cut : location of the cut in log10; sign : +1 cuts off lower values, -1 higher ones; width : width of the transition in
+    decades; index : steepness, roughly the power-law index of the cut region.  Host arithmetic: it regularises the power
+    spectrum that ``corrfunc.ps_to_corr`` evaluates on the host."""
+    sign = np.sign(sign)
+    return (0.5 * (1 + np.tanh(sign * (np.log10(x) - cut) / width))) ** index
+
+
 def exponential_FoG_kernel(chi, sigmaP, D):
     """The ``len(chi) x len(chi)`` exponential smoothing matrix that approximates Fingers of God
     (cora/signal/lssutil.py:518-589): the Fourier conjugate of a Lorentzian ``(1 + k_par^2 sigmaP^2 / 2)^-1``,

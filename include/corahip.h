@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -444,6 +444,25 @@ int corahip_xi_table_average(corahip_ctx *ctx, const double *knots_x, const doub
                              double *out);
 int corahip_legendre_project(corahip_ctx *ctx, const double *mu, const double *wt, int nm, int lmax,
                              const double *xi, long ncol, double *out);
+
+/* ---- P(k) -> xi(r) (csrc/pk2xi.hip) --------------------------------------------------------
+ * The numerical halves of corrfunc.ps_to_corr (cora/signal/corrfunc.py:72-84, 150-264).
+ * sinc_romb:     out[j] = dlk romb_i(g[i] sinc(ka[i] r[j])) over the 2^k + 1 samples i, 1 <= k <= 24, unit spacing
+ *                (scipy.integrate.romb as _corr_direct uses it; the caller passes g = P(ka) ka^3 / 2 pi^2).
+ *                sinc(0) = 1; nothing of size nr x 2^k is stored; a repeated call returns the same bits.
+ * fftlog_phase:  u[m] = exp(i (eta ln 2 + 2 Im lnGamma((mu + 1 + i eta) / 2))), eta = 2 pi m / L, m = 0 .. N / 2
+ *                (complex [N / 2 + 1]): the FFTLog kernel at q = 0.  mu > -1, L > 0.
+ * logconv:       data <- irfft(rfft(data) u) in place for a real signal of length N = N1 N2 held as complex
+ *                [N] (imaginary parts zero on entry, rounding residue on return); u complex [N / 2 + 1].  A unit
+ *                factor means one line transform each way (N <= 4096); otherwise the four-step scheme on the
+ *                [N1, N2] view, both factors <= 4096.
+ * logconv_split: a split logconv takes: (N, 1) for N <= 4096, else the cheapest pair of divisors, both <= 4096;
+ *                CORAHIP_EINVAL when there is none (N has a prime factor above 4096, or N > 4096^2).  No GPU needed. */
+int corahip_sinc_romb(corahip_ctx *ctx, const double *g, const double *ka, int k, double dlk, const double *r,
+                      int nr, double *out);
+int corahip_fftlog_phase(corahip_ctx *ctx, double mu, double L, int64_t N, double *u);
+int corahip_logconv(corahip_ctx *ctx, double *data, const double *u, int64_t N, int N1, int N2);
+int corahip_logconv_split(int64_t N, int *N1, int *N2);
 
 /* ---- flat-sky Gaussian fields (flat-sky half) ------------------------------
  * n-dimensional FFTs over C-contiguous device arrays, complex = interleaved (re, im) float64; every
