@@ -205,3 +205,20 @@ __device__ static inline void block_sum2(double &a, double &b, double *red) {
     a = ((red[0] + red[2]) + red[4]) + red[6];
     b = ((red[1] + red[3]) + red[5]) + red[7];
 }
+
+// op over the values of the NT threads of a workgroup (NT a power of two) by a halving tree in red [NT] (LDS):
+// red[t] = op(red[t], red[t + s]) for s = NT / 2 .. 1, a fixed order; the result goes to every thread.  Ends with a
+// barrier, so red may be reused at once; whatever the threads wrote before the call is published by it as well.
+template <int NT, class Op>
+__device__ __forceinline__ double block_reduce(double v, double *red, Op op) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = op(red[tid], red[tid + s]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}

@@ -21,6 +21,14 @@
 
 #define CH_NB 32
 
+// jitter = max(diag) * jitter_rel, on every thread of the NT-thread workgroup; red [NT] is LDS scratch
+template <int NT>
+__device__ __forceinline__ double diag_jitter(const double *A, int F, double jitter_rel, double *red) {
+    double dmax = -INFINITY;
+    for (int i = threadIdx.x; i < F; i += NT) dmax = fmax(dmax, A[(size_t)i * F + i]);
+    return block_reduce<NT>(dmax, red, [](double a, double b) { return fmax(a, b); }) * jitter_rel;
+}
+
 // lower Cholesky of C + jitter on the diagonal -> T (upper triangle zeroed); info = 1 on failure
 __global__ void __launch_bounds__(256)
 chol_kernel(const double *__restrict__ C, int F, double jitter_rel, double *__restrict__ T,
@@ -37,18 +45,8 @@ chol_kernel(const double *__restrict__ C, int F, double jitter_rel, double *__re
     const double *A = C + off;
     double *Tl = T + off;
 
-    // jitter = max(diag) * jitter_rel
-    double dmax = -INFINITY;
-    for (int i = tid; i < F; i += 256) dmax = fmax(dmax, A[(size_t)i * F + i]);
-    red[tid] = dmax;
-    if (tid == 0) *flag = 0;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double jit = red[0] * jitter_rel;
-    __syncthreads();
+    if (tid == 0) *flag = 0;             // (published by the barriers of the reduction)
+    const double jit = diag_jitter<256>(A, F, jitter_rel, red);
     // copy lower triangle (+jitter), zero the upper
     for (long q = tid; q < (long)F * F; q += 256) {
         const int i = (int)(q / F), j = (int)(q % F);
@@ -197,8 +195,175 @@ chol_kernel(const double *__restrict__ C, int F, double jitter_rel, double *__re
 //  * three barriers per block column.
 // Ablations of the right-looking MFMA version (F = 256, 2.11 ms): diagonal blocks 0.50, panel solve 0.35, trailing update
 // 0.62, copy-in 0.5 ms.
+//
+// The steps on a tile, on the diagonal block and on a row of the panel are written ONCE, below, for the three
+// left-looking kernels (chol_ll_kernel<false>, chol_ll_kernel<true>, chol_coop_kernel): the kernels deal tiles and rows
+// to waves and threads, stage the factor blocks and synchronise.  tests/test_gpu_factor.py holds the cooperative and
+// the batch kernel to the same bits.
 // ------------------------------------------------------------------------------------
 #define CHM_S 34    // doubles per staged block row
+
+// One wave's view of its matrix: the lane roles of the left-looking kernels and the tile steps that depend on them.
+struct ll_wave {
+    const double *A;     // the input matrix
+    double *Tl;          // its factor (the output)
+    int F;
+    double jit;          // what goes on the diagonal
+    // accumulator tile (a, b), register r <-> row 16 a + kq + 4 r, column 16 b + ri of the 32 x 32 tile (the MFMA's C layout)
+    int ri, kq;
+    // this lane's part of a 32 x 32 block moved as rows: half a row (16 doubles) = row (lane >> 1), columns 16 (lane & 1) ..
+    int srow, scol;
+
+    __device__ __forceinline__ ll_wave(const double *A_, double *Tl_, int F_, double jit_, int lane)
+        : A(A_), Tl(Tl_), F(F_), jit(jit_), ri(lane & 15), kq(lane >> 4), srow(lane >> 1), scol(16 * (lane & 1)) {}
+
+    // (the loads are unconditional - a row past the end reads row 0 and is zeroed by the sign when it is staged: with the
+    //  zeroing at the load the compiler waited for the prefetched values right behind their request)
+    __device__ __forceinline__ void load_block(int row0, int col0, double2 (&v)[8]) const {   // rows row0 .. + 31, columns col0 .. + 31 of the factor
+        const double *src = Tl + (size_t)(row0 + srow < F ? row0 + srow : 0) * F + col0 + scol;
+#pragma unroll
+        for (int q = 0; q < 8; q++) v[q] = *reinterpret_cast<const double2 *>(src + 2 * q);
+    }
+    __device__ __forceinline__ void store_block(double *P, const double2 (&v)[8], double sign, int row0) const {
+        const double sg = row0 + srow < F ? sign : 0.0;
+#pragma unroll
+        for (int q = 0; q < 8; q++)
+            *reinterpret_cast<double2 *>(P + srow * CHM_S + scol + 2 * q) = make_double2(sg * v[q].x, sg * v[q].y);
+    }
+
+    // the tile at rows i0 .., columns kb .. starts from the lower triangle of the INPUT block, the jitter on the diagonal
+    // (has = false: a wave without a tile in this round of the 64-row form holds zeros)
+    __device__ __forceinline__ void tile_init(d4_t (&acc)[2][2], int i0, int kb, bool has = true) const {
+        const int nrow = has ? F : 0;    // (one select: with `has &&` in the test below every element got a branch of its own)
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int row = i0 + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
+                    double v = 0.0;
+                    if (row < nrow && col <= row) v = A[(size_t)row * F + col] + (row == col ? jit : 0.0);
+                    acc[a][b][r] = v;
+                }
+    }
+
+    // acc[a][b] += PA[a] PB[b]^T over the 32 columns of two staged blocks: eight sub-steps of 2 x 2 MFMAs
+    __device__ __forceinline__ void tile_mma(d4_t (&acc)[2][2], const double *PA, const double *PB) const {
+#pragma unroll
+        for (int s = 0; s < 8; s++) {
+            double af[2], bf[2];
+#pragma unroll
+            for (int a = 0; a < 2; a++) {
+                af[a] = PA[(16 * a + ri) * CHM_S + 4 * s + kq];
+                bf[a] = PB[(16 * a + ri) * CHM_S + 4 * s + kq];
+            }
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+                    acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
+        }
+    }
+
+    // the diagonal tile goes to the LDS block D [32][33]
+    __device__ __forceinline__ void tile_to_lds(const d4_t (&acc)[2][2], double *D) const {
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) D[(16 * a + kq + 4 * r) * (CH_NB + 1) + 16 * b + ri] = acc[a][b][r];
+    }
+
+    // an off-diagonal tile is stored for the solve; its mirror block of the upper triangle is zeroed
+    __device__ __forceinline__ void tile_store(const d4_t (&acc)[2][2], int i0, int kb) const {
+#pragma unroll
+        for (int a = 0; a < 2; a++)
+#pragma unroll
+            for (int b = 0; b < 2; b++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int row = i0 + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
+                    if (row < F && col < F) Tl[(size_t)row * F + col] = acc[a][b][r];
+                }
+        if (kb + srow < F) {
+            double *z = Tl + (size_t)(kb + srow) * F + i0 + scol;
+#pragma unroll
+            for (int q = 0; q < 8; q++)
+                if (i0 + scol + 2 * q < F) *reinterpret_cast<double2 *>(z + 2 * q) = make_double2(0.0, 0.0);
+        }
+    }
+};
+
+// Step B: ONE wave factors the nb x nb diagonal block, row i of the block (columns 0 .. i, zeros behind) in row[] of
+// lane i: column jj is scaled by 1 / sqrt(d) (v_rsq_f64 + two Newton steps), broadcast with v_readlane and applied to
+// the rows below.  Lane jj hands 1 / L_jj to put_rdiag(jj, y); where the rows come from and go to is the caller's.
+// Returns true if a pivot was not positive (the rows are then unfinished).
+template <class Put>
+__device__ __forceinline__ bool diag_factor_rows(double (&row)[CH_NB], int nb, int lane, Put put_rdiag) {
+    auto bcast = [](double v, int src) {
+        const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
+        const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+        return __hiloint2double(hi, lo);
+    };
+    bool bad = false;
+#pragma unroll
+    for (int jj = 0; jj < CH_NB; jj++) {
+        if (jj < nb && !bad) {
+            const double d = bcast(row[jj], jj);
+            if (!(d > 0.0)) {  // also catches NaN: LAPACK potrf "not positive definite"
+                bad = true;
+            } else {
+                double y = __builtin_amdgcn_rsq(d);
+                const double hd = 0.5 * d;
+                y = fma(y, fma(-hd * y, y, 0.5), y);
+                y = fma(y, fma(-hd * y, y, 0.5), y);       // 1 / sqrt(d)
+                const double lij = row[jj] * y;            // lane jj: sqrt(d); lanes above jj: unused garbage
+                row[jj] = lij;
+                if (lane == jj) put_rdiag(jj, y);
+#pragma unroll
+                for (int k = jj + 1; k < CH_NB; k++) row[k] = fma(-lij, bcast(lij, k), row[k]);
+            }
+        }
+    }
+    return bad;
+}
+
+// Step C for one row below the diagonal block: x <- x L_jj^{-T} on the 32 doubles at row, in place, against the LDS
+// block D [32][33] and rdiag [32] = 1 / L_jj (nb == 32 whenever there are rows below)
+__device__ __forceinline__ void panel_solve_row(double *row, const double *D, const double *rdiag, int nb) {
+    double x[CH_NB];
+#pragma unroll
+    for (int jj = 0; jj < CH_NB; jj += 2) {
+        const double2 v = *reinterpret_cast<const double2 *>(row + jj);
+        x[jj] = v.x;
+        x[jj + 1] = v.y;
+    }
+    // (the run-time test on nb keeps the 528 reads of D inside the caller's row loop: without it they are hoisted in
+    //  front of it as loop invariants - into 1000 registers, i.e. scratch)
+    // four partial sums per dot product: the 496 multiply-adds of a row are otherwise ONE dependent chain (8 cycles
+    // per link, nothing to overlap it with at one or two waves per SIMD)
+#pragma unroll
+    for (int jj = 0; jj < CH_NB; jj++) {
+        if (jj < nb) {
+            double s[4] = {x[jj], 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int p = 0; p < CH_NB; p++)
+                if (p < jj) s[p & 3] = fma(-x[p], D[jj * (CH_NB + 1) + p], s[p & 3]);
+            x[jj] = ((s[0] + s[1]) + (s[2] + s[3])) * rdiag[jj];
+        }
+    }
+#pragma unroll
+    for (int jj = 0; jj < CH_NB; jj += 2) *reinterpret_cast<double2 *>(row + jj) = make_double2(x[jj], x[jj + 1]);
+}
+
+// dynamic LDS of a left-looking kernel: D [32][33], red [256], the flag (2), rdiag [32], then the staged 32 x 32 blocks -
+// an A and a B block per wave (8), or with the shared B block an A block per wave and the B block twice (6)
+static size_t ll_lds_bytes(bool shared_b) {
+    return sizeof(double) * (CH_NB * (CH_NB + 1) + 256 + 2 + CH_NB + (shared_b ? 6 : 8) * 32 * CHM_S) + 16;
+}
+
 #ifndef CHM_STAMPS
 #define CHM_STAMPS 0   // diagnostic build (make ab ... DEFS=-DCHM_STAMPS=1): s_memtime per phase of chol_ll_kernel, summed over the waves
 #endif
@@ -228,7 +393,6 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
     double *stage = rdiag + CH_NB;                     // per wave: A block [32][CHM_S], B block [32][CHM_S]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ri = lane & 15, kq = lane >> 4;
     const size_t off = (size_t)blockIdx.x * F * F;
     const double *A = C + off;
     double *Tl = T + off;
@@ -236,45 +400,19 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
     double *PA = stage + (size_t)wave * (TALL ? 1 : 2) * 32 * CHM_S, *PB = PA + 32 * CHM_S;
     double *PBS = stage + 4 * 32 * CHM_S;              // (tall) [2][32][CHM_S]
 
-    // jitter = max(diag) * jitter_rel
-    double dmax = -INFINITY;
-    for (int i = tid; i < F; i += 256) dmax = fmax(dmax, A[(size_t)i * F + i]);
-    red[tid] = dmax;
-    if (tid == 0) *flag = 0;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double jit = red[0] * jitter_rel;
-    __syncthreads();
+    if (tid == 0) *flag = 0;             // (published by the barriers of the reduction)
+    const ll_wave w(A, Tl, F, diag_jitter<256>(A, F, jitter_rel, red), lane);
 
 #if CHM_STAMPS
     unsigned long long c_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, c_last;
     { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory"); c_last = _t; }
 #endif
     const int nblk = (F + 31) / 32;
-    // this lane's part of a 32 x 32 block moved as rows: half a row (16 doubles) = row (lane >> 1), columns 16 (lane & 1) ..
-    const int srow = lane >> 1, scol = 16 * (lane & 1);
-    // (the loads are unconditional - a row past the end reads row 0 and is zeroed by the sign when it is staged: with the
-    //  zeroing at the load the compiler waited for the prefetched values right behind their request)
-    auto load_block = [&](int row0, int col0, double2 (&v)[8]) {   // rows row0 .. + 31, columns col0 .. + 31 of the factor
-        const double *src = Tl + (size_t)(row0 + srow < F ? row0 + srow : 0) * F + col0 + scol;
-#pragma unroll
-        for (int q = 0; q < 8; q++) v[q] = *reinterpret_cast<const double2 *>(src + 2 * q);
-    };
-    auto store_block = [&](double *P, const double2 (&v)[8], double sign, int row0) {
-        const double sg = row0 + srow < F ? sign : 0.0;
-#pragma unroll
-        for (int q = 0; q < 8; q++)
-            *reinterpret_cast<double2 *>(P + srow * CHM_S + scol + 2 * q) = make_double2(sg * v[q].x, sg * v[q].y);
-    };
 
     for (int j = 0; j < nblk; j++) {
         const int kb = 32 * j;
         const int nb = min(CH_NB, F - kb);
         // ---- A. the tiles (i >= j, j) of the block column: input block minus the products of the factor blocks to the left.
-        //         Tile (a, b), register r of the accumulators <-> row i0 + 16 a + kq + 4 r, column kb + 16 b + ri.
         if (TALL) {
             const int ntile = (nblk - j + 1) / 2;          // tiles of two block rows: (j, j+1), (j+2, j+3), ...
             const int nround = (ntile + 3) / 4;
@@ -294,23 +432,14 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
                 const int t = wave + 4 * u;
                 const bool has = t < ntile;
                 const int i0 = 32 * (j + 2 * t);           // first row of the tile
-                d4_t acc[4][2];
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int b = 0; b < 2; b++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int row = i0 + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
-                            double v = 0.0;
-                            if (has && row < F && col <= row) v = A[(size_t)row * F + col] + (row == col ? jit : 0.0);
-                            acc[a][b][r] = v;
-                        }
+                d4_t acc[2][2][2];                         // [block row of the tile][a][b]
+                w.tile_init(acc[0], i0, kb, has);
+                w.tile_init(acc[1], i0 + 32, kb, has);
                 if (j > 0) {
                     double2 va0[8], va1[8], vb[2];
                     if (has) {
-                        load_block(i0, 0, va0);
-                        load_block(i0 + 32, 0, va1);
+                        w.load_block(i0, 0, va0);
+                        w.load_block(i0 + 32, 0, va1);
                     }
                     load_bq(0, vb);
                     for (int k = 0; k < j; k++) {
@@ -321,38 +450,12 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
                         if (has) {
                             // rows 0..31 of the tile through the wave-private A buffer, then rows 32..63 through the same
                             // buffer (one wave, LDS in order: the reads of a half complete before the next half's writes)
-                            store_block(PA, va0, -1.0, i0);
-                            if (k + 1 < j) load_block(i0, 32 * (k + 1), va0);
-#pragma unroll
-                            for (int s = 0; s < 8; s++) {
-                                double af[2], bf[2];
-#pragma unroll
-                                for (int a = 0; a < 2; a++) {
-                                    af[a] = PA[(16 * a + ri) * CHM_S + 4 * s + kq];
-                                    bf[a] = PBc[(16 * a + ri) * CHM_S + 4 * s + kq];
-                                }
-#pragma unroll
-                                for (int a = 0; a < 2; a++)
-#pragma unroll
-                                    for (int b = 0; b < 2; b++)
-                                        acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
-                            }
-                            store_block(PA, va1, -1.0, i0 + 32);
-                            if (k + 1 < j) load_block(i0 + 32, 32 * (k + 1), va1);
-#pragma unroll
-                            for (int s = 0; s < 8; s++) {
-                                double af[2], bf[2];
-#pragma unroll
-                                for (int a = 0; a < 2; a++) {
-                                    af[a] = PA[(16 * a + ri) * CHM_S + 4 * s + kq];
-                                    bf[a] = PBc[(16 * a + ri) * CHM_S + 4 * s + kq];
-                                }
-#pragma unroll
-                                for (int a = 0; a < 2; a++)
-#pragma unroll
-                                    for (int b = 0; b < 2; b++)
-                                        acc[2 + a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[2 + a][b], 0, 0, 0);
-                            }
+                            w.store_block(PA, va0, -1.0, i0);
+                            if (k + 1 < j) w.load_block(i0, 32 * (k + 1), va0);
+                            w.tile_mma(acc[0], PA, PBc);
+                            w.store_block(PA, va1, -1.0, i0 + 32);
+                            if (k + 1 < j) w.load_block(i0 + 32, 32 * (k + 1), va1);
+                            w.tile_mma(acc[1], PA, PBc);
                         }
                     }
                     __syncthreads();         // the last step's reads of the shared buffers, before the next round refills them
@@ -362,31 +465,8 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
                     for (int hb = 0; hb < 2; hb++) {       // the two block rows of the tile
                         const int r0b = i0 + 32 * hb;
                         if (r0b >= F) continue;
-                        if (t == 0 && hb == 0) {            // the diagonal block goes to LDS
-#pragma unroll
-                            for (int a = 0; a < 2; a++)
-#pragma unroll
-                                for (int b = 0; b < 2; b++)
-#pragma unroll
-                                    for (int r = 0; r < 4; r++)
-                                        D[(16 * a + kq + 4 * r) * (CH_NB + 1) + 16 * b + ri] = acc[a][b][r];
-                        } else {                            // stored for the solve; its mirror block of the upper triangle zeroed
-#pragma unroll
-                            for (int a = 0; a < 2; a++)
-#pragma unroll
-                                for (int b = 0; b < 2; b++)
-#pragma unroll
-                                    for (int r = 0; r < 4; r++) {
-                                        const int row = r0b + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
-                                        if (row < F && col < F) Tl[(size_t)row * F + col] = acc[2 * hb + a][b][r];
-                                    }
-                            if (kb + srow < F) {
-                                double *z = Tl + (size_t)(kb + srow) * F + r0b + scol;
-#pragma unroll
-                                for (int q = 0; q < 8; q++)
-                                    if (r0b + scol + 2 * q < F) *reinterpret_cast<double2 *>(z + 2 * q) = make_double2(0.0, 0.0);
-                            }
-                        }
+                        if (t == 0 && hb == 0) w.tile_to_lds(acc[hb], D);     // the diagonal block
+                        else w.tile_store(acc[hb], r0b, kb);
                     }
                 }
             }
@@ -394,105 +474,36 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
         for (int i = j + wave; i < nblk; i += 4) {
             const int i0 = 32 * i;
             d4_t acc[2][2];
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int row = i0 + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
-                        double v = 0.0;
-                        if (row < F && col <= row) v = A[(size_t)row * F + col] + (row == col ? jit : 0.0);
-                        acc[a][b][r] = v;
-                    }
+            w.tile_init(acc, i0, kb);
             if (j > 0) {
                 double2 va[8], vb[8];
-                load_block(i0, 0, va);
-                load_block(kb, 0, vb);
+                w.load_block(i0, 0, va);
+                w.load_block(kb, 0, vb);
                 for (int k = 0; k < j; k++) {
-                    store_block(PA, va, -1.0, i0);
-                    store_block(PB, vb, 1.0, kb);
+                    w.store_block(PA, va, -1.0, i0);
+                    w.store_block(PB, vb, 1.0, kb);
                     if (k + 1 < j) {          // the next k-step's blocks, in flight during the MFMAs below
-                        load_block(i0, 32 * (k + 1), va);
-                        load_block(kb, 32 * (k + 1), vb);
+                        w.load_block(i0, 32 * (k + 1), va);
+                        w.load_block(kb, 32 * (k + 1), vb);
                     }
                     // (wave-private LDS: the ds_writes above complete before the reads below, and these before the next
                     //  k-step's writes - one wave, in order.  Requesting the blocks TWO k-steps ahead - two register sets,
                     //  248 VGPRs - was measured: 14.6 / 7.36 / 1.73 against 14.4 / 7.32 / 1.70 ms, nothing)
-#pragma unroll
-                    for (int s = 0; s < 8; s++) {
-                        double af[2], bf[2];
-#pragma unroll
-                        for (int a = 0; a < 2; a++) {
-                            af[a] = PA[(16 * a + ri) * CHM_S + 4 * s + kq];
-                            bf[a] = PB[(16 * a + ri) * CHM_S + 4 * s + kq];
-                        }
-#pragma unroll
-                        for (int a = 0; a < 2; a++)
-#pragma unroll
-                            for (int b = 0; b < 2; b++)
-                                acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
-                    }
+                    w.tile_mma(acc, PA, PB);
                 }
             }
-            if (i == j) {      // (wave 0) the diagonal tile goes to LDS
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int b = 0; b < 2; b++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) D[(16 * a + kq + 4 * r) * (CH_NB + 1) + 16 * b + ri] = acc[a][b][r];
-            } else {           // an off-diagonal tile is stored for the solve; its mirror tile of the upper triangle is zeroed
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int b = 0; b < 2; b++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int row = i0 + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
-                            if (row < F && col < F) Tl[(size_t)row * F + col] = acc[a][b][r];
-                        }
-                if (kb + srow < F) {
-                    double *z = Tl + (size_t)(kb + srow) * F + i0 + scol;
-#pragma unroll
-                    for (int q = 0; q < 8; q++)
-                        if (i0 + scol + 2 * q < F) *reinterpret_cast<double2 *>(z + 2 * q) = make_double2(0.0, 0.0);
-                }
-            }
+            if (i == j) w.tile_to_lds(acc, D);      // (wave 0) the diagonal tile
+            else w.tile_store(acc, i0, kb);
         }
         CSTAMP(0);           // A: tile initialisation, update loop, tile stores
         __syncthreads();
         CSTAMP(1);           // barrier behind A
         // ---- B. factor the diagonal block with ONE wave, row i of the block in the registers of lane i
         if (tid < 64) {
-            auto bcast = [](double v, int src) {
-                const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-                const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-                return __hiloint2double(hi, lo);
-            };
             double row[CH_NB];
 #pragma unroll
             for (int k = 0; k < CH_NB; k++) row[k] = (lane < nb && k <= lane) ? D[lane * (CH_NB + 1) + k] : 0.0;
-            bool bad = false;
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj++) {
-                if (jj < nb && !bad) {
-                    const double d = bcast(row[jj], jj);
-                    if (!(d > 0.0)) {  // also catches NaN: LAPACK potrf "not positive definite"
-                        bad = true;
-                    } else {
-                        double y = __builtin_amdgcn_rsq(d);
-                        const double hd = 0.5 * d;
-                        y = fma(y, fma(-hd * y, y, 0.5), y);
-                        y = fma(y, fma(-hd * y, y, 0.5), y);       // 1 / sqrt(d)
-                        const double lij = row[jj] * y;            // lane jj: sqrt(d); lanes above jj: unused garbage
-                        row[jj] = lij;
-                        if (lane == jj) rdiag[jj] = y;
-#pragma unroll
-                        for (int k = jj + 1; k < CH_NB; k++) row[k] = fma(-lij, bcast(lij, k), row[k]);
-                    }
-                }
-            }
+            const bool bad = diag_factor_rows(row, nb, lane, [&](int jj, double y) { rdiag[jj] = y; });
 #pragma unroll
             for (int k = 0; k < CH_NB; k++)
                 if (lane < nb && k <= lane) D[lane * (CH_NB + 1) + k] = row[k];
@@ -506,34 +517,8 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
             const int i = q / nb, jj = q % nb;
             Tl[(size_t)(kb + i) * F + kb + jj] = (jj <= i) ? D[i * (CH_NB + 1) + jj] : 0.0;
         }
-        const int r0 = kb + nb;
-        // ---- C. the tiles below: X = S L_jj^{-T}, one row per thread, in place (nb == 32 whenever there are rows below)
-        for (int r = r0 + tid; r < F; r += 256) {
-            double x[CH_NB];
-            double *row = Tl + (size_t)r * F + kb;
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj += 2) {
-                const double2 v = *reinterpret_cast<const double2 *>(row + jj);
-                x[jj] = v.x;
-                x[jj + 1] = v.y;
-            }
-            // (the run-time test on nb keeps the 528 reads of D inside the row loop: without it they are hoisted in
-            //  front of it as loop invariants - into 1000 registers, i.e. scratch)
-            // four partial sums per dot product: the 496 multiply-adds of a row are otherwise ONE dependent chain (8 cycles
-            // per link, nothing to overlap it with at one or two waves per SIMD)
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj++) {
-                if (jj < nb) {
-                    double s[4] = {x[jj], 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int p = 0; p < CH_NB; p++)
-                        if (p < jj) s[p & 3] = fma(-x[p], D[jj * (CH_NB + 1) + p], s[p & 3]);
-                    x[jj] = ((s[0] + s[1]) + (s[2] + s[3])) * rdiag[jj];
-                }
-            }
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj += 2) *reinterpret_cast<double2 *>(row + jj) = make_double2(x[jj], x[jj + 1]);
-        }
+        // ---- C. the tiles below: X = S L_jj^{-T}, one row per thread, in place
+        for (int r = kb + nb + tid; r < F; r += 256) panel_solve_row(Tl + (size_t)r * F + kb, D, rdiag, nb);
         CSTAMP(4);           // C: diagonal block store + panel solve
         __syncthreads();  // the block column is final and visible to the whole workgroup (same CU, write-through L1)
         CSTAMP(5);           // barrier behind C
@@ -555,7 +540,8 @@ chol_ll_kernel(const double *__restrict__ C, int F, double jitter_rel, double *_
 // the diagonal tile is factored by the first wave and published through the output matrix, the rows of the panel
 // solve are dealt over all threads; two device-scope barriers per block column (arrival counter in global memory, one
 // spinning thread per workgroup - the grid is at most one workgroup per CU and is launched behind the batch kernel on
-// the same stream, so its workgroups are co-resident).  Same arithmetic per tile as the 32 x 32 form of chol_ll_kernel.
+// the same stream, so its workgroups are co-resident).  Same arithmetic per tile as the 32 x 32 form of chol_ll_kernel:
+// the same step functions, in the same order.
 // ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
 chol_coop_kernel(const double *__restrict__ C, int F, double jitter_rel, double *T, int32_t *__restrict__ info, int mat0, int nrem,
@@ -567,7 +553,6 @@ chol_coop_kernel(const double *__restrict__ C, int F, double jitter_rel, double 
     double *stage = rdiag + CH_NB;                     // per wave: A block [32][CHM_S], B block [32][CHM_S]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ri = lane & 15, kq = lane >> 4;
     // The G workgroups of a matrix are blocks with equal blockIdx % 8: under the round-robin dispatch of workgroups over
     // the eight XCDs they share ONE L2, and a barrier between them needs no L2 write-back / invalidate (an agent-scope
     // fence does both on gfx942 / gfx950 - the L2s of different XCDs are not coherent for ordinary device memory).
@@ -582,16 +567,7 @@ chol_coop_kernel(const double *__restrict__ C, int F, double jitter_rel, double 
     double *Tl = T + off;
     double *PA = stage + (size_t)wave * 2 * 32 * CHM_S, *PB = PA + 32 * CHM_S;
 
-    double dmax = -INFINITY;
-    for (int i = tid; i < F; i += 256) dmax = fmax(dmax, A[(size_t)i * F + i]);
-    red[tid] = dmax;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double jit = red[0] * jitter_rel;
-    __syncthreads();
+    const ll_wave w(A, Tl, F, diag_jitter<256>(A, F, jitter_rel, red), lane);
 
     unsigned nsync = 0;
     bool same_xcc = false;
@@ -645,18 +621,6 @@ chol_coop_kernel(const double *__restrict__ C, int F, double jitter_rel, double 
     }
 
     const int nblk = (F + 31) / 32;
-    const int srow = lane >> 1, scol = 16 * (lane & 1);
-    auto load_block = [&](int row0, int col0, double2 (&v)[8]) {
-        const double *src = Tl + (size_t)(row0 + srow < F ? row0 + srow : 0) * F + col0 + scol;
-#pragma unroll
-        for (int q = 0; q < 8; q++) v[q] = *reinterpret_cast<const double2 *>(src + 2 * q);
-    };
-    auto store_block = [&](double *P, const double2 (&v)[8], double sign, int row0) {
-        const double sg = row0 + srow < F ? sign : 0.0;
-#pragma unroll
-        for (int q = 0; q < 8; q++)
-            *reinterpret_cast<double2 *>(P + srow * CHM_S + scol + 2 * q) = make_double2(sg * v[q].x, sg * v[q].y);
-    };
     int failed = 0;
     for (int j = 0; j < nblk; j++) {
         const int kb = 32 * j;
@@ -665,99 +629,32 @@ chol_coop_kernel(const double *__restrict__ C, int F, double jitter_rel, double 
         for (int i = j + gw; i < nblk; i += NW) {
             const int i0 = 32 * i;
             d4_t acc[2][2];
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int row = i0 + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
-                        double v = 0.0;
-                        if (row < F && col <= row) v = A[(size_t)row * F + col] + (row == col ? jit : 0.0);
-                        acc[a][b][r] = v;
-                    }
+            w.tile_init(acc, i0, kb);
             if (j > 0) {
                 double2 va[8], vb[8];
-                load_block(i0, 0, va);
-                load_block(kb, 0, vb);
+                w.load_block(i0, 0, va);
+                w.load_block(kb, 0, vb);
                 for (int k = 0; k < j; k++) {
-                    store_block(PA, va, -1.0, i0);
-                    store_block(PB, vb, 1.0, kb);
+                    w.store_block(PA, va, -1.0, i0);
+                    w.store_block(PB, vb, 1.0, kb);
                     if (k + 1 < j) {
-                        load_block(i0, 32 * (k + 1), va);
-                        load_block(kb, 32 * (k + 1), vb);
+                        w.load_block(i0, 32 * (k + 1), va);
+                        w.load_block(kb, 32 * (k + 1), vb);
                     }
-#pragma unroll
-                    for (int s = 0; s < 8; s++) {
-                        double af[2], bf[2];
-#pragma unroll
-                        for (int a = 0; a < 2; a++) {
-                            af[a] = PA[(16 * a + ri) * CHM_S + 4 * s + kq];
-                            bf[a] = PB[(16 * a + ri) * CHM_S + 4 * s + kq];
-                        }
-#pragma unroll
-                        for (int a = 0; a < 2; a++)
-#pragma unroll
-                            for (int b = 0; b < 2; b++)
-                                acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[a], bf[b], acc[a][b], 0, 0, 0);
-                    }
+                    w.tile_mma(acc, PA, PB);
                 }
             }
-            if (i == j) {      // (first wave of the group) the diagonal tile goes to LDS
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int b = 0; b < 2; b++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) D[(16 * a + kq + 4 * r) * (CH_NB + 1) + 16 * b + ri] = acc[a][b][r];
-            } else {           // stored for the solve; its mirror tile of the upper triangle is zeroed
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int b = 0; b < 2; b++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int row = i0 + 16 * a + kq + 4 * r, col = kb + 16 * b + ri;
-                            if (row < F && col < F) Tl[(size_t)row * F + col] = acc[a][b][r];
-                        }
-                if (kb + srow < F) {
-                    double *z = Tl + (size_t)(kb + srow) * F + i0 + scol;
-#pragma unroll
-                    for (int q = 0; q < 8; q++)
-                        if (i0 + scol + 2 * q < F) *reinterpret_cast<double2 *>(z + 2 * q) = make_double2(0.0, 0.0);
-                }
-            }
+            if (i == j) w.tile_to_lds(acc, D);      // (first wave of the group) the diagonal tile
+            else w.tile_store(acc, i0, kb);
         }
         // ---- B. the first wave factors the diagonal block (row i in the registers of lane i) and publishes it
         if (gw == 0) {
-            auto bcast = [](double v, int src) {
-                const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-                const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-                return __hiloint2double(hi, lo);
-            };
             double row[CH_NB];
 #pragma unroll
             for (int k = 0; k < CH_NB; k++) row[k] = (lane < nb && k <= lane) ? D[lane * (CH_NB + 1) + k] : 0.0;
-            bool bad = false;
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj++) {
-                if (jj < nb && !bad) {
-                    const double d = bcast(row[jj], jj);
-                    if (!(d > 0.0)) {
-                        bad = true;
-                    } else {
-                        double y = __builtin_amdgcn_rsq(d);
-                        const double hd = 0.5 * d;
-                        y = fma(y, fma(-hd * y, y, 0.5), y);
-                        y = fma(y, fma(-hd * y, y, 0.5), y);
-                        const double lij = row[jj] * y;
-                        row[jj] = lij;
-                        if (lane == jj) __hip_atomic_store(&rd[mi * CH_NB + jj], y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                        for (int k = jj + 1; k < CH_NB; k++) row[k] = fma(-lij, bcast(lij, k), row[k]);
-                    }
-                }
-            }
+            const bool bad = diag_factor_rows(row, nb, lane, [&](int jj, double y) {
+                __hip_atomic_store(&rd[mi * CH_NB + jj], y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            });
             if (lane < nb) {
                 double *o = Tl + (size_t)(kb + lane) * F + kb;
 #pragma unroll
@@ -776,28 +673,7 @@ chol_coop_kernel(const double *__restrict__ C, int F, double jitter_rel, double 
         }
         if (tid < CH_NB) rdiag[tid] = tid < nb ? __hip_atomic_load(&rd[mi * CH_NB + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
         __syncthreads();
-        for (int r = kb + nb + wgl * 256 + tid; r < F; r += 256 * G) {
-            double x[CH_NB];
-            double *row = Tl + (size_t)r * F + kb;
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj += 2) {
-                const double2 v = *reinterpret_cast<const double2 *>(row + jj);
-                x[jj] = v.x;
-                x[jj + 1] = v.y;
-            }
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj++) {
-                if (jj < nb) {
-                    double s[4] = {x[jj], 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int p = 0; p < CH_NB; p++)
-                        if (p < jj) s[p & 3] = fma(-x[p], D[jj * (CH_NB + 1) + p], s[p & 3]);
-                    x[jj] = ((s[0] + s[1]) + (s[2] + s[3])) * rdiag[jj];
-                }
-            }
-#pragma unroll
-            for (int jj = 0; jj < CH_NB; jj += 2) *reinterpret_cast<double2 *>(row + jj) = make_double2(x[jj], x[jj + 1]);
-        }
+        for (int r = kb + nb + wgl * 256 + tid; r < F; r += 256 * G) panel_solve_row(Tl + (size_t)r * F + kb, D, rdiag, nb);
         group_sync();       // the block column is final for every workgroup of the group
     }
     if (wgl == 0 && tid == 0) {
@@ -829,16 +705,7 @@ jacobi_root_kernel(const double *__restrict__ C, const int32_t *__restrict__ lis
     double *V = Vall + (size_t)blockIdx.x * F * F;
     double *Tl = T + (size_t)l * F * F;
 
-    double dmax = -INFINITY;
-    for (int i = tid; i < F; i += JAC_NT) dmax = fmax(dmax, A[(size_t)i * F + i]);
-    red[tid] = dmax;
-    __syncthreads();
-    for (int s = JAC_NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    const double jit = red[0] * jitter_rel;
-    __syncthreads();
+    const double jit = diag_jitter<JAC_NT>(A, F, jitter_rel, red);
     // symmetrised working copy (use the lower triangle, like LAPACK's default uplo='L')
     for (long q = tid; q < (long)F * F; q += JAC_NT) {
         const int i = (int)(q / F), j = (int)(q % F);
@@ -852,14 +719,7 @@ jacobi_root_kernel(const double *__restrict__ C, const int32_t *__restrict__ lis
     __syncthreads();
     double emax = -INFINITY;
     for (int i = tid; i < F; i += JAC_NT) emax = fmax(emax, ev[i]);
-    red[tid] = emax;
-    __syncthreads();
-    for (int s = JAC_NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
-        __syncthreads();
-    }
-    emax = red[0];
-    __syncthreads();
+    emax = block_reduce<JAC_NT>(emax, red, [](double a, double b) { return fmax(a, b); });
     // rank of each eigenvalue (stable) -> output column
     jacobi_rank(ev, order, F);
     __syncthreads();
@@ -871,6 +731,15 @@ jacobi_root_kernel(const double *__restrict__ C, const int32_t *__restrict__ lis
     }
 }
 
+// device memory that is freed on every way out of the function that allocated it
+struct dev_mem {
+    void *p = nullptr;
+    dev_mem() = default;
+    dev_mem(const dev_mem &) = delete;
+    dev_mem &operator=(const dev_mem &) = delete;
+    ~dev_mem() { (void)hipFree(p); }
+};
+
 extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl, int F, double jitter_rel,
                                       double eig_thresh, double *T, int32_t *info) {
     ARG_CHECK(ctx != nullptr && C != nullptr && T != nullptr && info != nullptr);
@@ -878,7 +747,7 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
     StageTimer t(ctx, "factor");
     if (F >= 64 && (F % 2) == 0) {
         const bool tall = F >= 384;   // tall tiles + shared L_jk (see chol_ll_kernel)
-        const size_t shm = sizeof(double) * (CH_NB * (CH_NB + 1) + 256 + 2 + CH_NB + (tall ? 6 : 8) * 32 * CHM_S) + 16;
+        const size_t shm = ll_lds_bytes(tall);
         // The last nl mod (2 x CUs) matrices of a tall batch, if they are few, go to the cooperative kernel behind the batch:
         // a straggler round of the one-workgroup form costs a whole single-matrix latency (4.4 ms at F = 1024) for them.
         // CORAHIP_K2_COOP=0 switches it off (A/B).
@@ -895,7 +764,7 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
             if (nl > slots && r > 0 && ((r + 7) / 8) * 8 * G <= ctx->num_cu && r <= 16) nrem = r;
             if (coop_env && atoi(coop_env) == 2 && ((nl + 7) / 8) * 8 * G <= ctx->num_cu) nrem = nl;     // (tests: every matrix through the cooperative kernel)
         }
-        const size_t shm2 = sizeof(double) * (CH_NB * (CH_NB + 1) + 256 + 2 + CH_NB + 8 * 32 * CHM_S) + 16;
+        const size_t shm2 = ll_lds_bytes(false);           // the cooperative kernel stages per wave
         if (nrem > 0) {
             // the cooperative grid spins on barriers between its workgroups: it must be co-resident.  The occupancy
             // calculation covers this kernel's own resources (what else holds CUs at launch time it cannot know: the
@@ -954,8 +823,7 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
         bool redo = false;
         for (int l = 0; l < nl; l++)
             if (hinfo[l] == 3) {
-                const size_t shm = sizeof(double) * (CH_NB * (CH_NB + 1) + 256 + 2 + CH_NB + 6 * 32 * CHM_S) + 16;
-                chol_ll_kernel<true><<<1, 256, shm, ctx->stream>>>(C + (size_t)l * F * F, F, jitter_rel, T + (size_t)l * F * F, info + l);
+                chol_ll_kernel<true><<<1, 256, ll_lds_bytes(true), ctx->stream>>>(C + (size_t)l * F * F, F, jitter_rel, T + (size_t)l * F * F, info + l);
                 LAUNCH_CHECK();
                 redo = true;
             }
@@ -971,10 +839,11 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
     // process in batches bounded by scratch size (2 F^2 doubles per matrix)
     const size_t per = (size_t)2 * F * F * sizeof(double);
     const size_t batch = std::max<size_t>(1, std::min<size_t>(list.size(), ((size_t)1 << 31) / per));
-    int32_t *dlist = nullptr;
-    double *scratch = nullptr;
-    HIP_TRY(hipMalloc((void **)&dlist, sizeof(int32_t) * list.size()));
-    HIP_TRY(hipMalloc((void **)&scratch, per * batch));
+    dev_mem dlist_mem, scratch_mem;       // (freed behind the last kernel, or on an error return)
+    HIP_TRY(hipMalloc(&dlist_mem.p, sizeof(int32_t) * list.size()));
+    HIP_TRY(hipMalloc(&scratch_mem.p, per * batch));
+    int32_t *dlist = static_cast<int32_t *>(dlist_mem.p);
+    double *scratch = static_cast<double *>(scratch_mem.p);
     HIP_TRY(hipMemcpyAsync(dlist, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));
     const size_t shm = sizeof(double) * (2 * (F / 2 + 1) + JAC_NT + F) + sizeof(int) * (F + 4) + 16;
     for (size_t b0 = 0; b0 < list.size(); b0 += batch) {
@@ -984,7 +853,5 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
         LAUNCH_CHECK();
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(dlist);
-    (void)hipFree(scratch);
     return 0;
 }

@@ -37,22 +37,9 @@ __device__ __forceinline__ void jacobi_sweeps(double *W, double *V, int F, doubl
             if (i == j) dia += v * v;
             else offs += v * v;
         }
-        red[tid] = offs;
-        __syncthreads();
-        for (int s = JAC_NT / 2; s > 0; s >>= 1) {
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
-        offs = red[0];
-        __syncthreads();
-        red[tid] = dia;
-        __syncthreads();
-        for (int s = JAC_NT / 2; s > 0; s >>= 1) {
-            if (tid < s) red[tid] += red[tid + s];
-            __syncthreads();
-        }
-        dia = red[0];
-        __syncthreads();
+        const auto plus = [](double a, double b) { return a + b; };
+        offs = block_reduce<JAC_NT>(offs, red, plus);
+        dia = block_reduce<JAC_NT>(dia, red, plus);
         if (offs <= 1e-30 * dia || offs == 0.0) break;
         // A rotation lowers the off-diagonal norm by 2 a_pq^2 in exact arithmetic, so a sweep that did not lower it has
         // reached rounding.  That floor is ~F u |W|: from F ~ 100 on it can lie ABOVE the relative rule of the line before,

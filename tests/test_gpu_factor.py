@@ -111,6 +111,25 @@ def test_backward_error_on_every_path(ctx, monkeypatch, F, nl, coop):
     print("worst bound ratio path=%s F=%d nl=%d: %.4f" % (_path(F, coop), F, nl, worst))
 
 
+# ---------------------------------------------------------------------------------------- cooperative = batch, bit for bit
+@pytest.mark.parametrize("nl", (1, 9))
+@pytest.mark.parametrize("F", F_COOP)
+def test_cooperative_equals_batch_bits(ctx, monkeypatch, F, nl):
+    """chol_coop_kernel states "same arithmetic per tile" as the batch kernel: the same batch (for nl = 9 with a planted
+    +2^-20 pivot in matrix 4) through chol_ll_kernel<true> (CORAHIP_K2_COOP unset; nl is far below 2 x CUs, so no
+    matrix is a straggler) and through the cooperative kernel gives the same bits of T, and info = 0 in both."""
+    C = fo.wishart(F, 5000 + F, nl)
+    if nl == 9:
+        C[4] = fo.planted(F, F // 2, +fo.DELTA, 1000 + F)[0]
+    _set_coop(ctx, monkeypatch, False, nl, F)
+    Tb, ib = _factor(ctx, C, 1e-14)
+    _set_coop(ctx, monkeypatch, True, nl, F)
+    Tc, ic = _factor(ctx, C, 1e-14)
+    assert np.array_equal(ib, np.zeros(nl, dtype=np.int32)), (F, nl, ib)
+    assert np.array_equal(ic, np.zeros(nl, dtype=np.int32)), (F, nl, ic)
+    assert np.array_equal(Tc, Tb), (F, nl, np.abs(Tc - Tb).max())
+
+
 # ---------------------------------------------------------------------------------------- jitter semantics
 @pytest.mark.parametrize("F,imax", [(33, 0), (33, 32), (130, 0), (130, 129), (400, 0), (400, 399), (400, 300)])
 def test_jitter_is_quarter_of_max_diagonal(ctx, monkeypatch, F, imax):
