@@ -95,6 +95,9 @@ SIGNATURES = {
     "corahip_dct1_workspace_bytes": (c_int, [ctypes.c_long, c_int, ctypes.POINTER(c_size_t)]),
     "corahip_dct1_rows": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, c_double, c_void_p, c_size_t]),
     "corahip_legendre_project": (c_int, [c_void_p, PTR, PTR, c_int, c_int, PTR, ctypes.c_long, PTR]),
+    "corahip_xi_multi_average": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, c_int, c_double,
+                                         ctypes.POINTER(c_double), PTR, c_int, PTR, PTR, c_int, c_int, c_int, PTR]),
+    "corahip_cl_blocks": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, c_int, PTR]),
     "corahip_fft_c2c": (c_int, [c_void_p, PTR, c_int, PTR, c_int, c_int]),
     "corahip_irfftn": (c_int, [c_void_p, PTR, c_int, PTR, c_int, PTR]),
     "corahip_rfftn": (c_int, [c_void_p, PTR, c_int, PTR, c_int, PTR]),
@@ -1264,6 +1267,49 @@ class Context:
             raise ValueError("Given output array is incompatible.")
         _check(self.lib.corahip_legendre_project(self.h, self._f64(mu), self._f64(wt), nm, lmax, self._f64(xi),
                                                  ncol, self._f64(out)))
+        return out
+
+    XI_MULTI_MAX = 4             # tables one ``xi_multi_average`` call takes
+
+    def xi_multi_average(self, kx, ky, ky2, kind, x_t, f_t, mu, xa, xw, F, xint, nm_rows=None, out=None):
+        """``corahip_xi_multi_average``: ``ky``, ``ky2`` [nfun, nk] on the knots ``kx`` [nk], ``f_t`` a host sequence
+        [nfun] -> packed ``out`` [nm_rows, nfun, F (F + 1) / 2] (rows from ``mu.numel()`` on are zeros)."""
+        nm, nk = mu.numel(), kx.numel()
+        if ky.dim() != 2 or ky.shape[1] != nk or tuple(ky2.shape) != tuple(ky.shape):
+            raise ValueError("xi_multi_average: ky and ky2 must be [nfun, %d] (got %s, %s)" % (nk, tuple(ky.shape), tuple(ky2.shape)))
+        if not (kx.is_contiguous() and ky.is_contiguous() and ky2.is_contiguous()):
+            raise ValueError("xi_multi_average: kx, ky and ky2 must be contiguous")
+        nfun = int(ky.shape[0])
+        f_t = np.ascontiguousarray(f_t, dtype=np.float64).reshape(-1)
+        if f_t.size != nfun:
+            raise ValueError("xi_multi_average: %d values of f_t for %d tables" % (f_t.size, nfun))
+        nm_rows = nm if nm_rows is None else int(nm_rows)
+        npair = F * (F + 1) // 2
+        if out is None:
+            out = self.empty((max(nm_rows, 0), nfun, npair))
+        if tuple(out.shape) != (nm_rows, nfun, npair) or not out.is_contiguous():
+            raise ValueError("Given output array is incompatible.")
+        _check(self.lib.corahip_xi_multi_average(self.h, self._f64(kx), self._f64(ky), self._f64(ky2), nk, nfun, kind,
+                                                 float(x_t), f_t.ctypes.data_as(ctypes.POINTER(c_double)), self._f64(mu),
+                                                 nm, self._f64(xa), self._f64(xw), F, xint, nm_rows, self._f64(out)))
+        return out
+
+    def cl_blocks(self, packed, F, out=None):
+        """``corahip_cl_blocks``: packed [L, npair] -> [L, F, F], or packed [L, 3, npair] (delta delta, phi delta, phi phi)
+        -> the extended blocks [L, 2F, 2F] of the initial-LSS draw."""
+        npair = F * (F + 1) // 2
+        if packed.dim() not in (2, 3) or packed.shape[-1] != npair:
+            raise ValueError("cl_blocks: packed must be [L, %d] or [L, nfun, %d] (got %s)" % (npair, npair, tuple(packed.shape)))
+        if not packed.is_contiguous():
+            raise ValueError("cl_blocks: packed must be contiguous (got strides %s)" % (tuple(packed.stride()),))
+        L = int(packed.shape[0])
+        nfun = 1 if packed.dim() == 2 else int(packed.shape[1])
+        n = F if nfun == 1 else 2 * F
+        if out is None:
+            out = self.empty((L, n, n))
+        if tuple(out.shape) != (L, n, n) or not out.is_contiguous():
+            raise ValueError("Given output array is incompatible.")
+        _check(self.lib.corahip_cl_blocks(self.h, self._f64(packed), L, nfun, F, self._f64(out)))
         return out
 
     # -- P(k) -> xi(r) (csrc/pk2xi.hip) --------------------------------------------------

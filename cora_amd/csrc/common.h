@@ -35,7 +35,7 @@ struct corahip_linefft_plan {
     double2 *rtw = nullptr;    // [n/2 + 1]  e^{+2 pi i k / 2n}: (un)packing of a real transform of length 2n
 };
 
-#define CORAHIP_NSCRATCH 12
+#define CORAHIP_NSCRATCH 13
 struct corahip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;

@@ -4,6 +4,8 @@
 // projection  C_l = sum_m (w_m 4 pi / wsum) P_l(mu_m) xi_m  (corrfunc.py:387-397) for any input.
 //
 //   xi_table_kernel      [mu][i][j >= i]: radial-bin average of the spline at r(mu, x_i + a, x_j + b)
+//   xi_multi_kernel      the same for up to 4 tables on shared knots at once, [mu][table][packed i <= j], tables read from
+//                        interval records in global memory (no knot limit from LDS); cl_blocks_kernel unpacks / assembles
 //   legendre_matrix      lm[l][m] = weight_m P_l(mu_m) by the three-term recurrence (one thread per node)
 //   dgemm_nn_kernel      C[L x N] = A[L x M] B[M x N] on FP64 MFMA: gemm_nn_128 of mfma_tile.h as it is
 #include "common.h"
@@ -21,24 +23,50 @@ struct spline_lds {
     int n, nlut;
     double x0, inv_dx;
 };
+// the three expressions of one evaluation (cubicspline.pyx:126-175), on values: xi_table_kernel takes them from LDS,
+// xi_multi_kernel from the interval records it reads through the caches
+__device__ static inline double spline_below(double x0, double x1, double y0, double y1, double z1, double x) {
+    const double h = x1 - x0;
+    return ((y1 - y0) / h - h * z1 / 6.0) * (x - x0) + y0;
+}
+__device__ static inline double spline_above(double xm, double xn, double ym, double yn, double zm, double x) {
+    const double h = xn - xm;
+    return ((yn - ym) / h + h * zm / 6.0) * (x - xn) + yn;
+}
+__device__ static inline double spline_interp(double xk, double xk1, double ih, double h2o6, double yk, double yk1,
+                                              double zk, double zk1, double x) {
+    const double a = (xk1 - x) * ih, b = (x - xk) * ih;
+    return a * yk + b * yk1 + ((a * a * a - a) * zk + (b * b * b - b) * zk1) * h2o6;
+}
+// interval of xs[0] <= x < xs[n-1]: the last knot with xs[k] <= x, from the look-up cell walked both ways;
+// knot(k) = xs[k], next(k) = xs[k + 1]
+template <class Knot, class Next>
+__device__ static inline int spline_interval(Knot knot, Next next, const int *lut, int n, int nlut, double x0,
+                                             double inv_dx, double x) {
+    int g = (int)((x - x0) * inv_dx);
+    g = g < 0 ? 0 : (g >= nlut ? nlut - 1 : g);
+    int kl = lut[g];
+    while (kl > 0 && knot(kl) > x) kl--;            // (rounding of the cell index at a cell edge)
+    while (kl + 2 < n && next(kl) <= x) kl++;
+    return kl;
+}
+// lut[g]: bisection for the last knot at or before the left edge of cell g
+__device__ static inline int spline_lut_cell(const double *xs, int nk, double xl) {
+    int kl = 0, kh = nk;
+    while (kh - kl > 1) {
+        const int kn = (kh + kl) >> 1;
+        if (xs[kn] > xl) kh = kn;
+        else kl = kn;
+    }
+    return kl;
+}
 __device__ static inline double spline_eval(const spline_lds &S, double x) {
     const int n = S.n;
-    if (x < S.xs[0]) {
-        const double h = S.xs[1] - S.xs[0];
-        return ((S.ys[1] - S.ys[0]) / h - h * S.y2[1] / 6.0) * (x - S.xs[0]) + S.ys[0];
-    }
-    if (x >= S.xs[n - 1]) {
-        const double h = S.xs[n - 1] - S.xs[n - 2];
-        return ((S.ys[n - 1] - S.ys[n - 2]) / h + h * S.y2[n - 2] / 6.0) * (x - S.xs[n - 1]) + S.ys[n - 1];
-    }
-    int g = (int)((x - S.x0) * S.inv_dx);
-    g = g < 0 ? 0 : (g >= S.nlut ? S.nlut - 1 : g);
-    int kl = S.lut[g];
-    while (kl > 0 && S.xs[kl] > x) kl--;            // (rounding of the cell index at a cell edge)
-    while (kl + 2 < n && S.xs[kl + 1] <= x) kl++;
-    const double ih = S.invh[kl];
-    const double a = (S.xs[kl + 1] - x) * ih, b = (x - S.xs[kl]) * ih;
-    return a * S.ys[kl] + b * S.ys[kl + 1] + ((a * a * a - a) * S.y2[kl] + (b * b * b - b) * S.y2[kl + 1]) * S.h2o6[kl];
+    if (x < S.xs[0]) return spline_below(S.xs[0], S.xs[1], S.ys[0], S.ys[1], S.y2[1], x);
+    if (x >= S.xs[n - 1]) return spline_above(S.xs[n - 2], S.xs[n - 1], S.ys[n - 2], S.ys[n - 1], S.y2[n - 2], x);
+    const int kl = spline_interval([&](int k) { return S.xs[k]; }, [&](int k) { return S.xs[k + 1]; }, S.lut, n, S.nlut,
+                                   S.x0, S.inv_dx, x);
+    return spline_interp(S.xs[kl], S.xs[kl + 1], S.invh[kl], S.h2o6[kl], S.ys[kl], S.ys[kl + 1], S.y2[kl], S.y2[kl + 1], x);
 }
 
 // asinh(u), u >= 0: log(u + sqrt(u^2 + 1)) with the short log / sqrt of rng_dev.h (the argument is >= 1, where
@@ -85,6 +113,15 @@ __device__ static inline double fast_exp(double y) {
     return y < 0.0 ? 1.0 / E1 : E1;
 }
 
+// (i, j >= i) from the row-major index p of the packed upper triangle of an F x F matrix
+__device__ static inline void pair_decode(long p, int F, int &i, int &j) {
+    i = (int)(((2.0 * F + 1.0) - sqrt((2.0 * F + 1.0) * (2.0 * F + 1.0) - 8.0 * (double)p)) * 0.5);
+    i = max(0, min(i, F - 1));
+    while (i > 0 && (long)i * F - (long)i * (i - 1) / 2 > p) i--;
+    while ((long)(i + 1) * F - (long)(i + 1) * i / 2 <= p) i++;
+    j = i + (int)(p - ((long)i * F - (long)i * (i - 1) / 2));
+}
+
 // kind: 0 plain, 1 log-log (exp(spline(log r))), 2 sinh (f_t sinh(spline(asinh(r / x_t))))
 __global__ void __launch_bounds__(256)
 xi_table_kernel(const double *__restrict__ kx, const double *__restrict__ ky, const double *__restrict__ ky2, int nk,
@@ -111,14 +148,7 @@ xi_table_kernel(const double *__restrict__ kx, const double *__restrict__ ky, co
     const double dx = (sx[nk - 1] - sx[0]) / (double)nlut;
     S.inv_dx = 1.0 / dx;
     for (int g = threadIdx.x; g < nlut; g += blockDim.x) {
-        const double xl = S.x0 + g * dx;        // left edge of the cell: bisection for the last knot <= xl
-        int kl = 0, kh = nk;
-        while (kh - kl > 1) {
-            const int kn = (kh + kl) >> 1;
-            if (sx[kn] > xl) kh = kn;
-            else kl = kn;
-        }
-        slut[g] = kl;
+        slut[g] = spline_lut_cell(sx, nk, S.x0 + g * dx);        // left edge of the cell
     }
     __syncthreads();
     const double inv_xt = 1.0 / x_t;
@@ -126,13 +156,9 @@ xi_table_kernel(const double *__restrict__ kx, const double *__restrict__ ky, co
     const long total = (long)nm * npair;
     for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
         const int m = (int)(q / npair);
-        long p = q - (long)m * npair;
-        // (i, j >= i) from the row-major pair index
-        int i = (int)(((2.0 * F + 1.0) - sqrt((2.0 * F + 1.0) * (2.0 * F + 1.0) - 8.0 * (double)p)) * 0.5);
-        i = max(0, min(i, F - 1));
-        while (i > 0 && (long)i * F - (long)i * (i - 1) / 2 > p) i--;
-        while ((long)(i + 1) * F - (long)(i + 1) * i / 2 <= p) i++;
-        const int j = i + (int)(p - ((long)i * F - (long)i * (i - 1) / 2));
+        const long p = q - (long)m * npair;
+        int i, j;
+        pair_decode(p, F, i, j);
         const double om = 1.0 - mu[m];
         double acc = 0.0;
         for (int a = 0; a < xint; a++) {
@@ -154,6 +180,154 @@ xi_table_kernel(const double *__restrict__ kx, const double *__restrict__ ky, co
         }
         out[((size_t)m * F + i) * F + j] = acc;
         out[((size_t)m * F + j) * F + i] = acc;
+    }
+}
+
+// ---- several tables on shared knots, read through the caches (no knot limit from LDS) ----------------------------
+// One record per interval k = 0 .. nk - 2, XI_REC(nfun) doubles: xs_k, xs_{k+1}, 1/h, h^2/6, then per function
+// y_k, y_{k+1}, y''_k, y''_{k+1} (three functions: 16 doubles, one 128-byte line), so that an evaluation reads one look-up
+// cell and one record.  The end-slope branches read records 0 and nk - 2, which hold every knot value they need.
+#define XI_MULTI_MAX 4
+#define XI_REC(nfun) (4 + 4 * (nfun))
+struct xi_multi_ft {
+    double v[XI_MULTI_MAX];
+};
+
+__global__ void xi_multi_records_kernel(const double *__restrict__ kx, const double *__restrict__ ky,
+                                        const double *__restrict__ ky2, int nk, int nfun, int nlut,
+                                        double *__restrict__ rec, int *__restrict__ lut) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < nk - 1) {
+        double *R = rec + (size_t)t * XI_REC(nfun);
+        const double h = kx[t + 1] - kx[t];
+        R[0] = kx[t];
+        R[1] = kx[t + 1];
+        R[2] = 1.0 / h;
+        R[3] = (h * h) / 6.0;
+        for (int f = 0; f < nfun; f++) {
+            const size_t o = (size_t)f * nk + t;
+            R[4 + 4 * f] = ky[o];
+            R[5 + 4 * f] = ky[o + 1];
+            R[6 + 4 * f] = ky2[o];
+            R[7 + 4 * f] = ky2[o + 1];
+        }
+    }
+    if (t < nlut) {
+        const double x0 = kx[0];
+        const double dx = (kx[nk - 1] - x0) / (double)nlut;
+        lut[t] = min(spline_lut_cell(kx, nk, x0 + t * dx), nk - 2);     // (an interval index: the walk ends there anyway)
+    }
+}
+
+// out [nm_rows, NF, F (F + 1) / 2]: per (node, i, j >= i, a, b) the separation, the abscissa and the interval once, then
+// NF evaluations and output transforms; rows nm .. nm_rows - 1 are written as zeros
+template <int NF>
+__global__ void __launch_bounds__(256)
+xi_multi_kernel(const double *__restrict__ rec, const int *__restrict__ lut, int nk, int nlut, int kind, double x_t,
+                xi_multi_ft ft, const double *__restrict__ mu, int nm, int nm_rows, const double *__restrict__ xa,
+                const double *__restrict__ xw, int F, int xint, double *__restrict__ out) {
+    constexpr int RS = XI_REC(NF);
+    const double *last = rec + (size_t)(nk - 2) * RS;
+    const double xfirst = rec[0], xlast = last[1];
+    const double dx = (xlast - xfirst) / (double)nlut;
+    const double inv_dx = 1.0 / dx;
+    const double inv_xt = 1.0 / x_t;
+    const long npair = (long)F * (F + 1) / 2;
+    const long total = (long)nm_rows * npair;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+        const int m = (int)(q / npair);
+        const long p = q - (long)m * npair;
+        double *o = out + (size_t)m * NF * npair + p;
+        if (m >= nm) {
+#pragma unroll
+            for (int f = 0; f < NF; f++) o[(size_t)f * npair] = 0.0;
+            continue;
+        }
+        int i, j;
+        pair_decode(p, F, i, j);
+        const double om = 1.0 - mu[m];
+        double acc[NF];
+#pragma unroll
+        for (int f = 0; f < NF; f++) acc[f] = 0.0;
+        for (int a = 0; a < xint; a++) {
+            const double x1 = xa[i * xint + a];
+            double row[NF];
+#pragma unroll
+            for (int f = 0; f < NF; f++) row[f] = 0.0;
+            for (int b = 0; b < xint; b++) {
+                const double x2 = xa[j * xint + b];
+                const double dx12 = x1 - x2;
+                const double r = sqrt(fma(dx12, dx12, 2.0 * x1 * x2 * om));      // as xi_table_kernel
+                double x;
+                if (kind == 1) x = r > 0.0 ? fast_log01(r) : -INFINITY;
+                else if (kind == 2) x = fast_asinh_pos(r * inv_xt);
+                else x = r;
+                double s[NF];
+                if (x < xfirst) {
+#pragma unroll
+                    for (int f = 0; f < NF; f++) s[f] = spline_below(rec[0], rec[1], rec[4 + 4 * f], rec[5 + 4 * f], rec[7 + 4 * f], x);
+                } else if (x >= xlast) {
+#pragma unroll
+                    for (int f = 0; f < NF; f++) s[f] = spline_above(last[0], last[1], last[4 + 4 * f], last[5 + 4 * f], last[6 + 4 * f], x);
+                } else {
+                    const int kl = spline_interval([&](int k) { return rec[(size_t)k * RS]; },
+                                                   [&](int k) { return rec[(size_t)k * RS + 1]; }, lut, nk, nlut, xfirst,
+                                                   inv_dx, x);
+                    const double *R = rec + (size_t)kl * RS;
+                    const double xk = R[0], xk1 = R[1], ih = R[2], h2o6 = R[3];
+#pragma unroll
+                    for (int f = 0; f < NF; f++)
+                        s[f] = spline_interp(xk, xk1, ih, h2o6, R[4 + 4 * f], R[5 + 4 * f], R[6 + 4 * f], R[7 + 4 * f], x);
+                }
+#pragma unroll
+                for (int f = 0; f < NF; f++) {
+                    double v;
+                    if (kind == 1) v = fast_exp(s[f]);
+                    else if (kind == 2) v = ft.v[f] * fast_sinh(s[f]);
+                    else v = s[f];
+                    row[f] += xw[b] * v;
+                }
+            }
+#pragma unroll
+            for (int f = 0; f < NF; f++) acc[f] += xw[a] * row[f];
+        }
+#pragma unroll
+        for (int f = 0; f < NF; f++) o[(size_t)f * npair] = acc[f];
+    }
+}
+
+// packed projection output -> full blocks.  NF = 1: in [L, npair] -> out [L, F, F].  NF = 3: in [L, 3, npair] with the
+// slots (delta delta, phi delta, phi phi) -> out [L, 2F, 2F] = [[phi phi, phi delta], [phi delta, delta delta]]
+// (lss.py:441-445).  Every value goes to its mirror positions from one register.
+template <int NF>
+__global__ void cl_blocks_kernel(const double *__restrict__ in, long L, int F, double *__restrict__ out) {
+    const long npair = (long)F * (F + 1) / 2;
+    const long total = L * npair;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+        const long l = q / npair;
+        const long p = q - l * npair;
+        int ii, jj;
+        pair_decode(p, F, ii, jj);
+        const size_t i = (size_t)ii, j = (size_t)jj, Fs = (size_t)F;
+        const double *src = in + ((size_t)l * NF) * (size_t)npair + (size_t)p;
+        if (NF == 1) {
+            double *o = out + (size_t)l * Fs * Fs;
+            const double v = src[0];
+            o[i * Fs + j] = v;
+            o[j * Fs + i] = v;
+        } else {
+            const size_t N = 2 * Fs;
+            double *o = out + (size_t)l * N * N;
+            const double dd = src[0], pd = src[(size_t)npair], pp = src[2 * (size_t)npair];
+            o[i * N + j] = pp;
+            o[j * N + i] = pp;
+            o[(Fs + i) * N + Fs + j] = dd;
+            o[(Fs + j) * N + Fs + i] = dd;
+            o[i * N + Fs + j] = pd;
+            o[(Fs + j) * N + i] = pd;
+            o[j * N + Fs + i] = pd;
+            o[(Fs + i) * N + j] = pd;
+        }
     }
 }
 
@@ -192,6 +366,16 @@ static int xi_lds_bytes(corahip_ctx *ctx, int *bytes) {
     return 0;
 }
 
+// the largest table xi_multi_average takes: its look-up grid of 4 nk cells is indexed by int
+#define XI_MULTI_MAX_KNOTS (1 << 24)
+
+template <int NF>
+static void xi_multi_launch(corahip_ctx *ctx, int blocks, const double *rec, const int *lut, int nk, int nlut, int kind,
+                            double x_t, const xi_multi_ft &ft, const double *mu, int nm, int nm_rows, const double *xa,
+                            const double *xw, int F, int xint, double *out) {
+    xi_multi_kernel<NF><<<blocks, 256, 0, ctx->stream>>>(rec, lut, nk, nlut, kind, x_t, ft, mu, nm, nm_rows, xa, xw, F, xint, out);
+}
+
 extern "C" {
 
 int corahip_xi_table_max_knots(corahip_ctx *ctx, int *max_knots) {
@@ -223,6 +407,63 @@ int corahip_xi_table_average(corahip_ctx *ctx, const double *knots_x, const doub
     const int blocks = (int)std::min<long>((total + 255) / 256, (long)ctx->num_cu * 8);
     xi_table_kernel<<<blocks, 256, shm, ctx->stream>>>(knots_x, knots_y, knots_y2, nk, nlut, kind, x_t, f_t, mu, nm, xa, xw,
                                                       F, xint, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_xi_multi_average(corahip_ctx *ctx, const double *knots_x, const double *knots_y, const double *knots_y2,
+                             int nk, int nfun, int kind, double x_t, const double *f_t, const double *mu, int nm,
+                             const double *xa, const double *xw, int F, int xint, int nm_rows, double *out) {
+    ARG_CHECK(ctx != nullptr && knots_x && knots_y && knots_y2 && f_t && mu && xa && xw && out);
+    ARG_CHECK(kind >= 0 && kind <= 2 && nm >= 1 && F >= 1 && xint >= 1);
+    if (nfun < 1 || nfun > XI_MULTI_MAX) {
+        corahip_set_error("invalid argument: nfun = %d tables, xi_multi_average takes 1 to %d (%s:%d)", nfun, XI_MULTI_MAX,
+                          __FILE__, __LINE__);
+        return CORAHIP_EINVAL;
+    }
+    if (nk < 4 || nk > XI_MULTI_MAX_KNOTS) {
+        corahip_set_error("invalid argument: nk = %d knots, xi_multi_average takes 4 to %d (%s:%d)", nk, XI_MULTI_MAX_KNOTS,
+                          __FILE__, __LINE__);
+        return CORAHIP_EINVAL;
+    }
+    if (nm_rows < nm) {
+        corahip_set_error("invalid argument: nm_rows = %d output rows for nm = %d nodes (%s:%d)", nm_rows, nm, __FILE__, __LINE__);
+        return CORAHIP_EINVAL;
+    }
+    ARG_CHECK((long)F * xint <= 0x7fffffffL);
+    StageTimer t(ctx, "xi_multi_average");
+    const int nlut = 4 * nk;
+    const size_t rec_bytes = sizeof(double) * XI_REC(nfun) * (size_t)(nk - 1);
+    char *ws = nullptr;
+    int rc = corahip_ctx_scratch(ctx, 12, rec_bytes + sizeof(int) * (size_t)nlut, (void **)&ws);
+    if (rc) return rc;
+    double *rec = reinterpret_cast<double *>(ws);
+    int *lut = reinterpret_cast<int *>(ws + rec_bytes);
+    xi_multi_records_kernel<<<(nlut + 255) / 256, 256, 0, ctx->stream>>>(knots_x, knots_y, knots_y2, nk, nfun, nlut, rec, lut);
+    LAUNCH_CHECK();
+    xi_multi_ft ft;
+    for (int f = 0; f < XI_MULTI_MAX; f++) ft.v[f] = f < nfun ? f_t[f] : 0.0;
+    const long total = (long)nm_rows * ((long)F * (F + 1) / 2);
+    const int blocks = (int)std::min<long>((total + 255) / 256, (long)ctx->num_cu * 8);
+    if (nfun == 1) xi_multi_launch<1>(ctx, blocks, rec, lut, nk, nlut, kind, x_t, ft, mu, nm, nm_rows, xa, xw, F, xint, out);
+    else if (nfun == 2) xi_multi_launch<2>(ctx, blocks, rec, lut, nk, nlut, kind, x_t, ft, mu, nm, nm_rows, xa, xw, F, xint, out);
+    else if (nfun == 3) xi_multi_launch<3>(ctx, blocks, rec, lut, nk, nlut, kind, x_t, ft, mu, nm, nm_rows, xa, xw, F, xint, out);
+    else xi_multi_launch<4>(ctx, blocks, rec, lut, nk, nlut, kind, x_t, ft, mu, nm, nm_rows, xa, xw, F, xint, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_cl_blocks(corahip_ctx *ctx, const double *packed, long L, int nfun, int F, double *out) {
+    ARG_CHECK(ctx != nullptr && packed && out && L >= 1 && F >= 1);
+    if (nfun != 1 && nfun != 3) {
+        corahip_set_error("invalid argument: nfun = %d, cl_blocks unpacks 1 function or assembles 3 (%s:%d)", nfun, __FILE__, __LINE__);
+        return CORAHIP_EINVAL;
+    }
+    StageTimer t(ctx, "cl_blocks");
+    const long total = L * ((long)F * (F + 1) / 2);
+    const unsigned blocks = grid_blocks(ctx, total);
+    if (nfun == 1) cl_blocks_kernel<1><<<blocks, 256, 0, ctx->stream>>>(packed, L, F, out);
+    else cl_blocks_kernel<3><<<blocks, 256, 0, ctx->stream>>>(packed, L, F, out);
     LAUNCH_CHECK();
     return 0;
 }

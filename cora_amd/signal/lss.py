@@ -14,7 +14,10 @@ their mass shared among the 4 bilinear-interpolation pixels of the new direction
 The steps around it (csrc/lsschain.hip): ``biased_field`` (GenerateBiasedFieldBase.process, lss.py:556-603),
 ``linear_dynamics`` (LinearDynamics.process, :862-918), ``fingers_of_god`` (FingersOfGod.process, :1162-1220),
 ``biased_lss_to_map`` (BiasedLSSToMap.process, :944-993) and their composition ``tracer_map_device``: ``phi, delta``
-in, map out, on the device.  The bias, growth and temperature models of the reference are not part of this package:
+in, map out, on the device.  ``multifrequency_aps_device`` and ``generate_initial_lss_device`` are the step before it
+(CalculateMultiFrequencyAngularPowerSpectrum.process, :289-373, GenerateInitialLSSFromCl, :397-478): the three
+correlation functions of ``calculate_correlations`` to C_l(chi, chi') in one pass, the extended covariance, the draw of
+``phi, delta`` - so that P(k) -> xi -> C_l -> (phi, delta) -> tracer map is one device chain.  The bias, growth and temperature models of the reference are not part of this package:
 ``b1``, ``b2``, ``sigmaP``, ``D``, ``f``, ``T_b`` are per-slice arrays (or scalars) the caller supplies.
 
 The reference's scatter (pmesh_util.c:37, called from pmesh.pyx:_bin_delta) indexes ``out`` with a row stride of 9
@@ -425,6 +428,107 @@ def calculate_correlations(ps, minlogr=-1, maxlogr=5, switchlogr=1, samples_per_
         c = plan.run(pd * plan.kdirect**-n, pf * plan.kfine**-n).cpu().numpy()
         out["corr%d" % n] = cubicspline.SinhInterpolater(np.column_stack([plan.r, c]), x_t=plan.r[1], f_t=f_t)
     return out
+
+
+# ------------------------------------------------------------------------------------
+# xi(r) -> C_l(chi, chi') -> (phi, delta) (cora/signal/lss.py:246-478)
+# ------------------------------------------------------------------------------------
+_APS_SLOTS = ("Cl_delta_delta", "Cl_phi_delta", "Cl_phi_phi")     # function slots 0, 1, 2 of the packed spectra
+
+
+def multifrequency_aps_device(correlations, nside, redshift=None, frequencies=None, cosmology=None, xromb=2, leg_q=4):
+    """The body of ``CalculateMultiFrequencyAngularPowerSpectrum.process`` (lss.py:289-373) with the spectra left on the
+    device.
+
+    correlations : ``{"corr0", "corr2", "corr4"}`` of :func:`calculate_correlations`: the density, cross and potential
+        correlation functions, interpolaters on the same knots.
+    nside : ``lmax = 3 nside - 1``.
+    redshift, frequencies : where to evaluate (arrays); ``frequencies`` (MHz) override ``redshift`` through ``nu21``.
+        RuntimeError when neither is given.
+    cosmology : its ``comoving_distance(redshift)`` gives ``chi``; default ``cora_amd.util.cosmology.Cosmology()``.
+    xromb, leg_q : radial-bin quadrature order and Legendre accuracy parameter of ``corrfunc.corr_to_clarray``.
+
+    Returns a dict: ``ell`` [lmax+1], ``chi``, ``redshift``, ``freq`` (None unless ``frequencies`` were given) as numpy
+    arrays, ``Cl_delta_delta``, ``Cl_phi_delta``, ``Cl_phi_phi`` as device tensors [lmax+1, nz, nz], and ``cosmology``.
+    The three functions are integrated in one pass (``corrfunc.corr_to_clarray_multi_device``)."""
+    from ..util import constants
+    from . import corrfunc
+
+    if redshift is None and frequencies is None:
+        raise RuntimeError("Redshifts or frequencies must be specified!")
+    if cosmology is None:
+        from ..util.cosmology import Cosmology
+
+        cosmology = Cosmology()
+    if frequencies is None:
+        redshift = np.asarray(redshift, dtype=np.float64)
+    else:
+        frequencies = np.asarray(frequencies, dtype=np.float64)
+        redshift = constants.nu21 / frequencies - 1.0
+    xa = np.asarray(cosmology.comoving_distance(redshift), dtype=np.float64)
+    # NOTE (the reference's): it is important not to set this any higher, or power aliases back down in the synthesis
+    lmax = 3 * int(nside) - 1
+    corrs = [correlations["corr0"], correlations["corr2"], correlations["corr4"]]
+    full = corrfunc.corr_to_clarray_multi_device(corrs, lmax, xa, xromb=xromb, q=leg_q)
+    aps = {"ell": np.arange(lmax + 1), "chi": xa, "redshift": redshift, "freq": frequencies, "cosmology": cosmology}
+    for n, name in enumerate(_APS_SLOTS):
+        aps[name] = full[n]
+    return aps
+
+
+def multifrequency_aps(correlations, nside, redshift=None, frequencies=None, cosmology=None, xromb=2, leg_q=4):
+    """:func:`multifrequency_aps_device` with the three spectra as numpy arrays."""
+    aps = multifrequency_aps_device(correlations, nside, redshift, frequencies, cosmology, xromb=xromb, leg_q=leg_q)
+    ctx = _lib.get_context()
+    for name in _APS_SLOTS:
+        aps[name] = ctx.to_host(aps[name])
+    return aps
+
+
+def initial_lss_covariance_device(aps):
+    """The extended covariance of ``GenerateInitialLSSFromCl.process`` (lss.py:439-445) -> device tensor
+    [L, 2 nz, 2 nz]: phi phi at ``[:nz, :nz]``, delta delta at ``[nz:, nz:]``, phi delta at both off-diagonal blocks,
+    symmetric bit for bit (``corahip_cl_blocks``).  ``aps``: the dict of :func:`multifrequency_aps_device` or
+    :func:`multifrequency_aps`: the three spectra [L, nz, nz] as device tensors or arrays; their upper triangles
+    (i, j >= i) are what is used, as they stand at the time of the call."""
+    import torch
+
+    ctx = _lib.get_context()
+    cls = [c if isinstance(c, torch.Tensor) else ctx.to_device(c) for c in (aps[name] for name in _APS_SLOTS)]
+    L, nz = int(cls[0].shape[0]), int(cls[0].shape[1])
+    for name, c in zip(_APS_SLOTS, cls):
+        _assert_shape(c, (L, nz, nz), name)
+    iu = torch.triu_indices(nz, nz, device=ctx.device)
+    packed = torch.stack([c[:, iu[0], iu[1]] for c in cls], dim=1).contiguous()
+    return ctx.cl_blocks(packed, nz)
+
+
+def generate_initial_lss_device(aps, nside=None, seed=0, rng=None):
+    """``GenerateInitialLSSFromCl`` (lss.py:397-478): one realisation ``(phi, delta)``, device tensors [nz, npix], drawn
+    from the extended covariance of :func:`initial_lss_covariance_device` by ``skysim.mkfullsky_device``.
+
+    nside : default ``hputil.nside_for_lmax(L - 1, accuracy_boost=0)``; a larger one is a RuntimeError.
+    seed, rng : ``rng`` defaults to ``numpy.random.default_rng(seed)``; the numpy stream is continued on the device, so
+    the random numbers are the reference's."""
+    from ..core import skysim
+
+    nside_from_cl = hputil.nside_for_lmax(len(aps["ell"]) - 1, accuracy_boost=0)
+    if nside is None:
+        nside = nside_from_cl
+    elif nside > nside_from_cl:
+        raise RuntimeError(f"Requested nside ({nside}) cannot exceed nside used for input C_l ({nside_from_cl})")
+    if rng is None:
+        rng = np.random.default_rng(seed)
+    nz = len(aps["chi"])
+    sky = skysim.mkfullsky_device(initial_lss_covariance_device(aps), nside, rng=rng)
+    return sky[:nz], sky[nz:]
+
+
+def generate_initial_lss(aps, nside=None, seed=0, rng=None):
+    """:func:`generate_initial_lss_device` with ``(phi, delta)`` as numpy arrays."""
+    phi, delta = generate_initial_lss_device(aps, nside=nside, seed=seed, rng=rng)
+    ctx = _lib.get_context()
+    return ctx.to_host(phi), ctx.to_host(delta)
 
 
 def tracer_map_device(phi, delta, chi, D, f, b1, b2=None, sigmaP=None, dynamics="zeldovich", lognormal=False,

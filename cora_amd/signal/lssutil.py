@@ -1,4 +1,4 @@
-"""Counterpart of the functions of cora/signal/lssutil.py that the LSS steps use: ``gradient``
+"""Counterpart of the functions of cora/signal/lssutil.py that the LSS steps use: ``linspace`` (lssutil.py:14-51), ``gradient``
 (lssutil.py:225-261), ``assert_shape`` (lssutil.py:630-640), ``diff2`` (:99-185), ``calculate_width`` (:491-515),
 ``exponential_FoG_kernel`` (:518-589), ``lognormal_transform`` (:592-627); the last four with the kernels of
 csrc/lsschain.hip.  The angular derivatives come from the derivative
@@ -12,6 +12,27 @@ from ..util import hputil
 
 # slices that go through analysis + derivative synthesis together (a multiple of 4: whole channel groups)
 SLICE_CHUNK = 16
+
+
+def linspace(x):
+    """Counterpart of lssutil.linspace (cora/signal/lssutil.py:14-51), the parser of the ``redshift`` / ``frequencies``
+    settings: an ndarray is returned as it is; a dict with ``start``, ``stop``, ``num`` and optionally ``endpoint``, or a
+    list ``[start, stop, num]`` / ``[start, stop, num, endpoint]``, becomes ``numpy.linspace`` of those.  Any other type
+    is a TypeError (where the reference raises its configuration error)."""
+    if isinstance(x, np.ndarray):
+        return x
+    if isinstance(x, dict):
+        args = {k: x[k] for k in ("start", "stop", "num")}
+        if "endpoint" in x:
+            args["endpoint"] = x["endpoint"]
+    elif isinstance(x, list):
+        args = dict(zip(("start", "stop", "num", "endpoint"), x[:4]))
+        for k in ("start", "stop", "num"):
+            if k not in args:
+                raise IndexError("linspace needs [start, stop, num] (got %d values)" % len(x))
+    else:
+        raise TypeError("linspace takes a dict, a list or an array (got %s)" % type(x).__name__)
+    return np.linspace(**args)
 
 
 def assert_shape(arr, shape, name):

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -444,6 +444,24 @@ int corahip_xi_table_average(corahip_ctx *ctx, const double *knots_x, const doub
                              double *out);
 int corahip_legendre_project(corahip_ctx *ctx, const double *mu, const double *wt, int nm, int lmax,
                              const double *xi, long ncol, double *out);
+
+/* xi_multi_average: the radial-bin average of xi_table_average for nfun (1 to 4) tables at once that share their knots
+ *   knots_x [nk], their kind and x_t; knots_y, knots_y2 [nfun, nk] and f_t [nfun] (host memory) are per table.  The
+ *   separation, the abscissa and the interval are found once per (node, i, j >= i, a, b), then nfun splines are
+ *   evaluated with the arithmetic of xi_table_average.  The tables are read from global memory through the caches
+ *   (a prologue kernel writes one record per interval and the look-up grid into context scratch): 4 <= nk <= 2^24,
+ *   no limit from LDS.  out [nm_rows, nfun, F (F + 1) / 2]: the upper triangle (i, j >= i) row-major; nm_rows >= nm, rows
+ *   nm .. nm_rows - 1 are written as zeros (nm_rows a multiple of 16 and zero weights for those rows let
+ *   legendre_project take the buffer as its operand without a padded copy).
+ * cl_blocks: packed projection output -> full symmetric blocks, each value written to its mirror positions from one
+ *   register.  nfun = 1: packed [L, npair] -> out [L, F, F].  nfun = 3: packed [L, 3, npair] with slots (0 delta delta,
+ *   1 phi delta, 2 phi phi) -> out [L, 2F, 2F] with phi phi at [:F, :F], delta delta at [F:, F:] and phi delta at both
+ *   off-diagonal blocks (cora/signal/lss.py:441-445).  Any other nfun is CORAHIP_EINVAL. */
+int corahip_xi_multi_average(corahip_ctx *ctx, const double *knots_x, const double *knots_y,
+                             const double *knots_y2, int nk, int nfun, int kind, double x_t, const double *f_t,
+                             const double *mu, int nm, const double *xa, const double *xw, int F, int xint,
+                             int nm_rows, double *out);
+int corahip_cl_blocks(corahip_ctx *ctx, const double *packed, long L, int nfun, int F, double *out);
 
 /* ---- P(k) -> xi(r) (csrc/pk2xi.hip) --------------------------------------------------------
  * The numerical halves of corrfunc.ps_to_corr (cora/signal/corrfunc.py:72-84, 150-264).
