@@ -52,6 +52,8 @@ SIGNATURES = {
     "corahip_normals_philox": (c_int, [c_void_p, c_u64, c_int, c_int, PTR]),
     "corahip_normals_pcg64": (c_int, [c_void_p, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.c_int64, PTR,
                                       ctypes.POINTER(c_u64)]),
+    "corahip_normal_rows_pcg64": (c_int, [c_void_p, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), ctypes.c_long, ctypes.c_long,
+                                          PTR, PTR, PTR, c_int, ctypes.POINTER(c_u64)]),
     "corahip_normals_mt19937_legacy": (c_int, [c_void_p, c_void_p, ctypes.c_int64, PTR]),
     "corahip_glibc_exp": (c_int, [c_void_p, PTR, ctypes.c_int64, PTR]),
     "corahip_pcg64_advance": (c_int, [ctypes.POINTER(c_u64), ctypes.POINTER(c_u64), c_u64, ctypes.POINTER(c_u64)]),
@@ -578,6 +580,61 @@ class Context:
         nraw = c_u64(0)
         _check(self.lib.corahip_normals_pcg64(self.h, st, ic, int(n), self._f64(g), ctypes.byref(nraw)))
         return g, int(nraw.value)
+
+    @staticmethod
+    def check_rows(scale, ncol, out, row_off=None):
+        """The host-side argument checks of :meth:`normal_rows_pcg64` (no device call): ``scale`` [nrow], ``out`` a
+        contiguous float64 tensor, every row ``row_off[r] : row_off[r] + ncol`` (``row_off`` None: ``r * ncol``) inside
+        ``out`` - ValueError otherwise.  Returns ``(nrow, row_off as a host int64 array or None)``."""
+        torch = _torch()
+        if len(scale.shape) != 1:
+            raise ValueError("scale must be one value per row (got shape %s)" % (tuple(scale.shape),))
+        nrow = int(scale.shape[0])
+        if ncol < 0:
+            raise ValueError("ncol must not be negative (got %d)" % ncol)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 tensor")
+        size = int(out.numel())
+        if row_off is None:
+            if nrow * ncol > size:
+                raise ValueError("out holds %d values, %d rows of %d need %d" % (size, nrow, ncol, nrow * ncol))
+            return nrow, None
+        ro = row_off.cpu().numpy() if isinstance(row_off, torch.Tensor) else np.asarray(row_off)
+        if ro.shape != (nrow,) or ro.dtype.kind not in "iu":
+            raise ValueError("row_off must be %d integers (got shape %s, dtype %s)" % (nrow, ro.shape, ro.dtype))
+        ro = np.ascontiguousarray(ro, dtype=np.int64)
+        bad = np.flatnonzero((ro < 0) | (ro > size - ncol))
+        if len(bad):
+            raise ValueError("row_off[%d] = %d: a row of %d values from there would leave out (%d values)"
+                             % (int(bad[0]), int(ro[bad[0]]), ncol, size))
+        return nrow, ro
+
+    def normal_rows_pcg64(self, state, inc, scale, ncol, out, row_off=None, accumulate=False):
+        """numpy's ``Generator(PCG64).normal(scale=scale[:, None], size=(len(scale), ncol))`` from bit-generator
+        ``state`` / ``inc`` (python ints), written (``accumulate=False``) or added (``True``) in place on the device:
+        row ``r`` goes to ``out.view(-1)[row_off[r] : row_off[r] + ncol]`` (``row_off`` None: ``r * ncol``).  ``scale``:
+        [nrow] host array or device tensor; ``row_off``: [nrow] integers (host array or device tensor), rows must not
+        overlap; ``out``: a contiguous device float64 tensor.  Every ``row_off[r] + ncol`` is checked against ``out``
+        here, on the host (:meth:`check_rows`, ValueError) - the kernel cannot.  Returns ``n_raw``, the raw draws
+        consumed."""
+        torch = _torch()
+        ncol = int(ncol)
+        sc = scale.to(dtype=torch.float64).contiguous() if isinstance(scale, torch.Tensor) \
+            else np.ascontiguousarray(scale, dtype=np.float64)
+        nrow, ro = self.check_rows(sc, ncol, out, row_off)
+        if nrow == 0 or ncol == 0:
+            return 0
+        if not isinstance(sc, torch.Tensor):
+            sc = self.to_device(sc)
+        if ro is not None:
+            ro = self.to_device(ro, dtype=np.int64)
+        M = 2**64 - 1
+        st = (c_u64 * 2)((int(state) >> 64) & M, int(state) & M)
+        ic = (c_u64 * 2)((int(inc) >> 64) & M, int(inc) & M)
+        nraw = c_u64(0)
+        _check(self.lib.corahip_normal_rows_pcg64(self.h, st, ic, nrow, ncol, self._f64(sc), self._p0(ro), self._f64(out),
+                                                  1 if accumulate else 0, ctypes.byref(nraw)))
+        return int(nraw.value)
 
     def glibc_exp(self, x):
         """exp(x) of a device float64 tensor as the wedge test of the device ziggurat evaluates it (glibc's routine,

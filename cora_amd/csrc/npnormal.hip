@@ -886,18 +886,121 @@ zig_entry_kernel(long nblk, long ntile, const unsigned *__restrict__ fun, const 
     }
 }
 
-// pass 2: every block with its true entry; the normals with ordinals in [o_lo, o_hi) go to g[ordinal - o_lo] (the whole
-// stream: o_lo = 0, o_hi = n; one range of the l-range pipeline: its ordinals, g = the ring slot).  blk_first: device
+// Where pass 2 puts a normal: a functor called with (ordinal, value) at each of the emit kernel's store sites, after
+// block(first ordinal of the block) - wave-uniform, once per block.
+// The plain store: ordinal o goes to g[o - o_lo].
+struct sink_store {
+    double *__restrict__ g;
+    unsigned long long o_lo;
+    struct stage_t {};
+    __device__ inline void attach(stage_t *) {}
+    __device__ inline void block(unsigned long long) {}
+    __device__ inline void operator()(unsigned long long o, double v) const { g[o - o_lo] = v; }
+    __device__ inline void flush(unsigned long long) {}
+};
+// numpy's Generator.normal(0, scale[:, None], (nrow, ncol)) written or added in place: ordinal o is element (r, c) =
+// divmod(o, ncol), its value 0.0 + scale[r] z (one rounded multiply, the rounded add of 0.0 that makes scale = 0 give
+// +0.0 whatever the sign of z, and in accumulate mode one more rounded add), stored at out[row_off[r] + c] (row_off
+// NULL: r ncol + c).  The ordinals of a block are consecutive and fewer than ZIG_BLK, so the one 64-bit division is
+// that of the block's first ordinal: element d of the block is at column c0 + d of row r0 - past the end of the row at
+// most once when ncol >= ZIG_BLK, and a 32-bit division (of a value < 2 ZIG_BLK) below that, where several field rows
+// fall inside one block, or one 64-lane row.
+// The store sites only park z in a wave-private LDS stage, at the ordinal's place in the block; flush(), once per block,
+// walks the stage 64 consecutive ordinals at a time: consecutive addresses per instruction except across a field-row end,
+// and in accumulate mode eight loads of the field in flight per lane before the first add.  (Read, add and store at the
+// store sites themselves, one dependent memory round trip per wave row at four waves per SIMD, made this emit pass 2.5
+// times as long as the plain one.)
+struct sink_rows {
+    struct stage_t {
+        double z[ZIG_BLK];
+    };
+    const double *__restrict__ scale;
+    const int64_t *__restrict__ row_off;
+    double *out;
+    unsigned long long ncol;
+    int accumulate;
+    unsigned long long ord_blk, r0, c0;
+    stage_t *stage;
+    __device__ inline void attach(stage_t *s) { stage = s; }
+    __device__ inline void block(unsigned long long ob) {
+        ord_blk = ob;
+        r0 = ob / ncol;
+        c0 = ob - r0 * ncol;
+    }
+    __device__ inline void operator()(unsigned long long o, double z) const {
+        const unsigned long long d = o - ord_blk;
+        if (d < ZIG_BLK) stage->z[d] = z;
+    }
+    // element d of the block: its address in out and its row's scale
+    __device__ inline double *locate(unsigned d, double &sc) const {
+        unsigned long long r = r0, c = c0 + d;
+        if (c >= ncol) {
+            if (ncol >= ZIG_BLK) {
+                r += 1;
+                c -= ncol;
+            } else {
+                const unsigned q = (unsigned)c / (unsigned)ncol;
+                r += q;
+                c -= (unsigned long long)q * ncol;
+            }
+        }
+        sc = scale[r];
+        return out + (row_off ? (unsigned long long)row_off[r] : r * ncol) + c;
+    }
+    // ord_end: the ordinal after the block's last sample that was handed over
+    __device__ inline void flush(unsigned long long ord_end) const {
+#pragma clang fp contract(off)
+        constexpr int NB = 8;
+        const unsigned cnt = (unsigned)std::min<unsigned long long>(ord_end - ord_blk, (unsigned long long)ZIG_BLK);
+        const unsigned lane = threadIdx.x & 63;
+        wave_lds_fence();
+        for (unsigned h = 0; h < cnt; h += 64u * NB) {
+            double *p[NB];
+            double v[NB], old[NB];
+#pragma unroll
+            for (int i = 0; i < NB; i++) {
+                const unsigned d = h + 64u * i + lane;
+                p[i] = nullptr;
+                v[i] = 0.0;
+                if (d < cnt) {
+                    double sc;
+                    p[i] = locate(d, sc);
+                    v[i] = __dadd_rn(0.0, __dmul_rn(sc, stage->z[d]));
+                }
+            }
+            if (accumulate) {
+#pragma unroll
+                for (int i = 0; i < NB; i++) old[i] = p[i] ? *p[i] : 0.0;
+#pragma unroll
+                for (int i = 0; i < NB; i++)
+                    if (p[i]) *p[i] = __dadd_rn(old[i], v[i]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < NB; i++)
+                    if (p[i]) *p[i] = v[i];
+            }
+        }
+        wave_lds_fence();                                   // (the next block parks its values in the same stage)
+    }
+};
+
+// pass 2: every block with its true entry; the normals with ordinals in [o_lo, o_hi) go to the sink - sink_store: to
+// g[ordinal - o_lo] (the whole stream: o_lo = 0, o_hi = n; one range of the l-range pipeline: its ordinals, g = the ring
+// slot); sink_rows: scaled into the rows of a field.  blk_first: device
 // word holding the first block to look at - the one that contains ordinal o_lo (zig_range_kernel) -, NULL = block 0.
 // Lane p of row j holds position 64 j + p: the samples of a row leave as one store instruction to consecutive addresses.
+template <class Sink>
 __global__ void __launch_bounds__(ZIG_WG)
 zig_emit_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64_t i_lo, long nblk,
                 const ulonglong2 *__restrict__ entry, const ulonglong2 *__restrict__ classes,
                 const unsigned long long *__restrict__ tails, unsigned long long pos0, unsigned long long n,
                 unsigned long long o_lo, unsigned long long o_hi, const long *__restrict__ blk_first,
-                double *__restrict__ g, zig_status *st) {
+                const Sink sink_arg, zig_status *st) {
     __shared__ zig_lds L;
     zig_lds_fill(L);
+    __shared__ typename Sink::stage_t stages[ZIG_WG / 64];
+    Sink sink = sink_arg;                                   // (block() keeps the block's row and column in it)
+    sink.attach(&stages[threadIdx.x >> 6]);
     const u128 inc = mk128(i_hi, i_lo);
     const u128 c64 = inc * mk128(H_POW2.v[6].ghi, H_POW2.v[6].glo);
     constexpr u128 M64 = mk128(H_POW2.v[6].mhi, H_POW2.v[6].mlo);
@@ -911,6 +1014,7 @@ zig_emit_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64_
         const ulonglong2 en = entry[b];
         const unsigned long long ord_blk = uni64(en.y);
         if (ord_blk >= o_hi) break;                         // (blocks are in ordinal order: nothing left to write)
+        sink.block(ord_blk);
         const ulonglong2 bs = blk_state[b];
         const u128 s_blk = mk128(uni64(bs.x), uni64(bs.y));
         // classes of the 16 rows, row j in lane j
@@ -950,26 +1054,27 @@ zig_emit_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64_
                             const unsigned long long o = ord_blk + readlane32(base_col, j) +
                                                          __builtin_popcountll(all & ((1ull << pz) - 1ull));
                             if (lane == 0 && o - o_lo < o_n) {
-                                g[o - o_lo] = v;
+                                sink(o, v);
                                 if (o + 1 == n) st->n_raw = blk_pos + 64u * j + pz + 1 + consumed;
                             }
                         }
                         if ((e >> lane) & 1) {
                             const unsigned long long o = ord_blk + readlane32(base_col, j) + mbcnt64(all);
                             if (o - o_lo < o_n) {
-                                g[o - o_lo] = zig_value(raw, L.wi);
+                                sink(o, zig_value(raw, L.wi));
                                 if (o + 1 == n) st->n_raw = blk_pos + 64u * j + lane + 1 + ((readlane64(ew_col, j) >> lane) & 1);
                             }
                         }
                     } else if ((e >> lane) & 1) {
                         const unsigned long long o = ord_blk + readlane32(base_col, j) + mbcnt64(e);
                         if (o - o_lo < o_n) {
-                            g[o - o_lo] = zig_value(raw, L.wi);
+                            sink(o, zig_value(raw, L.wi));
                             if (o + 1 == n) st->n_raw = blk_pos + 64u * j + lane + 1 + ((readlane64(ew_col, j) >> lane) & 1);
                         }
                     }
                     s = s * M64 + c64;
                 }
+                sink.flush(std::min<unsigned long long>(ord_blk + readlane32(base_col + pc, ZIG_ROWS - 1), o_hi));
                 continue;
             }
         }
@@ -986,7 +1091,7 @@ zig_emit_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64_
                 if ((e >> lane) & 1) {
                     const unsigned long long o = ord + mbcnt64(e);
                     if (o - o_lo < o_n) {
-                        g[o - o_lo] = zig_value(raw, L.wi);
+                        sink(o, zig_value(raw, L.wi));
                         if (o + 1 == n) st->n_raw = blk_pos + 64u * j + lane + 1 + ((r.e_wedge >> lane) & 1);
                     }
                 }
@@ -996,13 +1101,14 @@ zig_emit_kernel(const ulonglong2 *__restrict__ blk_state, uint64_t i_hi, uint64_
                 unsigned consumed;
                 zig_tail_walk(s_blk, inc, 64u * j + r.tl_bit, v, consumed, &st->error);
                 if (lane == 0 && ord - o_lo < o_n) {
-                    g[ord - o_lo] = v;
+                    sink(ord, v);
                     if (ord + 1 == n) st->n_raw = blk_pos + 64u * j + r.tl_bit + 1 + consumed;
                 }
                 ord += 1;
                 pos = 64u * j + r.tl_bit + 1 + consumed;
             }
         }
+        sink.flush(std::min<unsigned long long>(ord, o_hi));
     }
 }
 
@@ -1164,7 +1270,8 @@ int zig_stream_emit_range(corahip_ctx *ctx, hipStream_t stream, zig_session *s, 
     const unsigned grid = (unsigned)std::max<long>(1, std::min<long>((est + ZIG_WG / 64 - 1) / (ZIG_WG / 64), (long)ctx->num_cu * 32));
     StageTimer t3(ctx, "zig_emit", stream, stream != ctx->stream);
     zig_emit_kernel<<<grid, ZIG_WG, 0, stream>>>(s->rd.blk_state, s->inc[0], s->inc[1], s->rd.nblk, s->rd.entry, s->rd.classes,
-                                                s->rd.tails, 0ull, s->n, o_lo, o_hi, s->d_first + r, slot, s->rd.st);
+                                                s->rd.tails, 0ull, s->n, o_lo, o_hi, s->d_first + r, sink_store{slot, o_lo},
+                                                s->rd.st);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1183,6 +1290,39 @@ int zig_stream_finish(corahip_ctx *ctx, hipStream_t stream, zig_session *s, uint
 }
 
 void zig_stream_free(zig_session *s) { delete s; }
+
+// the next n normals from (state, inc) through `sink`, ordinals 0 .. n: rounds of block tables until n are out
+// (almost always one; a short round is followed by another from where it ended)
+template <class Sink>
+static int zig_rounds(corahip_ctx *ctx, const uint64_t state[2], const uint64_t inc[2], unsigned long long n, const Sink &sink,
+                      const char *what, uint64_t *n_raw) {
+    unsigned long long pos0 = 0, ord0 = 0;
+    for (int round = 0; round < 64; round++) {
+        zig_round rd;
+        int rc = zig_round_tables(ctx, n - ord0, 0, rd);
+        if (rc) return rc;
+        if ((rc = zig_round_count_scan(ctx, ctx->stream, state, inc, pos0, ord0, rd))) return rc;
+        {
+            StageTimer t3(ctx, "zig_emit");
+            zig_emit_kernel<<<rd.grid, ZIG_WG, 0, ctx->stream>>>(rd.blk_state, inc[0], inc[1], rd.nblk, rd.entry, rd.classes, rd.tails,
+                                                                pos0, n, 0ull, n, nullptr, sink, rd.st);
+            LAUNCH_CHECK();
+        }
+        zig_status hs;
+        if ((rc = zig_status_read(ctx->stream, rd.st, what, hs))) return rc;
+        if (hs.total >= n) {
+            *n_raw = hs.n_raw;
+            return 0;
+        }
+        pos0 += (unsigned long long)rd.nblk * ZIG_BLK + hs.k_last;
+        ord0 = hs.total;
+    }
+    corahip_set_error("%s: no convergence", what);
+    return CORAHIP_ESTATE;
+}
+
+// values per session of corahip_normal_rows_pcg64
+#define ZIG_ROWS_SESSION (1ull << 28)
 
 extern "C" {
 
@@ -1213,30 +1353,39 @@ int corahip_normals_pcg64(corahip_ctx *ctx, const uint64_t state[2], const uint6
         return CORAHIP_ESTATE;
     }
     StageTimer timer(ctx, "normals_pcg64");
-    unsigned long long pos0 = 0, ord0 = 0;
-    for (int round = 0; round < 64; round++) {
-        zig_round rd;
-        int rc = zig_round_tables(ctx, (unsigned long long)n - ord0, 0, rd);
-        if (rc) return rc;
-        if ((rc = zig_round_count_scan(ctx, ctx->stream, state, inc, pos0, ord0, rd))) return rc;
-        {
-            StageTimer t3(ctx, "zig_emit");
-            zig_emit_kernel<<<rd.grid, ZIG_WG, 0, ctx->stream>>>(rd.blk_state, inc[0], inc[1], rd.nblk, rd.entry, rd.classes, rd.tails,
-                                                                pos0, (unsigned long long)n, 0ull, (unsigned long long)n, nullptr,
-                                                                g, rd.st);
-            LAUNCH_CHECK();
-        }
-        zig_status hs;
-        if ((rc = zig_status_read(ctx->stream, rd.st, "normals_pcg64", hs))) return rc;
-        if (hs.total >= (unsigned long long)n) {
-            *n_raw = hs.n_raw;
-            return 0;
-        }
-        pos0 += (unsigned long long)rd.nblk * ZIG_BLK + hs.k_last;
-        ord0 = hs.total;
+    return zig_rounds(ctx, state, inc, (unsigned long long)n, sink_store{g, 0ull}, "normals_pcg64", n_raw);
+}
+
+int corahip_normal_rows_pcg64(corahip_ctx *ctx, const uint64_t state[2], const uint64_t inc[2], long nrow, long ncol,
+                              const double *scale, const int64_t *row_off, double *out, int accumulate, uint64_t *n_raw) {
+    ARG_CHECK(ctx != nullptr && state != nullptr && inc != nullptr && nrow >= 0 && ncol >= 0 && n_raw != nullptr);
+    ARG_CHECK(accumulate == 0 || accumulate == 1);
+    ARG_CHECK(nrow == 0 || ncol == 0 || ncol <= (long)(0x7fffffffffffffffll / nrow));
+    *n_raw = 0;
+    if (nrow == 0 || ncol == 0) return 0;
+    ARG_CHECK(scale != nullptr && out != nullptr);
+    if (ctx->draw_pending) {
+        corahip_set_error("normal_rows_pcg64: a corahip_draw_alm_numpy_begin session is pending (its tables share this call's scratch)");
+        return CORAHIP_ESTATE;
     }
-    corahip_set_error("normals_pcg64: no convergence");
-    return CORAHIP_ESTATE;
+    StageTimer timer(ctx, "normal_rows_pcg64");
+    // whole rows per session, so that the block tables (0.3 bytes per value) stay below ~80 MB; a session ends on a
+    // sample boundary and the next continues from the state numpy would be in there: the bits do not depend on the cut
+    const long per = std::max<long>(1, (long)(ZIG_ROWS_SESSION / (unsigned long long)ncol));
+    uint64_t st[2] = {state[0], state[1]};
+    for (long r0 = 0; r0 < nrow; r0 += per) {
+        const long nr = std::min<long>(per, nrow - r0);
+        sink_rows sink{scale + r0, row_off ? row_off + r0 : nullptr, row_off ? out : out + (size_t)r0 * (size_t)ncol,
+                       (unsigned long long)ncol, accumulate, 0ull, 0ull, 0ull, nullptr};
+        uint64_t used = 0;
+        const int rc = zig_rounds(ctx, st, inc, (unsigned long long)nr * (unsigned long long)ncol, sink, "normal_rows_pcg64", &used);
+        if (rc) return rc;
+        const u128 s = host_advance(mk128(st[0], st[1]), mk128(inc[0], inc[1]), used);
+        st[0] = (uint64_t)(s >> 64);
+        st[1] = (uint64_t)s;
+        *n_raw += used;
+    }
+    return 0;
 }
 
 }  // extern "C"

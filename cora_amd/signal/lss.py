@@ -17,8 +17,11 @@ The steps around it (csrc/lsschain.hip): ``biased_field`` (GenerateBiasedFieldBa
 in, map out, on the device.  ``multifrequency_aps_device`` and ``generate_initial_lss_device`` are the step before it
 (CalculateMultiFrequencyAngularPowerSpectrum.process, :289-373, GenerateInitialLSSFromCl, :397-478): the three
 correlation functions of ``calculate_correlations`` to C_l(chi, chi') in one pass, the extended covariance, the draw of
-``phi, delta`` - so that P(k) -> xi -> C_l -> (phi, delta) -> tracer map is one device chain.  The bias, growth and temperature models of the reference are not part of this package:
-``b1``, ``b2``, ``sigmaP``, ``D``, ``f``, ``T_b`` are per-slice arrays (or scalars) the caller supplies.
+``phi, delta`` - so that P(k) -> xi -> C_l -> (phi, delta) -> tracer map is one device chain.  ``tracer_map_device`` takes ``b1``, ``b2``, ``sigmaP``, ``D``, ``f``, ``T_b`` as per-slice arrays (or scalars) the
+caller supplies; ``tracer_models`` derives them from a redshift axis and the models of ``signal/lssmodels.py``, and
+``tracer_map_from_models_device`` composes the chain with them and with ``add_correlated_shot_noise_device``
+(``AddCorrelatedShotNoise``, lss.py:1223-1302).  ``generate_flat_spectrum_map_device`` (``GenerateFlatSpectrumMap``,
+:1422-1552) draws through the same ``nputil.normal_rows_device``: numpy's scaled normals out of the device generator.
 
 The reference's scatter (pmesh_util.c:37, called from pmesh.pyx:_bin_delta) indexes ``out`` with a row stride of 9
 (the number of pixel weights) instead of the map's npix, so mass meant for radial bin ``ri`` lands ri (npix - 9)
@@ -556,3 +559,280 @@ def tracer_map_device(phi, delta, chi, D, f, b1, b2=None, sigmaP=None, dynamics=
     if sigmaP is not None:
         final = fingers_of_god_device(final, chi, sigmaP, fog_D, alpha_FoG, band_cut)
     return biased_lss_to_map_device(final, map_lognormal, map_prefactor, T_b, polarisation)
+
+
+# ------------------------------------------------------------------------------------
+# tracer models, correlated shot noise, flat-spectrum maps
+# (cora/signal/lss.py:182-243, 676-684, 1223-1302, 1422-1589; the models: signal/lssmodels.py)
+# ------------------------------------------------------------------------------------
+def _default_cosmology(cosmology):
+    if cosmology is None:
+        from ..util.cosmology import Cosmology
+
+        cosmology = Cosmology()
+    return cosmology
+
+
+def polynomial_bias(z, model=None, z_eff=None, bias_coeff=None, alpha_b=1.0):
+    """``GeneratePolynomialBias._bias_1`` (lss.py:657-684): the first-order LAGRANGIAN bias at redshift ``z``, from
+    ``z_eff`` and ``bias_coeff`` (``sum_n c_n (z - z_eff)^n``) when both are given, else from the named ``model`` of
+    ``lssmodels.bias``; ValueError when neither is.  ``alpha_b`` scales the EULERIAN bias: ``alpha_b b + alpha_b - 1``."""
+    from . import lssmodels
+
+    if z_eff is not None and bias_coeff is not None:
+        b = lssmodels.PolyModelSet.evaluate_poly(z, z_eff, bias_coeff)
+    elif model is not None:
+        b = lssmodels.bias[model](z)
+    else:
+        raise ValueError("Either `model` must be set, or `z_eff` and `bias_coeff`")
+    return alpha_b * b + alpha_b - 1.0
+
+
+def blend_power_spectrum(ps_linear, ps_nonlinear, alpha_NL=1.0):
+    """The mix of ``BlendNonLinearPowerSpectrum.process`` (lss.py:233-238) for callables: returns
+    ``k -> ps_linear(k) (1 - alpha_NL) + ps_nonlinear(k) alpha_NL`` (0: linear, 1: non-linear), a ``ps`` for
+    :func:`calculate_correlations`."""
+
+    def ps(k):
+        return ps_linear(k) * (1 - alpha_NL) + ps_nonlinear(k) * alpha_NL
+
+    return ps
+
+
+def differential_comoving_volume(z, cosmo=None):
+    """Comoving volume per unit redshift and steradian at ``z`` in (Mpc/h)^3, ``chi^2 c / H`` (lss.py:1555-1589);
+    ``cosmo`` defaults to ``Cosmology()``."""
+    from ..util import constants
+
+    cosmo = _default_cosmology(cosmo)
+    H_z = cosmo.H(z) * (cosmo._unit_distance / 1000.0)          # (km h) / (Mpc s)
+    dm = cosmo.comoving_distance(z)
+    return dm**2 * (constants.c / 1e3) / H_z
+
+
+def shot_noise_seed(delta):
+    """The seed ``AddCorrelatedShotNoise.setup`` derives from the initial field (lss.py:1259-1263): ``zlib.adler32`` of
+    ``delta[:, :100]`` as contiguous float64 bytes.  For a device tensor that corner is copied to the host."""
+    import zlib
+
+    sub = delta[:, :100]
+    sub = np.ascontiguousarray(_host(sub), dtype=np.float64)
+    return zlib.adler32(sub.copy().tobytes())
+
+
+def shot_noise_std(nside, chi, n_eff):
+    """Standard deviation per slice of the shot noise of ``n_eff`` sources per (Mpc/h)^3 in a HEALPix voxel
+    (lss.py:1289-1296): ``(pixarea chi^2 width(chi) n_eff) ** -0.5``."""
+    pixarea = 4 * np.pi / hputil.nside2npix(nside)
+    chi = np.asarray(chi, dtype=np.float64)
+    volume = pixarea * (chi**2) * lssutil.calculate_width(chi)
+    return (volume * n_eff) ** -0.5
+
+
+def _shot_noise_n_eff(n, n_eff, log_M_HI_g, redshift, cosmology, omega_HI_model):
+    from . import lssmodels
+
+    if n_eff is not None:
+        return np.ones(n) * _rows(n_eff, n, "n_eff")
+    if log_M_HI_g is not None:
+        if redshift is None:
+            raise ValueError("log_M_HI_g needs the redshift of every slice")
+        z = _rows(redshift, n, "redshift")
+        return lssmodels.log_M_HI_g_to_n_eff(log_M_HI_g, _default_cosmology(cosmology), z, omega_HI_model)
+    raise RuntimeError("One of `n_eff` or `log_M_HI_g` must be set.")
+
+
+def _shot_noise_rng(rng, seed, seed_field):
+    if rng is not None:
+        return rng
+    if seed is None:
+        seed = shot_noise_seed(seed_field)
+    return np.random.default_rng(seed)
+
+
+def add_correlated_shot_noise_device(delta, chi, n_eff=None, log_M_HI_g=None, redshift=None, cosmology=None,
+                                     omega_HI_model="Crighton2015", seed=None, rng=None, seed_from=None):
+    """``AddCorrelatedShotNoise`` (lss.py:1223-1302) IN PLACE on a device tensor ``delta`` [nchi, npix]:
+    ``delta += rng.normal(scale=std[:, None], size=delta.shape)`` with ``std = shot_noise_std(nside, chi, n_eff)``;
+    returns ``delta``.
+
+    n_eff : sources per (Mpc/h)^3, a scalar or one value per slice.  It wins over ``log_M_HI_g``, the log10 of the HI
+        mass per tracer in solar masses, which needs the ``redshift`` of every slice (and ``cosmology``, default
+        ``Cosmology()``, ``omega_HI_model``).  RuntimeError when neither is given.
+    rng, seed, seed_from : the generator is ``rng`` if given, else ``numpy.random.default_rng(seed)``; with ``seed``
+        None the seed is :func:`shot_noise_seed` of ``seed_from`` (the INITIAL field, as in the reference, so that
+        every tracer of one realisation gets the same noise) or of ``delta`` itself.
+
+    The draw equals the reference's statement bit for bit GIVEN THE SAME Generator: a PCG64 generator is continued on
+    the device, the normals leave the generator's emit pass scaled and added (``nputil.normal_rows_device``).  How the
+    reference's task builds its generator from the seed (caput's ``RandomTask``) is not restated here."""
+    from ..util import nputil
+
+    n, npix = _check_field(delta, "delta")
+    chi_h = np.asarray(_host(chi), dtype=np.float64)
+    _assert_shape(chi_h, (n,), "chi")
+    nside = hputil._npix2nside(npix)
+    ne = _shot_noise_n_eff(n, n_eff, log_M_HI_g, redshift, cosmology, omega_HI_model)
+    std = shot_noise_std(nside, chi_h, ne)
+    rng = _shot_noise_rng(rng, seed, delta if seed_from is None else seed_from)
+    nputil.normal_rows_device(rng, std, npix, delta, accumulate=True)
+    return delta
+
+
+def add_correlated_shot_noise(delta, chi, n_eff=None, log_M_HI_g=None, redshift=None, cosmology=None,
+                              omega_HI_model="Crighton2015", seed=None, rng=None, seed_from=None):
+    """:func:`add_correlated_shot_noise_device` for a numpy array: returns a new array, ``delta`` is left as it is."""
+    delta = np.asarray(delta, dtype=np.float64)
+    n, npix = _check_field(delta, "delta")
+    _assert_shape(np.asarray(chi), (n,), "chi")
+    hputil._npix2nside(npix)
+    _shot_noise_n_eff(n, n_eff, log_M_HI_g, redshift, cosmology, omega_HI_model)
+    rng = _shot_noise_rng(rng, seed, delta if seed_from is None else seed_from)
+    ctx = _lib.get_context()
+    return ctx.to_host(add_correlated_shot_noise_device(ctx.to_device(delta), chi, n_eff, log_M_HI_g, redshift, cosmology,
+                                                        omega_HI_model, rng=rng))
+
+
+_STOKES = ("I", "Q", "U", "V")
+
+
+def _flat_spectrum_plan(nside, frequencies, full_pol, pol, variance, P_SN, use_freq_dependent_voxel_volume, cosmology):
+    """Everything of ``GenerateFlatSpectrumMap`` (lss.py:1476-1535) up to the draw, on the host:
+    ``(nfreq, npol_total, ipol, scale_f [nfreq], attrs)``."""
+    from ..util import constants
+
+    if (variance is None) == (P_SN is None):
+        raise ValueError("Only one of variance or P_SN can be specified.")
+    pol = list(pol)
+    if not full_pol and pol != ["I"]:
+        raise RuntimeError("Must have full_pol=True if nonzero non-I maps are desired.")
+    pol_axis = list(_STOKES) if full_pol else ["I"]
+    ipol = [pol_axis.index(p) for p in pol]
+    if len(set(ipol)) != len(ipol):
+        raise ValueError("pol names a Stokes parameter twice: %r" % (pol,))
+    freq = np.asarray(frequencies, dtype=np.float64)
+    nfreq = len(freq)
+    redshift = constants.nu21 / freq - 1
+    ref_chan = int(nfreq / 2.0)
+    omega = 4 * np.pi / hputil.nside2npix(nside)
+    if use_freq_dependent_voxel_volume:
+        dV = differential_comoving_volume(redshift, cosmology)
+        dz = lssutil.calculate_width(redshift)
+    else:
+        dV = differential_comoving_volume(redshift[ref_chan], cosmology)
+        dz = redshift[ref_chan + 1] - redshift[ref_chan]
+    voxvol = dV * dz * omega
+    if variance is not None:
+        scale = variance**0.5
+    else:
+        scale = P_SN**0.5
+        scale = scale / voxvol**0.5
+    scale_f = np.ones(nfreq) * scale
+    attrs = {"voxvol_ref": voxvol, "central_redshift": redshift[ref_chan]}
+    return nfreq, len(pol_axis), ipol, scale_f, attrs
+
+
+def generate_flat_spectrum_map_device(nside, frequencies, full_pol=True, pol=("I",), variance=None, P_SN=None,
+                                      use_freq_dependent_voxel_volume=False, cosmology=None, seed=None, rng=None):
+    """``GenerateFlatSpectrumMap`` (lss.py:1422-1552): a map [nfreq, 4 or 1, npix] on the device whose Stokes planes
+    ``pol`` hold zero-mean Gaussian noise of standard deviation ``variance ** 0.5`` or ``(P_SN / V_voxel) ** 0.5``,
+    the other planes zeros; returns ``(map, attrs)`` with ``attrs = {"voxvol_ref", "central_redshift"}``.
+
+    frequencies : MHz.  ``V_voxel`` is that of the central channel ``nfreq // 2``, or per channel with
+        ``use_freq_dependent_voxel_volume``.  Exactly one of ``variance`` and ``P_SN`` (ValueError); planes other than
+        I need ``full_pol`` (RuntimeError).
+    rng : default ``numpy.random.default_rng(seed)``.  The planes equal
+        ``rng.normal(scale=scale, size=(nfreq, len(pol), npix))`` bit for bit given the same Generator: one
+        ``nputil.normal_rows_device`` call whose rows are (channel, drawn plane) in C order."""
+    import torch
+
+    from ..util import nputil
+
+    nfreq, npol, ipol, scale_f, attrs = _flat_spectrum_plan(nside, frequencies, full_pol, pol, variance, P_SN,
+                                                            use_freq_dependent_voxel_volume, cosmology)
+    npix = hputil.nside2npix(nside)
+    if rng is None:
+        rng = np.random.default_rng(seed)
+    ctx = _lib.get_context()
+    m = torch.zeros((nfreq, npol, npix), dtype=torch.float64, device=ctx.device)
+    row_off = (np.arange(nfreq, dtype=np.int64)[:, np.newaxis] * npol + np.asarray(ipol, dtype=np.int64)[np.newaxis, :]) * npix
+    nputil.normal_rows_device(rng, np.repeat(scale_f, len(ipol)), npix, m, row_off=row_off.reshape(-1), accumulate=False)
+    return m, attrs
+
+
+def generate_flat_spectrum_map(nside, frequencies, full_pol=True, pol=("I",), variance=None, P_SN=None,
+                               use_freq_dependent_voxel_volume=False, cosmology=None, seed=None, rng=None):
+    """:func:`generate_flat_spectrum_map_device` with the map as a numpy array."""
+    _flat_spectrum_plan(nside, frequencies, full_pol, pol, variance, P_SN, use_freq_dependent_voxel_volume, cosmology)
+    ctx = _lib.get_context()
+    m, attrs = generate_flat_spectrum_map_device(nside, frequencies, full_pol, pol, variance, P_SN,
+                                                 use_freq_dependent_voxel_volume, cosmology, seed, rng)
+    return ctx.to_host(m), attrs
+
+
+def tracer_models(redshift, cosmology=None, bias_model="HI", alpha_b=1.0, sigma_P_model=None, use_mean_21cmT=False,
+                  omega_HI_model="Crighton2015"):
+    """The per-slice numbers the reference's tasks derive from a redshift axis (lss.py:569-577, 1191-1196, 982-989 and
+    the dynamics tasks): a dict of ``chi`` (``comoving_distance``), ``D`` (``growth_factor(z) / growth_factor(0)``),
+    ``f`` (``growth_rate``), ``b1`` (:func:`polynomial_bias` of ``bias_model``), ``sigmaP`` (``lssmodels.sigma_P`` model,
+    None without one), ``fog_D`` (``growth_factor(z)``, what ``FingersOfGod`` divides out) and ``T_b``
+    (``mean_21cm_temperature`` of the ``omega_HI`` model, None unless ``use_mean_21cmT``)."""
+    from . import lssmodels
+
+    c = _default_cosmology(cosmology)
+    z = np.asarray(redshift, dtype=np.float64)
+    T_b = None
+    if use_mean_21cmT:
+        T_b = lssmodels.mean_21cm_temperature(c, z, lssmodels.omega_HI.evaluate(z, model=omega_HI_model))
+    return {
+        "chi": np.asarray(c.comoving_distance(z), dtype=np.float64),
+        "D": c.growth_factor(z) / c.growth_factor(0),
+        "f": c.growth_rate(z),
+        "b1": polynomial_bias(z, model=bias_model, alpha_b=alpha_b),
+        "sigmaP": None if sigma_P_model is None else lssmodels.sigma_P[sigma_P_model](z),
+        "fog_D": c.growth_factor(z),
+        "T_b": T_b,
+    }
+
+
+def tracer_map_from_models_device(phi, delta, redshift, cosmology=None, bias_model="HI", alpha_b=1.0, b2=None,
+                                  sigma_P_model=None, n_eff=None, log_M_HI_g=None, use_mean_21cmT=False,
+                                  omega_HI_model="Crighton2015", seed=None, rng=None, **kw):
+    """:func:`tracer_map_device` with ``chi, D, f, b1, sigmaP, fog_D, T_b`` taken from :func:`tracer_models` of the
+    redshift axis, and correlated shot noise added to the final field before it becomes a map:
+    :func:`biased_field_device` -> the dynamics -> :func:`fingers_of_god_device` (with a ``sigma_P_model``) ->
+    :func:`add_correlated_shot_noise_device` (skipped when ``n_eff`` and ``log_M_HI_g`` are both None; seeded from
+    ``seed`` / ``rng``, else from the initial ``delta``) -> :func:`biased_lss_to_map_device`.  ``**kw``: the remaining
+    keywords of :func:`tracer_map_device` (``dynamics``, ``lognormal``, ``lightcone``, ``redshift_space``, ``fog_D``,
+    ``alpha_FoG``, ``band_cut``, ``map_lognormal``, ``map_prefactor``, ``polarisation``, ``sigma_chi``, ``lmax``,
+    ``niter``, ``sph``).  A composition only: every number comes from those calls."""
+    opt = dict(dynamics="zeldovich", lognormal=False, lightcone=True, redshift_space=True, alpha_FoG=1.0, band_cut=None,
+               map_lognormal=False, map_prefactor=1.0, polarisation=True, sigma_chi=None, lmax=None, niter=3, sph=True)
+    m = tracer_models(redshift, cosmology, bias_model, alpha_b, sigma_P_model, use_mean_21cmT, omega_HI_model)
+    opt["fog_D"] = m["fog_D"]
+    unknown = set(kw) - set(opt)
+    if unknown:
+        raise TypeError("tracer_map_from_models_device got unexpected keywords %s" % sorted(unknown))
+    opt.update(kw)
+    if opt["dynamics"] not in ("zeldovich", "linear"):
+        raise ValueError("dynamics must be 'zeldovich' or 'linear' (got %r)" % (opt["dynamics"],))
+    chi, D = m["chi"], m["D"]
+    n, _ = _check_field(delta, "delta")
+    noise = n_eff is not None or log_M_HI_g is not None
+    if noise:
+        _shot_noise_n_eff(n, n_eff, log_M_HI_g, redshift, cosmology, omega_HI_model)
+        rng = _shot_noise_rng(rng, seed, delta)          # (the seed comes from the INITIAL field, before anything else runs)
+    fd = m["f"] if opt["redshift_space"] else None
+    bias = biased_field_device(delta, D, m["b1"], b2, lognormal=opt["lognormal"], lightcone=opt["lightcone"])
+    if opt["dynamics"] == "zeldovich":
+        grid = {} if opt["sph"] else {"sph": False}
+        final = zeldovich_density_device(phi, delta, bias, chi, D, fd, sigma_chi=opt["sigma_chi"], lmax=opt["lmax"],
+                                         niter=opt["niter"], **grid)
+    else:
+        final = linear_dynamics_device(phi, delta, bias, chi, D, fd)
+    del bias
+    if m["sigmaP"] is not None:
+        final = fingers_of_god_device(final, chi, m["sigmaP"], opt["fog_D"], opt["alpha_FoG"], opt["band_cut"])
+    if noise:
+        add_correlated_shot_noise_device(final, chi, n_eff, log_M_HI_g, redshift, cosmology, omega_HI_model, rng=rng)
+    return biased_lss_to_map_device(final, opt["map_lognormal"], opt["map_prefactor"], m["T_b"], opt["polarisation"])

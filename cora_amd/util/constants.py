@@ -10,3 +10,7 @@ k_B = 1.3806503e-23
 mega_parsec = 3.08568025e22
 year = 365.25 * 86400.0
 mega_year = 1e6 * year
+# Used by signal/lssmodels.py (log_M_HI_g_to_n_eff).  The reference reads both from caput.astro.constants, which is not
+# available to compare with: these are the CODATA-2002-era values that go with k_B and mega_parsec above.
+G = 6.6742e-11
+solar_mass = 1.98892e30

@@ -75,6 +75,28 @@ class Cosmology:
             x = np.sinh(x * dhi) / dhi
         return x
 
+    def _pade_x(self, z):
+        if np.abs(self.omega_k) > 1e-3:
+            raise RuntimeError(f"Calculation only valid in a flat universe. Omega_k = {self.omega_k}")
+        return ((1.0 / self.omega_m) - 1.0) / (1.0 + z) ** 3
+
+    def growth_factor(self, z):
+        """Matter growth factor, the Pade approximation of arXiv:1012.2671 (cosmology.py:325-360); flat universes
+        only (RuntimeError for |omega_k| > 1e-3).  Not normalised: divide by ``growth_factor(0)``."""
+        x = self._pade_x(z)
+        num = 1.0 + 1.175 * x + 0.3064 * x**2 + 0.005355 * x**3
+        den = 1.0 + 1.857 * x + 1.021 * x**2 + 0.1530 * x**3
+        return (1.0 + x) ** 0.5 / (1.0 + z) * num / den
+
+    def growth_rate(self, z):
+        """Matter growth rate f = dlnD / dlna from the derivative of that Pade form (cosmology.py:362-401)."""
+        x = self._pade_x(z)
+        dnum = 3.0 * x * (1.175 + 0.6127 * x + 0.01607 * x**2)
+        dden = 3.0 * x * (1.857 + 2.042 * x + 0.4590 * x**2)
+        num = 1.0 + 1.175 * x + 0.3064 * x**2 + 0.005355 * x**3
+        den = 1.0 + 1.857 * x + 1.021 * x**2 + 0.1530 * x**3
+        return 1.0 + 1.5 * x / (1.0 + x) + dnum / num - dden / den
+
 
 def _intf_0_z(f, z):
     if not isinstance(z, np.ndarray):

@@ -3,7 +3,9 @@
 ``matrix_root_manynull`` runs the library's batched factor kernel (K2) on a batch of one;
 ``complex_std_normal`` consumes a numpy generator exactly as the reference does (that IS
 the definition of the seeded stream); ``DeviceRNG`` is this package's
-counter-based alternative that never leaves the GPU.
+counter-based alternative that never leaves the GPU; ``normal_rows_device`` is
+``rng.normal(scale=s[:, None], size=(nrow, ncol))`` stored or added in place on the device,
+for a PCG64 generator straight out of the device generator's emit pass.
 """
 import numpy as np
 
@@ -67,6 +69,68 @@ def complex_std_normal(shape, rng=None):
         re = rng.standard_normal(shape)
         im = rng.standard_normal(shape)
     return (re + 1.0j * im) / 2**0.5
+
+
+_HOST_CHUNK = 1 << 22          # values per rng.normal call of the host route of normal_rows_device
+
+
+def normal_rows_device(rng, scale, ncol, out, row_off=None, accumulate=False):
+    """``rng.normal(scale=scale[:, None], size=(len(scale), ncol))`` written (``accumulate=False``) or added in place to
+    the device tensor ``out`` - what ``AddCorrelatedShotNoise`` and ``GenerateFlatSpectrumMap`` draw
+    (cora/signal/lss.py:1297-1300, 1538-1540) - with the bits numpy gives for the same generator.
+
+    Row ``r`` goes to ``out.view(-1)[row_off[r] : row_off[r] + ncol]`` (``row_off`` None: ``r * ncol``); ``scale`` is a
+    host array [nrow], ``row_off`` host integers [nrow], ``out`` a contiguous device float64 tensor.
+
+    A ``Generator`` on PCG64 is continued on the device (``corahip_normal_rows_pcg64``: the values leave the
+    generator's emit pass scaled and placed, no buffer of normals exists) under ``bit_generator.lock``, and is left
+    where numpy would leave it.  Any other ``Generator`` - and a PCG64 one while a draw session holds the context's
+    tables (``CORAHIP_ESTATE``) - takes the host route: ``rng.normal`` in chunks of rows, each uploaded and stored or
+    added.  ``rng`` must be a ``numpy.random.Generator``: there is no legacy global stream here, the reference's tasks
+    always hold a generator; pass ``numpy.random.default_rng(seed)``.  Returns ``out``."""
+    from ..core import skysim
+
+    if not isinstance(rng, np.random.Generator):
+        raise TypeError("rng must be a numpy.random.Generator (got %s); use numpy.random.default_rng(seed)" % type(rng).__name__)
+    scale = np.ascontiguousarray(scale, dtype=np.float64)
+    if scale.ndim != 1:
+        raise ValueError("scale must be one value per row (got shape %s)" % (scale.shape,))
+    nrow, ncol = len(scale), int(ncol)
+    ctx = _lib.get_context()
+    if skysim._is_pcg64_generator(rng):
+        bg = rng.bit_generator
+        with bg.lock:                                          # the lock numpy's own draws hold
+            st = bg.state
+            s, inc = int(st["state"]["state"]), int(st["state"]["inc"])
+            try:
+                nraw = ctx.normal_rows_pcg64(s, inc, scale, ncol, out, row_off=row_off, accumulate=accumulate)
+            except _lib.CoraHipError as e:
+                if e.status != _lib.CORAHIP_ESTATE:
+                    raise
+                nraw = None                                    # a draw session is pending: the host route, outside the lock
+            else:
+                st["state"]["state"] = _lib.pcg64_advance(s, inc, nraw)
+                bg.state = st                                  # (has_uint32 / uinteger untouched, as normal leaves them)
+        if nraw is not None:
+            return out
+    # the host route (the wrapper's argument checks first: nothing is drawn for a call that is refused)
+    _, offs = _lib.Context.check_rows(scale, ncol, out, row_off)
+    if nrow == 0 or ncol == 0:
+        return out
+    if offs is None:
+        offs = np.arange(nrow, dtype=np.int64) * ncol
+    flat = out.view(-1)
+    per = max(1, _HOST_CHUNK // ncol)
+    for r0 in range(0, nrow, per):
+        r1 = min(nrow, r0 + per)
+        chunk = ctx.to_device(rng.normal(scale=scale[r0:r1, np.newaxis], size=(r1 - r0, ncol)))
+        for r in range(r0, r1):
+            dst = flat[int(offs[r]):int(offs[r]) + ncol]
+            if accumulate:
+                dst.add_(chunk[r - r0])
+            else:
+                dst.copy_(chunk[r - r0])
+    return out
 
 
 def save_ndarray_list(fname, la):

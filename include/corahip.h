@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64 */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -166,6 +166,21 @@ int corahip_normals_philox(corahip_ctx *ctx, uint64_t seed, int lmax, int F, dou
  * 256-strip ziggurat of numpy/random/src/distributions/distributions.c; restated in oracle/npnormal.py. */
 int corahip_normals_pcg64(corahip_ctx *ctx, const uint64_t host_state[2], const uint64_t host_inc[2], int64_t n,
                           double *g, uint64_t *host_n_raw);
+/* numpy's Generator(PCG64).normal(0, scale[:, None], (nrow, ncol)), written or added in place: with z the next
+ * nrow * ncol values of that generator's standard_normal in draw order (corahip_normals_pcg64), element (r, c) is
+ *   v = 0.0 + scale[r] * z[r * ncol + c]     (one rounded multiply, then the rounded add of 0.0 - numpy's loc -, which
+ *                                             gives +0.0 for scale = 0 whatever the sign of z; no contraction)
+ *   out[row_off[r] + c] = v                  (accumulate = 0)     or     = out[row_off[r] + c] + v   (accumulate = 1)
+ * straight out of the generator's emit pass: no buffer of normals, no second sweep over `out`.
+ *   scale     device [nrow]
+ *   row_off   device [nrow] element offsets into out, NULL = r * ncol.  The rows must not overlap; the CALLER checks
+ *             that every row_off[r] + ncol lies inside out (the kernel cannot).
+ *   host_n_raw as in corahip_normals_pcg64.  CORAHIP_ESTATE while a draw session is pending.
+ * The rows are cut into sessions of about 2^28 values (each continues from corahip_pcg64_advance of the one before: the
+ * bits do not depend on the cut); synchronises the context's stream once per session. */
+int corahip_normal_rows_pcg64(corahip_ctx *ctx, const uint64_t host_state[2], const uint64_t host_inc[2],
+                              long nrow, long ncol, const double *scale, const int64_t *row_off, double *out,
+                              int accumulate, uint64_t *host_n_raw);
 /* Test hook of that stream's one libm call in the accept path: y[i] = exp(x[i]) as the wedge test of the ziggurat
  * evaluates it on the device - glibc's table-driven exp (sysdeps/ieee754/dbl-64/e_exp.c) in the evaluation order of its
  * FMA build, the libm numpy's random_standard_normal calls (reached from cora/util/nputil.py:125) - for |x| < 512.
