@@ -153,6 +153,7 @@ SIGNATURES = {
     "corahip_sht_plan_ring_classes": (c_int, [c_void_p, PTR]),
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
     "corahip_sht_lambda_entry": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, PTR]),
+    "corahip_sht_lambda_segment_entry": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, PTR, PTR]),
 }
 
 
@@ -2107,6 +2108,17 @@ class Context:
         out = self.empty((lmax - m + 1,))
         _check(self.lib.corahip_sht_lambda_entry(self.h, plan, m, ring_pair, kq, self._f64(out)))
         return out
+
+    def sht_lambda_segment_entry(self, nside, lmax, rt, m, ring_pair, kq):
+        """lambda_lm as lane group ``kq`` of the scalar synthesis kernel forms them for ring tiles of ``128 rt`` ring
+        pairs (``rt`` = 1: 64 and more channels per call, 2: fewer): zero outside the rows the group feeds.  Returns
+        ``(lambda [lmax - m + 1], (l_begin, T, R_kq, entry row or -1))``."""
+        torch = _torch()
+        plan = self.sht_plan(nside, lmax)
+        out = self.empty((lmax - m + 1,))
+        info = self.empty((4,), dtype=torch.int32)
+        _check(self.lib.corahip_sht_lambda_segment_entry(self.h, plan, rt, m, ring_pair, kq, self._f64(out), self._p(info)))
+        return out, tuple(int(v) for v in info.cpu().tolist())
 
 
 _contexts = {}

@@ -54,6 +54,7 @@ struct corahip_sht_plan {
     double2 *d_coefmu = nullptr;                          // [nalm]: (alpha_l, s_l) at alm_idx(l,m)
     double2 *d_seedmu = nullptr;                          // [L][npair]: (mu_{lstart-1}, mu_{lstart})
     double2 *d_seed4 = nullptr;                           // [L][npair][4]: (mu_{R-2}, mu_{R-1}) in front of lane group kq's entry row R (seed_kernel)
+    std::map<int, double2 *> k4_segseed;                  // by RT: [L][npair][4] (mu_{R-2}, mu_{R-1}) in front of the entry row of legendre_kernel's lane group kq (lazy, sht_k4_segseed)
     int32_t *d_lmin = nullptr;                            // [L][ntile] first l per (m, ring tile)
     unsigned *d_queue = nullptr;                          // K4 work-queue head
     int32_t *d_mcut = nullptr;                            // [nring] number of m with any non-negligible lambda_lm
@@ -112,6 +113,37 @@ static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 #ifndef LEG_NBUF
 #define LEG_NBUF 2     // LDS stage ring: one being read + one in flight
 #endif
+
+// Item geometry of legendre_kernel, for the kernel and the plan (segment seeds, item count): an item (m, ring tile)
+// whose first contributing l is lmin walks T macro-steps from l_begin, as it always did, but lane group kq owns the
+// CONTIGUOUS rows [R(kq), R(kq) + Q) - a quarter of the item's 8 T rows - and walks two of them per macro-step: at
+// macro-step t it feeds row R(kq) + 2 t (l - m even) and the row behind it (odd).  Q is even, so the pairs are the
+// pairs (m + 2 j, m + 2 j + 1) of the staggered scheme; rows past lmax (segment 3's overhang; for T < 4 the others'
+// too) carry s = 0.  A ring whose first contributing l is ls is summed from the first pair whose even row is
+// >= ls - 1 on: lane group kq enters at macro-step entry(kq, ls).
+#define LEG_MSPS (LEG_KT / 8)       // macro-steps per LDS stage
+#define LEG_NEVER 0x7fffffff
+struct leg_seg {
+    int l_begin, T;
+    __host__ __device__ static inline leg_seg of(int m, int lmin, int lmax) {
+        leg_seg g;
+        g.l_begin = m + ((lmin - m) & ~7);
+        g.T = (lmax - g.l_begin) / 8 + 1;
+        return g;
+    }
+    __host__ __device__ inline int Q() const { return 2 * T; }
+    __host__ __device__ inline int R(int kq) const { return l_begin + kq * 2 * T; }
+    __host__ __device__ inline int nstage() const { return (T + LEG_MSPS - 1) / LEG_MSPS; }
+    // macro-step at which lane group kq starts to feed a ring with first contributing l `ls` (0: from the segment's
+    // first row, with the state the plan walked up to it), LEG_NEVER if the segment ends in front of row ls - 1
+    __host__ __device__ inline int entry(int kq, int ls, int lmax) const {
+        if (ls > lmax) return LEG_NEVER;
+        const int need = ls - 1 - R(kq);
+        if (need <= 0) return 0;
+        const int e = (need + 1) >> 1;
+        return e < T ? e : LEG_NEVER;
+    }
+};
 
 // LDS stage ring of the two K4 kernels, for the kernel and its launcher: NT 16-column tiles, KT rows of l per stage,
 // NBUF stages, XROWS doubles per coefficient row beyond the recurrence pair (0 scalar, 4 spin 2: its g table)
@@ -491,6 +523,9 @@ int sht_legendre(corahip_ctx *ctx, const corahip_sht_plan *p, int ncols, const d
 // legendre_kernel's work list for (RT ring row tiles per wave, ncg column groups): the (m, column group, ring tile) items with at
 // least one contributing l, m-major, as (m | rtile << 15 | cg << 23, first contributing l); cached in the plan
 int sht_k4_items(corahip_ctx *ctx, const corahip_sht_plan *p, int rt, int ncg, const int2 **items, int *nitems);
+// legendre_kernel's entry states for ring tiles of 128 rt ring pairs: per (m, ring pair) four states (mu_{R-2}, mu_{R-1}),
+// one per lane group, in front of its entry row (leg_seg); zeros for a lane group that never enters; cached in the plan
+int sht_k4_segseed(corahip_ctx *ctx, const corahip_sht_plan *p, int rt, const double2 **segseed);
 // K4 spin-2: interleaved (E, B) channels -> (Q, U) cells (builds the plan's g table on first use)
 int sht_legendre_pol(corahip_ctx *ctx, corahip_sht_plan *p, int ncols, const double *alm, double *inter);
 // K5: F_m cells -> maps for nnu_valid channels (nnu_chunk_pad = channels in the cell layout)

@@ -18,23 +18,27 @@ __device__ unsigned long long g_leg_stamps[16];
 #define LEG_STAMP(acc)
 #endif
 
-// Lane roles (wave = 16 rings x 4 k-slots, the A operand of v_mfma_f64_16x16x4_f64):
-// lane (ri = lane&15, kq = lane>>4) runs the recurrence of ring ri STAGGERED by 2 kq steps, so that
-// at every macro-step (8 consecutive l, base l0) the first two values it produces are exactly the
-// ones its k-slot must feed: lambda at l0+2kq (even l-m -> north+south accumulator) and l0+2kq+1
-// (odd).  No cross-lane movement, no selects; the price is that the recurrence coefficients are
-// no longer wave-uniform (4 distinct rows per step) - they are staged through LDS with the a_lm
-// rows and read with one broadcast ds_read_b128 per step.
+// Lane roles of legendre_kernel (wave = 16 rings x 4 k-slots, the A operand of v_mfma_f64_16x16x4_f64):
+// the K index of an MFMA is only a summation index, so slot kq need not hold row l0 + 2 kq of a window of 8
+// consecutive l: it may hold ANY row, provided the B operand of that slot is the a_lm row of the same l.  Lane
+// (ri = lane&15, kq = lane>>4) therefore walks its own CONTIGUOUS quarter of the item's l range (sht_internal.h:
+// leg_seg): rows R(kq), R(kq) + 1, ... of ring ri, two per macro-step, and feeds BOTH - the even l-m row to the
+// north+south accumulator, the odd one to the north-south accumulator.  Every lambda of a ring is computed once per
+// column group (the staggered scheme of rounds 1-6, which legendre_pol_kernel below keeps, computed each four times:
+// a lane ran all 8 rows of a window and fed 2 of them).  No cross-lane movement; the LDS-DMA puts global row
+// R(kq) + par + 2 (7 st + ms) into LDS row 8 ms + 2 kq + par of stage st, with its coefficient pair beside it, so the
+// consumer side (B reads, bank layout, accumulator tiles) is that of the staggered scheme.  The order in which an
+// accumulator sums its rows depends on the item's l_begin, hence on the ring-tile height 128 RT.
 // The recurrence runs in its SCALED two-instruction form (round 3): lambda_l = s_l mu_l with s_m = s_{m+1} = 1,
 // s_l = B_l s_{l-2}, so that  mu_l = (alpha_l x) mu_{l-1} - mu_{l-2},  alpha_l = A_l s_{l-1} / s_l  - a multiply and an
 // fma per step instead of two multiplies and an fma - and only the two values a lane feeds to the MFMAs are scaled back
-// (lambda = s mu): 18 instead of 24 DP instructions per macro-step.  `coef` holds (alpha_l, s_l), `seed` the mu pair at
-// the first contributing l (sht_plan.hip: d_coefmu, d_seedmu); rows past lmax are zeros: s = 0 makes their A operand 0.
-// Round 4: a lane ENTERS AT A WINDOW START.  `seed` is the plan's d_seed4: per (m, ring) four states (mu_{R-2},
-// mu_{R-1}), one per lane group kq, in front of the first row R = m + 2 kq + 8 k >= lstart - 1 (seed_kernel).  The
-// head stages' macro-steps then carry one compare + two selects per ring (is this window the entry?) instead of a
-// compare + three selects per ROW (19.2k against 16.4k cycles per stage, 13 % of the kernel's time was in head
-// stages), and the item prologue no longer walks lanes forward from the first contributing row with dependent loads.
+// (lambda = s mu): 6 DP instructions per macro-step (2 steps + 2 scale-backs).  `coef` holds (alpha_l, s_l)
+// (sht_plan.hip: d_coefmu); rows past lmax are zeros: s = 0 makes their A operand 0.
+// A lane ENTERS AT A PAIR START.  `seed` is the plan's segment-seed table for this RT (sht_k4_segseed): per (m, ring)
+// four states (mu_{R-2}, mu_{R-1}), one per lane group, in front of its entry row: the segment's first row when that
+// is >= lstart - 1 (the lane is live from macro-step 0, no select), else the first pair start >= lstart - 1 inside the
+// segment (one lane group per ring at the most; the head stages' macro-steps carry one compare + two selects per ring
+// for it), zeros if the segment ends before (zero stays zero under the recurrence).
 // NT = 16-column tiles per wave, RT = 16-ring row tiles per wave (RT x NT x 2 parities = 16 accumulator
 // tiles = 128 VGPRs in both shipped shapes: <8,1> for >= 128 columns, <4,2> for 64-column shards, where a
 // second, independent recurrence per lane keeps the recurrence : MFMA ratio of the wide shape).
@@ -52,6 +56,7 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
     constexpr int TRINGS = LEG_RINGS * RT;              // ring pairs per workgroup
     constexpr int RPM = RPW / (LEG_KT / 8);             // a_lm pieces each wave issues per macro-step
     static_assert(RPM * (LEG_KT / 8) == RPW && RPM >= 1 && RPM == LEG_RPM, "whole a_lm pieces per macro-step");
+    static_assert(LEG_WAVES == 8 && LEG_KT <= 64, "wave wv moves LDS rows wv + 8 ms: one segment (wv >> 1), one parity (wv & 1); one coefficient piece");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     int *const s_next = reinterpret_cast<int *>(lds + LEG_NBUF * STAGE);  // next work item, two slots used in turn (carved after the ring)
 
@@ -80,10 +85,11 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
     // (m, ring tile) pairs of cfg 3 have no contributing l at all), each with its first contributing l: decoding an
     // item is one 8-byte scalar load (rounds 1-3: two integer divisions and dependent loads from the first-l table).
     struct item_t {
-        int m, cg, rtile, l_begin, nstage;
+        int m, cg, rtile, l_begin, T, nstage;
         long base_m;
         const double *src0;   // a_lm row (base_m + l_begin) of this column group (wave-uniform)
         int row_limit;        // rows behind src0 that exist: the last m's stage overhang is clamped to the last row
+        int row0;             // first row (behind l_begin) of this WAVE's pieces: it serves segment wv >> 1, parity wv & 1
     };
     auto decode = [&](int it) {
         item_t w;
@@ -91,20 +97,22 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
         w.m = e.x & 0x7fff;
         w.rtile = (e.x >> 15) & 0xff;
         w.cg = (e.x >> 23) & 0xff;
-        const int lmin = e.y;
-        w.l_begin = w.m + ((lmin - w.m) & ~7);
-        w.nstage = (lmax - w.l_begin) / LEG_KT + 1;
+        const leg_seg sg = leg_seg::of(w.m, e.y, lmax);
+        w.l_begin = sg.l_begin;
+        w.T = sg.T;
+        w.nstage = sg.nstage();
         w.base_m = alm_idx(0, w.m, lmax);
         w.src0 = alm + (size_t)w.cg * TCOLS + (size_t)(w.base_m + w.l_begin) * ncols;
         w.row_limit = (int)(last_row - (w.base_m + w.l_begin));
+        w.row0 = (wv >> 1) * sg.Q() + (wv & 1);
         return w;
     };
     // LDS-DMA pieces: every wave issues exactly PIECES per stage (counted vmcnt): RPW a_lm rows (rows past
     // lmax are never used - their lambda is 0 - so any valid row is read, keeping the address scalar) and
     // the CROWS coefficient pairs (all waves write the same bytes).
     auto issue_row = [&](const item_t &w, int st, int rr) {
-        const int row = wv + LEG_WAVES * rr;
-        int r = st * LEG_KT + row;
+        const int row = wv + LEG_WAVES * rr;          // LDS row 8 ms + 2 kq + par of the stage: ms = rr
+        int r = w.row0 + 2 * (st * LEG_MSPS + rr);
         r = r < w.row_limit ? r : w.row_limit;
         // wave-uniform: scalar address arithmetic only (the byte offset of a row fits 32 bits: < 2^12 rows of < 2^13 B... x 8)
         const char *src = reinterpret_cast<const char *>(w.src0) + (unsigned)(r * ncols) * 8u;
@@ -115,13 +123,13 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
     // the macro-step loop costs issue time next to the MFMAs: the generic issue_row spends 8 scalar
     // instructions on the row address (clamp, multiply, 64-bit add, LDS offset) and 4 on saving / setting / restoring
     // M0.  Here the source is a per-STAGE scalar base + a per-lane byte offset that lives in a VGPR for the whole
-    // kernel (one per piece of a stage: voff[p] = 16 lane + 8 p ncols LEG_WAVES), the LDS destination a per-stage
+    // kernel (one per piece of a stage: voff[p] = 16 lane + 16 p ncols - a wave's pieces are two rows apart), the LDS destination a per-stage
     // scalar + an immediate, written straight into M0 (nothing else in this kernel reads M0: the other LDS-DMA
     // helpers set it themselves and the compiler does not use it on gfx950; checked in the ISA).  Only taken when
     // every row of the refilled stage exists (no clamping): the stage loop's `refill_clean`.
     unsigned voff[RPW];
 #pragma unroll
-    for (int p = 0; p < RPW; p++) voff[p] = 16u * lane + (unsigned)(p * LEG_WAVES * ncols) * 8u;
+    for (int p = 0; p < RPW; p++) voff[p] = 16u * lane + (unsigned)(2 * p * ncols) * 8u;
     auto issue_row_fast = [&](const char *rsrc, unsigned rdst, auto pc) {
         constexpr int P = decltype(pc)::value;
         constexpr int IMM = P * LEG_WAVES * STRIDE * 8;
@@ -136,15 +144,11 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
                                                  //  contract stays the comment above, checked in the ISA by tools/asm_of.sh)
     };
     auto issue_coef = [&](const item_t &w, int st) {
-        const int l = w.l_begin + st * LEG_KT + lane;
+        // lane i < LEG_KT fetches the pair of LDS row i = 8 ms + 2 kq + par: global row R(kq) + par + 2 (7 st + ms)
+        const int l = w.l_begin + ((lane >> 1) & 3) * 2 * w.T + (lane & 1) + 2 * (st * LEG_MSPS + (lane >> 3));
         const double *src = (l <= lmax) ? reinterpret_cast<const double *>(coef + w.base_m + l) : zeros;
         const unsigned dst = lds_base_bytes + (unsigned)(((st % LEG_NBUF) * STAGE + LEG_KT * STRIDE) * sizeof(double));
-        if (lane < CROWS) glds16(src, dst);
-        if constexpr (CROWS > 64) {            // (stages of 64 rows: the 72 coefficient rows take a second instruction)
-            const int l2 = l + 64;
-            const double *src2 = (l2 <= lmax) ? reinterpret_cast<const double *>(coef + w.base_m + l2) : zeros;
-            if (lane < CROWS - 64) glds16(src2, dst + 64 * 16);
-        }
+        if (lane < LEG_KT) glds16(src, dst);
     };
     auto issue_stage = [&](const item_t &w, int st) {
         issue_coef(w, st);
@@ -157,7 +161,7 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
     // The first gridDim.x entries are pre-assigned; the queue starts behind them.
     const int nwg = (int)gridDim.x;
     auto clamp_item = [&](unsigned t) { return t < (unsigned)nitems ? (int)t : nitems; };
-    // ring state of an item: cos(theta), first contributing l and the lane group's entry state (plan: d_seed4)
+    // ring state of an item: cos(theta), first contributing l and the lane group's entry state (plan: sht_k4_segseed)
     auto load_rings = [&](const item_t &w, double (&x)[RT], int (&my_ls)[RT], double2 (&sd)[RT]) {
 #pragma unroll
         for (int q = 0; q < RT; q++) {
@@ -211,23 +215,24 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
             // rings are dealt to the waves interleaved (ring = tile base + 8 (ri + 16 q) + wave) so that every
             // wave of the workgroup has the same mix of first-contributing l and reaches the barriers together
             double p0[RT], p1[RT];
-            int inj_l[RT];
-            int ls_min = lmax + 1;
+            int ent[RT];
+            int minent = LEG_NEVER, maxent = -1;
+            const leg_seg sg = {w.l_begin, w.T};
 #pragma unroll
             for (int q = 0; q < RT; q++) {
-                ls_min = min(ls_min, my_ls[q]);
-                // the lane's state is zero until its entry row (a window start of this lane group: >= l_begin + d)
-                p0[q] = 0.0;
-                p1[q] = 0.0;
-                const int t = my_ls[q] - 1 - m - d;
-                inj_l[q] = my_ls[q] <= lmax ? m + d + (t > 0 ? ((t + 7) >> 3) << 3 : 0) : 0x7fffffff;
+                // the lane's entry macro-step (item-wide index g = 7 st + ms): live from the start with the plan's state
+                // (0), zero until it enters mid-way (> 0: the one lane group whose segment holds the ring's row
+                // lstart - 1), or never (the plan's state is zero then)
+                ent[q] = sg.entry(kq, my_ls[q], lmax);
+                p0[q] = ent[q] == 0 ? sd[q].x : 0.0;
+                p1[q] = ent[q] == 0 ? sd[q].y : 0.0;
+                minent = min(minent, ent[q]);
+                maxent = max(maxent, ent[q] == LEG_NEVER ? -1 : ent[q]);
             }
-            // wave-uniform bounds of the start rows: the skip tests of the macro-step loop become scalar compares
-            // (every vector instruction there costs issue time next to the MFMAs)
-            int maxinj = -1;
-#pragma unroll
-            for (int q = 0; q < RT; q++) maxinj = max(maxinj, inj_l[q] == 0x7fffffff ? -1 : inj_l[q]);
-            const int ws_min = wave_min(ls_min), ws_maxinj = wave_max(maxinj);
+            // wave-uniform bounds of the entry steps: the skip tests of the macro-step loop become scalar compares
+            // (every vector instruction there costs issue time next to the MFMAs).  Before ws_minent all 64 lanes of
+            // the wave are zero; behind ws_maxent no lane enters any more.
+            const int ws_minent = wave_min(minent), ws_maxent = wave_max(maxent);
             // The ring's loads (z, first row, seed pair) are CONSUMED here.  Left to the compiler, the wait for the seed pair
             // lands at its only use - the injection branch inside the macro-step loop - and where its registers are
             // reused in the epilogue, as an s_waitcnt vmcnt(0): vmcnt is in order, so that wait also drains every LDS-DMA
@@ -235,25 +240,27 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
 #pragma unroll
             for (int q = 0; q < RT; q++) asm volatile("" ::"v"(x[q]), "v"(sd[q].x), "v"(sd[q].y), "v"(my_ls[q]));
 
-            // Stage loop in three consecutive pieces (same body, `stage` below): the head stages in which rings of
-            // the wave still start, the steady-state stages - every ring runs, none starts, every row <= lmax - whose
-            // macro-steps carry no tests at all and are fully unrolled (every scalar compare / branch / loop increment
-            // costs issue time next to the MFMAs), and the tail stage that overhangs lmax.
-            // A stage is "clean" when (lo) every ring of the wave already runs and none starts in it - true from some
-            // stage on - and (hi) all its rows are <= lmax, it refills the ring and every row of the stage it refills
-            // exists (the fast pieces do not clamp) - true up to some stage.  Both bounds are found once per item, so
-            // the steady-state loop's own condition is one scalar compare.
+            // Stage loop in three consecutive pieces (same body, `stage` below): the head stages in which lanes of
+            // the wave still enter, the steady-state stages - no lane enters any more, all 7 macro-steps belong to the
+            // item - whose macro-steps carry no tests at all and are fully unrolled (every scalar compare / branch / loop
+            // increment costs issue time next to the MFMAs), and the last stage, which stops after T mod 7 macro-steps.
+            // A stage is "clean" when (lo) some lane of the wave is live and none enters in it or later - true from some
+            // stage on - and (hi) all its macro-steps are < T, it refills the ring and every row of the stage it refills
+            // exists (the fast pieces do not clamp; segment 3 reaches furthest: row 6 T + 14 (st + 1) - 1 behind l_begin
+            // is the last of stage st) - true up to some stage.  Both bounds are found once per item, so the steady-state
+            // loop's own condition is one scalar compare.
             auto stage_lo = [&](int st) {
-                const int ls = w.l_begin + st * LEG_KT;
-                return (ws_min <= ls) && (ws_maxinj < ls);
+                const int g0 = st * LEG_MSPS;
+                return (ws_minent <= g0) && (ws_maxent < g0);
             };
-            int st_hi = min(min((lmax - w.l_begin + 1) / LEG_KT, (w.row_limit + 1) / LEG_KT - LEG_NBUF + 1),
+            int st_hi = min(min(w.T / LEG_MSPS, (w.row_limit + 1 - 6 * w.T) / (2 * LEG_MSPS) - LEG_NBUF + 1),
                             w.nstage - LEG_NBUF + 1);
             st_hi = __builtin_amdgcn_readfirstlane(st_hi);
-            // One stage = LEG_KT rows of l.  CLEAN: 1 steady-state stages (no tests at all), 2 head stages whose rows all
-            // exist (unrolled like the steady-state ones, fast refill pieces, but rings of the wave may still enter: the
-            // wave-uniform skip tests and the entry select stay), 0 the rolled generic form (tail stages, and heads of
-            // items too short for the fast pieces).
+            // One stage = LEG_MSPS macro-steps = LEG_KT rows of l, 2 LEG_MSPS from each segment.  CLEAN: 1 steady-state stages (no tests at all), 2 head stages whose rows all
+            // exist and in which some lane of the wave is live from the first macro-step (unrolled like the steady-state
+            // ones, fast refill pieces, one basic block: the entry select - a compare and two 64-bit selects per ring -
+            // runs in every macro-step, no scalar tests), 0 the rolled generic form (the last stage, heads of items too
+            // short for the fast pieces, and the rare stages in front of a wave's first entry: scalar skip tests).
             auto stage = [&](auto clean, const int st) __attribute__((always_inline)) {
                 constexpr int CLEAN = decltype(clean)::value;
                 // own pieces of stage st have landed when at most the pieces of the (up to LEG_NBUF-2) younger
@@ -267,15 +274,15 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
 #endif
                 const bool refill = CLEAN ? true : (st + LEG_NBUF - 1 < w.nstage);   // (the clean loops only take refilling stages)
                 if (refill) issue_coef(w, st + LEG_NBUF - 1);
-                const int ls = w.l_begin + st * LEG_KT;
+                const int g0 = st * LEG_MSPS;
                 const double *sb = lds + (st % LEG_NBUF) * STAGE;
                 const double2 *sc = reinterpret_cast<const double2 *>(sb + LEG_KT * STRIDE) + d;
                 // per-stage scalars of the fast refill pieces (CLEAN stages only)
                 const char *const rsrc = reinterpret_cast<const char *>(w.src0) +
-                                         (unsigned)(((st + LEG_NBUF - 1) * LEG_KT + wv) * ncols) * 8u;
+                                         (unsigned)((w.row0 + 2 * LEG_MSPS * (st + LEG_NBUF - 1)) * ncols) * 8u;
                 const unsigned rdst = __builtin_amdgcn_readfirstlane(
                     lds_base_bytes + (unsigned)((((st + LEG_NBUF - 1) % LEG_NBUF) * STAGE + wv * STRIDE) * sizeof(double)));
-                // One macro-step (8 consecutive l, 16 MFMAs in the <8,1> shape).  `ms` is its index inside the stage: an
+                // One macro-step (2 rows of each segment, 16 MFMAs in the <8,1> shape).  `ms` is its index inside the stage: an
                 // integral_constant in the CLEAN stages, so that every LDS offset and the LDS-DMA destination of the
                 // refill piece are immediates, and the loop variable in the rolled stages.
                 auto macro_step = [&](auto ms) __attribute__((always_inline)) {
@@ -290,25 +297,28 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
 #pragma unroll
                         for (int r = 0; r < RPM; r++) issue_row(w, st + LEG_NBUF - 1, ms * RPM + r);
                     }
-                    const int l0 = ls + 8 * ms;
-                    if (!CLEAN && l0 > lmax) return;
-                    // nothing of this wave starts before l0+14: skip the macro-step entirely
-                    if (CLEAN != 1 && ws_min > l0 + 13) return;
+                    const int g = g0 + ms;                 // macro-step of the item
+                    if (!CLEAN && g >= w.T) return;
+                    // no lane of this wave is live yet (all states and A operands are zero): skip the macro-step entirely
+                    // (the stages in front of the wave's first entry run in the rolled form: see the stage loops)
+                    if (CLEAN == 0 && g < ws_minent) return;
                     double ae[RT], ao[RT];
-                    double2 c[8];
+                    double2 c[2];
 #pragma unroll
-                    for (int j = 0; j < 8; j++) c[j] = sc[8 * ms + j];
-                    if (CLEAN != 1 && ws_maxinj >= l0) {   // (scalar) some ring of the wave may still enter at or after this macro-step
-                        const int lf = l0 + d;             // entry rows are window starts of the lane (plan: d_seed4)
+                    for (int j = 0; j < 2; j++) c[j] = sc[8 * ms + j];
+                    // the entry select: in the unrolled head stages unconditionally - they stay one basic block, and a
+                    // select no lane needs changes nothing; in the rolled form only while (scalar) some lane of the wave
+                    // may still enter at or after this macro-step
+                    if (CLEAN == 2 || (CLEAN == 0 && ws_maxent >= g)) {
 #pragma unroll
                         for (int q = 0; q < RT; q++) {
-                            const bool inj = (inj_l[q] == lf);
+                            const bool inj = (ent[q] == g);
                             p0[q] = inj ? sd[q].x : p0[q];
                             p1[q] = inj ? sd[q].y : p1[q];
                         }
                     }
 #pragma unroll
-                    for (int j = 0; j < 8; j++) {
+                    for (int j = 0; j < 2; j++) {
 #pragma unroll
                         for (int q = 0; q < RT; q++) {
                             const double vv = fma(c[j].x * x[q], p1[q], -p0[q]);
@@ -318,7 +328,6 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
                             if (j == 1) ao[q] = vv * c[1].y;
                         }
                     }
-                    if (CLEAN != 1 && ws_min > l0 + 7) return;  // all A operands of this macro-step are zero
 #if LEG_STAMPS
                     if constexpr (!CLEAN) n_tail_ms++;
 #endif
@@ -348,6 +357,8 @@ legendre_kernel(int lmax, int npair, int nring, int ncols, const double *__restr
 #if LEG_STAMPS
             int st_mark = 0;
 #endif
+            // (rare: every lane of the wave is still zero at the start of the stage - the rolled form skips those macro-steps)
+            for (; st < w.nstage && ws_minent > st * LEG_MSPS; st++) stage(std::integral_constant<int, 0>{}, st);
             for (; st < st_hi && !stage_lo(st); st++) stage(std::integral_constant<int, 2>{}, st);
             LEG_STAMP(t_head);
 #if LEG_STAMPS
@@ -724,12 +735,14 @@ static int launch_legendre(corahip_ctx *ctx, const corahip_sht_plan *p, int ncol
     int rc = sht_k4_items(ctx, p, RT, ncols / (16 * NT), &d_items, &nitems);
     if (rc) return rc;
     if (nitems == 0) return 0;
+    const double2 *d_segseed = nullptr;
+    if ((rc = sht_k4_segseed(ctx, p, RT, &d_segseed))) return rc;
     // persistent: as many workgroups as fit (LDS-limited: one per CU for NT = 8)
     const int per_cu = std::max<int>(1, std::min<int>(2, (int)((160 * 1024) / shm)));
     dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
     HIP_TRY(hipMemsetAsync(p->d_queue, 0, 1024, ctx->stream));
     legendre_kernel<NT, RT><<<grid, 64 * LEG_WAVES, shm, ctx->stream>>>(p->lmax, p->npair, p->nring, ncols, p->d_z,
-                                                                       p->d_coefmu, p->d_lstart, p->d_seed4, d_items, nitems,
+                                                                       p->d_coefmu, p->d_lstart, d_segseed, d_items, nitems,
                                                                        alm, p->d_zeros, inter, p->d_queue);
     LAUNCH_CHECK();
 #if LEG_STAMPS

@@ -206,6 +206,92 @@ __global__ void lambda_entry_kernel(int lmax, int npair, int m, int r, int kq, c
         out[l - m] = v * c.y;
     }
 }
+// first l of the item (m, ring tile of 128 rt ring pairs) that holds ring pair r: the minimum of the tile's 128-ring blocks
+__device__ static inline int tile_lmin(int lmax, int npair, int rt, int m, int r, const int32_t *__restrict__ lmin_tab) {
+    const int trings = LEG_RINGS * rt;
+    const int ntile128 = (npair + LMIN_RINGS - 1) / LMIN_RINGS;
+    const int tile = r / trings;
+    const int t_first = (tile * trings) / LMIN_RINGS;
+    const int t_last = min((tile * trings + trings - 1) / LMIN_RINGS, ntile128 - 1);
+    int lmin = lmax + 1;
+    for (int t = t_first; t <= t_last; t++) lmin = min(lmin, lmin_tab[m * ntile128 + t]);
+    return lmin;
+}
+// segseed[o][kq]: the state (mu_{R-2}, mu_{R-1}) in front of the entry row of legendre_kernel's lane group kq for
+// ring tiles of 128 rt ring pairs (sht_internal.h: leg_seg) - row R(kq) + 2 entry(kq) - and zeros for a lane group that
+// never enters.  One walk per (m, ring): from the staggered table's state in front of the first pair start
+// P0 >= lstart - 1 (seed4 of the lane group that starts there) forward in the kernel's own two-instruction form and
+// order, rows past lmax with the zero pair the kernel reads for them; every entry row is a pair start >= P0.
+__global__ void segseed_kernel(int lmax, int npair, int rt, const double *__restrict__ z,
+                               const double2 *__restrict__ coefmu, const int32_t *__restrict__ lstart,
+                               const double2 *__restrict__ seed4, const int32_t *__restrict__ lmin_tab,
+                               double2 *__restrict__ segseed) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int m = blockIdx.y;
+    if (r >= npair) return;
+    const long o = (long)m * npair + r;
+    const int ls = lstart[o];
+    double2 out[4];
+    int erow[4], last = -1;
+    const leg_seg sg = leg_seg::of(m, tile_lmin(lmax, npair, rt, m, r, lmin_tab), lmax);
+    for (int kq = 0; kq < 4; kq++) {
+        out[kq] = make_double2(0.0, 0.0);
+        const int e = sg.entry(kq, ls, lmax);
+        erow[kq] = e == LEG_NEVER ? -1 : sg.R(kq) + 2 * e;
+        last = max(last, erow[kq]);
+    }
+    if (last >= 0) {
+        const int t = ls - 1 - m;
+        const int P0 = m + (t > 0 ? ((t + 1) >> 1) << 1 : 0);
+        const double2 s0 = seed4[4 * o + (((P0 - m) >> 1) & 3)];
+        const double2 *cm = coefmu + alm_idx(0, m, lmax);
+        const double x = z[r];
+        double p0 = s0.x, p1 = s0.y;
+        for (int row = P0; row <= last; row += 2) {
+            for (int kq = 0; kq < 4; kq++)
+                if (erow[kq] == row) out[kq] = make_double2(p0, p1);
+            for (int j = 0; j < 2; j++) {
+                const double2 c = row + j <= lmax ? cm[row + j] : make_double2(0.0, 0.0);
+                const double vv = fma(c.x * x, p1, -p0);
+                p0 = p1;
+                p1 = vv;
+            }
+        }
+    }
+    for (int kq = 0; kq < 4; kq++) segseed[4 * o + kq] = out[kq];
+}
+// test hook: lambda_lm as legendre_kernel's lane group kq forms them for ring tiles of 128 rt ring pairs - zero outside
+// the rows it feeds, [entry row, R(kq) + Q) - and the geometry: info = (l_begin, T, R(kq), entry row or -1)
+__global__ void lambda_segment_kernel(int lmax, int npair, int rt, int m, int r, int kq, const double *__restrict__ z,
+                                      const double2 *__restrict__ coefmu, const int32_t *__restrict__ lstart,
+                                      const double2 *__restrict__ segseed, const int32_t *__restrict__ lmin_tab,
+                                      double *__restrict__ out, int32_t *__restrict__ info) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double x = z[r];
+    const long o = (long)m * npair + r;
+    const leg_seg sg = leg_seg::of(m, tile_lmin(lmax, npair, rt, m, r, lmin_tab), lmax);
+    const int e = sg.entry(kq, lstart[o], lmax);
+    const int erow = e == LEG_NEVER ? -1 : sg.R(kq) + 2 * e;
+    info[0] = sg.l_begin, info[1] = sg.T, info[2] = sg.R(kq), info[3] = erow;
+    const double2 sd = segseed[4 * o + kq];
+    const double2 *cf = coefmu + alm_idx(0, m, lmax);
+    double p0 = 0.0, p1 = 0.0;
+    for (int l = m; l <= lmax; l++) {
+        double v = 0.0;
+        if (l >= sg.R(kq) && l < sg.R(kq) + sg.Q()) {
+            if (l == erow) {
+                p0 = sd.x;
+                p1 = sd.y;
+            }
+            const double2 c = cf[l];
+            const double vv = fma(c.x * x, p1, -p0);
+            p0 = p1;
+            p1 = vv;
+            v = vv * c.y;
+        }
+        out[l - m] = v;
+    }
+}
 // per ring: mcut = number of m (from 0) whose lambda_lm reach the plan's cut for some l <= lmax; F_m of the ring
 // is exactly zero beyond (lstart is monotone in m), so K4 need not write and K5 need not read those cells
 __global__ void mcut_kernel(int lmax, int npair, int nring, const int32_t *__restrict__ lstart,
@@ -230,9 +316,10 @@ __global__ void lmin_kernel(int lmax, int npair, int ntile, const int32_t *__res
 }
 // FP64 MFMA instructions legendre_kernel<NT, RT> ISSUES for one column group, summed over (m, ring tile, wave): the
 // kernel's own skip logic restated (sht_legendre.hip: legendre_kernel's macro_step) - an item starts at
-// l_begin = m + ((lmin - m) & ~7) with lmin the tile's first contributing l; wave w of the workgroup owns the rings
-// tile * 128 RT + 8 j + w (j < 16 RT) and executes the 2 NT RT MFMAs of the macro-step at l0 = l_begin + 8 k iff
-// l0 <= lmax and ws_min <= l0 + 7 (ws_min = first contributing l of the wave's rings).  Thread = (m, tile, wave);
+// l_begin = m + ((lmin - m) & ~7) with lmin the tile's first contributing l and has T macro-steps (leg_seg); wave w of
+// the workgroup owns the rings tile * 128 RT + 8 j + w (j < 16 RT) and executes the 2 NT RT MFMAs of macro-step g < T
+// unless all its 64 lanes are still zero: g >= ws_minent, the first entry step of its (ring, lane group) lanes - 0 as
+// soon as one ring contributes at the first row of some segment, so the count is close to T per wave.  Thread = (m, tile, wave);
 // out accumulates the number of executed macro-steps.  The count is what SQ_INSTS_VALU_MFMA_F64 reads for the
 // launch (tests/test_gpu_fullsize.py checks it against the committed PMC profile): the roofline fraction of K4 is
 // priced on it, not on the algorithmic 8 nside nalm F of SURVEY 8(d), which counts terms nobody has to compute.
@@ -254,35 +341,28 @@ __global__ void k4_count_kernel(int lmax, int npair, int rt, const int32_t *__re
         const int t_last = min((tile * trings + trings - 1) / LMIN_RINGS, ntile128 - 1);
         for (int t = t_first; t <= t_last; t++) lmin = min(lmin, lmin_tab[m * ntile128 + t]);
         if (lmin <= lmax) {
-            int ws_min = lmax + 1;
+            // the wave's entry bounds as the kernel forms them: over its 16 rt rings x 4 lane groups
+            const leg_seg sg = leg_seg::of(m, lmin, lmax);
+            int ws_minent = LEG_NEVER, ws_maxent = -1;
             for (int j = 0; j < 16 * rt; j++) {
                 const int ring = tile * trings + j * LEG_WAVES + wave;
-                if (ring < npair) ws_min = min(ws_min, lstart[(long)m * npair + ring]);
+                if (ring >= npair) continue;
+                const int ls = lstart[(long)m * npair + ring];
+                for (int kq = 0; kq < 4; kq++) {
+                    const int e = sg.entry(kq, ls, lmax);
+                    ws_minent = min(ws_minent, e);
+                    if (e != LEG_NEVER) ws_maxent = max(ws_maxent, e);
+                }
             }
-            const int l_begin = m + ((lmin - m) & ~7);
-            const int k_max = (lmax - l_begin) / 8;
-            const int need = ws_min - 7 - l_begin;                 // l0 >= ws_min - 7
-            const int k_min = need > 0 ? (need + 7) / 8 : 0;
-            if (k_max >= k_min) n = (unsigned long long)(k_max - k_min + 1);
+            if (ws_minent < sg.T) n = (unsigned long long)(sg.T - ws_minent);
             if (out_clean) {
                 // macro-steps of this wave that run in the test-free steady-state stages (sht_legendre.hip: stage_lo && st < st_hi);
                 // row_limit is not restated: it only matters for the last m's
-                const int KT = LEG_KT;
-                const int nstage = (lmax - l_begin) / KT + 1;
-                const int st_hi = min((lmax - l_begin + 1) / KT, nstage - LEG_NBUF + 1);
-                // ws_maxinj: the last first-contributing l of the wave's rings that lies at or after l_begin + (stagger): bound it by the max lstart <= lmax
-                int ws_max = -1;
-                for (int j = 0; j < 16 * rt; j++) {
-                    const int ring = tile * trings + j * LEG_WAVES + wave;
-                    if (ring < npair) {
-                        const int ls = lstart[(long)m * npair + ring];
-                        if (ls <= lmax) ws_max = max(ws_max, ls);
-                    }
-                }
+                const int st_hi = min(sg.T / LEG_MSPS, sg.nstage() - LEG_NBUF + 1);
                 unsigned long long nc = 0;
                 for (int st = 0; st < st_hi; st++) {
-                    const int ls0 = l_begin + st * KT;
-                    if (ws_min <= ls0 && ws_max < ls0) nc += KT / 8;
+                    const int g0 = st * LEG_MSPS;
+                    if (ws_minent <= g0 && ws_maxent < g0) nc += LEG_MSPS;
                 }
                 if (nc) atomicAdd(out_clean, nc);     // (diagnostics only: one atomic per thread, divergent code - no wave reduction here)
             }
@@ -382,6 +462,22 @@ int sht_k4_items(corahip_ctx *ctx, const corahip_sht_plan *cp, int rt, int ncg, 
     return 0;
 }
 
+int sht_k4_segseed(corahip_ctx *ctx, const corahip_sht_plan *cp, int rt, const double2 **segseed) {
+    corahip_sht_plan *p = const_cast<corahip_sht_plan *>(cp);      // (lazy caches of the plan)
+    auto it = p->k4_segseed.find(rt);
+    if (it == p->k4_segseed.end()) {
+        double2 *d = nullptr;
+        HIP_TRY(hipMalloc((void **)&d, sizeof(double2) * 4 * (size_t)p->L * p->npair));
+        it = p->k4_segseed.emplace(rt, d).first;                  // (owned by the plan from here on)
+        dim3 grid((p->npair + 63) / 64, p->L);
+        segseed_kernel<<<grid, 64, 0, ctx->stream>>>(p->lmax, p->npair, rt, p->d_z, p->d_coefmu, p->d_lstart, p->d_seed4,
+                                                     p->d_lmin, d);
+        LAUNCH_CHECK();
+    }
+    *segseed = it->second;
+    return 0;
+}
+
 extern "C" {
 
 int corahip_sht_plan_destroy(corahip_ctx *ctx, corahip_sht_plan *p) {
@@ -398,6 +494,7 @@ int corahip_sht_plan_destroy(corahip_ctx *ctx, corahip_sht_plan *p) {
     (void)hipFree(p->d_seedmu);
     (void)hipFree(p->d_seed4);
     for (auto &kv : p->k4_items) (void)hipFree(kv.second.first);
+    for (auto &kv : p->k4_segseed) (void)hipFree(kv.second);
     (void)hipFree(p->d_tw);
     (void)hipFree(p->d_zeros);
     (void)hipFree(p->d_lmin);
@@ -772,6 +869,19 @@ int corahip_sht_lambda_entry(corahip_ctx *ctx, const corahip_sht_plan *p, int m,
     ARG_CHECK(m >= 0 && m <= p->lmax && ring_pair >= 0 && ring_pair < p->npair && kq >= 0 && kq < 4);
     lambda_entry_kernel<<<1, 64, 0, ctx->stream>>>(p->lmax, p->npair, m, ring_pair, kq, p->d_z, p->d_coefmu, p->d_lstart,
                                                    p->d_seed4, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_sht_lambda_segment_entry(corahip_ctx *ctx, const corahip_sht_plan *p, int rt, int m, int ring_pair, int kq,
+                                     double *out, int32_t *info) {
+    ARG_CHECK(ctx != nullptr && p != nullptr && out != nullptr && info != nullptr);
+    ARG_CHECK((rt == 1 || rt == 2) && m >= 0 && m <= p->lmax && ring_pair >= 0 && ring_pair < p->npair && kq >= 0 && kq < 4);
+    const double2 *d_segseed = nullptr;
+    int rc = sht_k4_segseed(ctx, p, rt, &d_segseed);
+    if (rc) return rc;
+    lambda_segment_kernel<<<1, 64, 0, ctx->stream>>>(p->lmax, p->npair, rt, m, ring_pair, kq, p->d_z, p->d_coefmu, p->d_lstart,
+                                                     d_segseed, p->d_lmin, out, info);
     LAUNCH_CHECK();
     return 0;
 }

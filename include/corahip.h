@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64 */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook) */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -791,6 +791,14 @@ int corahip_sht_lambda(corahip_ctx *ctx, const corahip_sht_plan *plan, int m, in
  * R = m + 2 kq + 8 k >= lstart - 1, the plan's entry state there (four per (m, ring)), the recurrence behind it; equal
  * to corahip_sht_lambda from row max(R, lstart) on, and below the plan's cut before it.  For tests. */
 int corahip_sht_lambda_entry(corahip_ctx *ctx, const corahip_sht_plan *plan, int m, int ring_pair, int kq, double *out);
+/* its counterpart for the scalar synthesis kernel, whose lane group kq walks the contiguous rows [R_kq, R_kq + 2 T) of
+ * an item (l_begin = m + ((lmin - m) & ~7), lmin the first contributing l of the ring's tile of 128 rt ring pairs,
+ * T = (lmax - l_begin) / 8 + 1 macro-steps, R_kq = l_begin + 2 kq T; rt = 1: 64 and more channels per call, 2: fewer):
+ * lambda from the plan's entry state of that group - in front of R_kq if R_kq >= lstart - 1, else in front of the first
+ * row R_kq + 2 t >= lstart - 1 of the segment - to the segment's end, zero elsewhere -> out [lmax-m+1] (device);
+ * info [4] (device) = (l_begin, T, R_kq, entry row or -1 if the group never enters).  For tests. */
+int corahip_sht_lambda_segment_entry(corahip_ctx *ctx, const corahip_sht_plan *plan, int rt, int m, int ring_pair, int kq,
+                                     double *out, int32_t *info);
 
 #ifdef __cplusplus
 }
