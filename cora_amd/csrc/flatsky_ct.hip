@@ -13,6 +13,11 @@
 // ringfft_blu_ct and stay written out: see the header of sht_ringfft_ct.hip.
 #include "fft_ct.h"
 #include "flatsky_ct.h"
+#include "fft_shapes.h"
+using fft_shapes::line_shape;
+static_assert(fft_shapes::scheduled<Sch, fft_shapes::LINE_REAL>() && fft_shapes::scheduled<Sch, fft_shapes::LINE_C2C>() &&
+                  fft_shapes::scheduled<Sch, fft_shapes::LINE_BLU>(),
+              "every line shape has its three-pass schedule");
 #include "rng_dev.h"
 #include "tile_walk.h"
 
@@ -395,17 +400,9 @@ int flat_c2c_ct(corahip_ctx *ctx, const double *in, double *out, long nouter, in
                 uint64_t seed, bool *took) {
     *took = false;
     if (flat_ct_off() || nouter < 1 || inner < 2) return 0;
-    int rc;
-    if (n == 256 && inner >= 16) rc = launch_linec2c<256, 16, 256>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else if (n == 512 && inner >= 16) rc = launch_linec2c<512, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else if (n == 1024 && inner >= 16) rc = launch_linec2c<1024, 16, 512, true>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else if (n == 1024 && inner >= 8) rc = launch_linec2c<1024, 8, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else if (n == 384 && inner >= 16) rc = launch_linec2c<384, 16, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else if (n == 768 && inner >= 8) rc = launch_linec2c<768, 8, 512>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
-    else return 0;
-    if (rc) return rc;
-    *took = true;
-    return 0;
+    return fft_shapes::dispatch<fft_shapes::LINE_C2C>([&](const line_shape &s) { return s.len == n && inner >= s.inner_min; }, [&](auto shape) {
+        return launch_linec2c<shape.row.len, shape.row.nch, shape.row.t, shape.row.h2>(ctx, in, out, nouter, inner, inverse, scale, gen, seed);
+    }, took);
 }
 
 // ------------------------------------------------------------------------------------
@@ -521,19 +518,9 @@ static int launch_liner2c(corahip_ctx *ctx, const double *in, double *spec, long
 int flat_r2c_ct(corahip_ctx *ctx, const double *in, double *spec, long nlines, int h, bool *took) {
     *took = false;
     if (flat_ct_off() || nlines < 1) return 0;
-    int rc;
-    if (h == 256) rc = launch_liner2c<256, 16, 512>(ctx, in, spec, nlines);
-    else if (h == 512) rc = launch_liner2c<512, 16, 512>(ctx, in, spec, nlines);
-    else if (h == 1024) rc = launch_liner2c<1024, 8, 512>(ctx, in, spec, nlines);
-    else if (h == 2048) rc = launch_liner2c<2048, 4, 512>(ctx, in, spec, nlines);
-    else if (h == 192) rc = launch_liner2c<192, 16, 512>(ctx, in, spec, nlines);
-    else if (h == 384) rc = launch_liner2c<384, 16, 512>(ctx, in, spec, nlines);
-    else if (h == 768) rc = launch_liner2c<768, 8, 512>(ctx, in, spec, nlines);
-    else if (h == 1536) rc = launch_liner2c<1536, 4, 512>(ctx, in, spec, nlines);
-    else return 0;
-    if (rc) return rc;
-    *took = true;
-    return 0;
+    return fft_shapes::dispatch<fft_shapes::LINE_REAL>([&](const line_shape &s) { return s.len == h; }, [&](auto shape) {
+        return launch_liner2c<shape.row.len, shape.row.nch, shape.row.t>(ctx, in, spec, nlines);
+    }, took);
 }
 
 template <int N, int NCH, int T>
@@ -551,19 +538,9 @@ static int launch_linec2r(corahip_ctx *ctx, const double *spec, double *out, lon
 int flat_c2r_ct(corahip_ctx *ctx, const double *spec, double *out, long nlines, int h, double scale, bool *took) {
     *took = false;
     if (flat_ct_off() || nlines < 1) return 0;
-    int rc;
-    if (h == 256) rc = launch_linec2r<256, 16, 256>(ctx, spec, out, nlines, scale);
-    else if (h == 512) rc = launch_linec2r<512, 16, 512>(ctx, spec, out, nlines, scale);
-    else if (h == 1024) rc = launch_linec2r<1024, 8, 512>(ctx, spec, out, nlines, scale);
-    else if (h == 2048) rc = launch_linec2r<2048, 4, 512>(ctx, spec, out, nlines, scale);
-    else if (h == 192) rc = launch_linec2r<192, 16, 256>(ctx, spec, out, nlines, scale);
-    else if (h == 384) rc = launch_linec2r<384, 16, 512>(ctx, spec, out, nlines, scale);
-    else if (h == 768) rc = launch_linec2r<768, 8, 512>(ctx, spec, out, nlines, scale);
-    else if (h == 1536) rc = launch_linec2r<1536, 4, 512>(ctx, spec, out, nlines, scale);
-    else return 0;
-    if (rc) return rc;
-    *took = true;
-    return 0;
+    return fft_shapes::dispatch<fft_shapes::LINE_REAL>([&](const line_shape &s) { return s.len == h; }, [&](auto shape) {
+        return launch_linec2r<shape.row.len, shape.row.nch, shape.row.t_c2r>(ctx, spec, out, nlines, scale);
+    }, took);
 }
 
 
@@ -990,17 +967,16 @@ lineblu_r2c_ct(const double2 *in, double2 *out, long nlines, int h, const double
 
 // the smallest scheduled length that holds the convolution of an n-point line (0: none)
 static int flat_blu_length(int n) {
-    static const int lens[] = {256, 320, 384, 512, 640, 768, 1024, 1280, 1536, 2048, 2560, 3072, 3584, 4096};
-    for (int P : lens)
-        if (P >= 2 * n - 1) return P;
+    for (const line_shape &s : fft_shapes::LINE_BLU)
+        if (s.len >= 2 * n - 1) return s.len;
     return 0;
 }
 template <int P>
 static int blu_filter_build(corahip_ctx *ctx, int n, const double2 *chirp, double2 *filt) {
-    constexpr int PK = 1;
+    constexpr int PK = 1, T = fft_shapes::LINE_BLU_FILTER_T;
     const size_t shm = sizeof(double2) * (fpc(P) + 1);
-    HIP_TRY(hipFuncSetAttribute((const void *)flat_blu_filter_kernel<P, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    flat_blu_filter_kernel<P, 256><<<1, 256, shm, ctx->stream>>>(n, chirp, filt);
+    HIP_TRY(hipFuncSetAttribute((const void *)flat_blu_filter_kernel<P, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    flat_blu_filter_kernel<P, T><<<1, T, shm, ctx->stream>>>(n, chirp, filt);
     LAUNCH_CHECK();
     return 0;
 }
@@ -1013,13 +989,9 @@ int flat_blu_plan(corahip_ctx *ctx, int n, const double2 *chirp, int *Pct, doubl
     if (!P || n < 17) return 0;
     double2 *f = nullptr;
     HIP_TRY(hipMalloc((void **)&f, sizeof(double2) * P));
-    int rc = -1;
-    switch (P) {
-#define BLU_CASE(PP) case PP: rc = blu_filter_build<PP>(ctx, n, chirp, f); break;
-        BLU_CASE(256) BLU_CASE(320) BLU_CASE(384) BLU_CASE(512) BLU_CASE(640) BLU_CASE(768) BLU_CASE(1024) BLU_CASE(1280)
-        BLU_CASE(1536) BLU_CASE(2048) BLU_CASE(2560) BLU_CASE(3072) BLU_CASE(3584) BLU_CASE(4096)
-#undef BLU_CASE
-    }
+    bool built;
+    const int rc = fft_shapes::dispatch<fft_shapes::LINE_BLU>([&](const line_shape &s) { return s.len == P; },
+                                                              [&](auto shape) { return blu_filter_build<shape.row.len>(ctx, n, chirp, f); }, &built);
     if (rc) {
         (void)hipFree(f);
         return rc;
@@ -1050,29 +1022,9 @@ int flat_blu_c2c_ct(corahip_ctx *ctx, const double *in, double *out, long nouter
                     uint64_t seed, int Pct, const double2 *chirp, const double2 *filt_ct, bool *took) {
     *took = false;
     if (flat_ct_off() || !Pct || !filt_ct || nouter < 1 || inner < 2) return 0;
-    int rc;
-#define BLU_ARGS ctx, in, out, nouter, inner, n, inverse, scale, gen, seed, chirp, filt_ct
-    switch (Pct) {
-    case 256: rc = launch_lineblu_c2c<256, 16, 512>(BLU_ARGS); break;
-    case 320: rc = launch_lineblu_c2c<320, 16, 512>(BLU_ARGS); break;
-    case 384: rc = launch_lineblu_c2c<384, 16, 512>(BLU_ARGS); break;
-    case 512: rc = launch_lineblu_c2c<512, 16, 512>(BLU_ARGS); break;
-    case 640: rc = launch_lineblu_c2c<640, 8, 512>(BLU_ARGS); break;
-    case 768: rc = launch_lineblu_c2c<768, 8, 512>(BLU_ARGS); break;
-    case 1024: rc = launch_lineblu_c2c<1024, 8, 512>(BLU_ARGS); break;
-    case 1280: rc = launch_lineblu_c2c<1280, 4, 512>(BLU_ARGS); break;
-    case 1536: rc = launch_lineblu_c2c<1536, 4, 512>(BLU_ARGS); break;
-    case 2048: rc = launch_lineblu_c2c<2048, 4, 512>(BLU_ARGS); break;
-    case 2560: rc = launch_lineblu_c2c<2560, 2, 512>(BLU_ARGS); break;
-    case 3072: rc = launch_lineblu_c2c<3072, 2, 512>(BLU_ARGS); break;
-    case 3584: rc = launch_lineblu_c2c<3584, 2, 512>(BLU_ARGS); break;
-    case 4096: rc = launch_lineblu_c2c<4096, 2, 512>(BLU_ARGS); break;
-    default: return 0;
-    }
-#undef BLU_ARGS
-    if (rc) return rc;
-    *took = true;
-    return 0;
+    return fft_shapes::dispatch<fft_shapes::LINE_BLU>([&](const line_shape &s) { return s.len == Pct; }, [&](auto shape) {
+        return launch_lineblu_c2c<shape.row.len, shape.row.nch, shape.row.t>(ctx, in, out, nouter, inner, n, inverse, scale, gen, seed, chirp, filt_ct);
+    }, took);
 }
 
 template <int P, int NCH, int T>
@@ -1099,27 +1051,7 @@ int flat_blu_real_ct(corahip_ctx *ctx, bool c2r, const double *in, double *out, 
                      const double2 *chirp, const double2 *filt_ct, const double2 *rtw, bool *took) {
     *took = false;
     if (flat_ct_off() || !Pct || !filt_ct || nlines < 1) return 0;
-    int rc;
-#define BLU_ARGS ctx, c2r, in, out, nlines, h, scale, chirp, filt_ct, rtw
-    switch (Pct) {
-    case 256: rc = launch_lineblu_real<256, 16, 512>(BLU_ARGS); break;
-    case 320: rc = launch_lineblu_real<320, 16, 512>(BLU_ARGS); break;
-    case 384: rc = launch_lineblu_real<384, 16, 512>(BLU_ARGS); break;
-    case 512: rc = launch_lineblu_real<512, 16, 512>(BLU_ARGS); break;
-    case 640: rc = launch_lineblu_real<640, 8, 512>(BLU_ARGS); break;
-    case 768: rc = launch_lineblu_real<768, 8, 512>(BLU_ARGS); break;
-    case 1024: rc = launch_lineblu_real<1024, 8, 512>(BLU_ARGS); break;
-    case 1280: rc = launch_lineblu_real<1280, 4, 512>(BLU_ARGS); break;
-    case 1536: rc = launch_lineblu_real<1536, 4, 512>(BLU_ARGS); break;
-    case 2048: rc = launch_lineblu_real<2048, 4, 512>(BLU_ARGS); break;
-    case 2560: rc = launch_lineblu_real<2560, 2, 512>(BLU_ARGS); break;
-    case 3072: rc = launch_lineblu_real<3072, 2, 512>(BLU_ARGS); break;
-    case 3584: rc = launch_lineblu_real<3584, 2, 512>(BLU_ARGS); break;
-    case 4096: rc = launch_lineblu_real<4096, 2, 512>(BLU_ARGS); break;
-    default: return 0;
-    }
-#undef BLU_ARGS
-    if (rc) return rc;
-    *took = true;
-    return 0;
+    return fft_shapes::dispatch<fft_shapes::LINE_BLU>([&](const line_shape &s) { return s.len == Pct; }, [&](auto shape) {
+        return launch_lineblu_real<shape.row.len, shape.row.nch, shape.row.t>(ctx, c2r, in, out, nlines, h, scale, chirp, filt_ct, rtw);
+    }, took);
 }

@@ -66,22 +66,26 @@ struct corahip_sht_plan {
     int32_t *d_blu_P = nullptr;                           // [nside]: 0 = power-of-two ring
     int64_t *d_blu_boff = nullptr, *d_blu_foff = nullptr; // offsets into chirp / filter arrays
     double2 *d_bchirp = nullptr, *d_bfilt = nullptr;
-    // second set of Bluestein filters for the rings whose 2 h - 1 also fits 3/4 of the power-of-two length (P3 = 1536 or
-    // 3072): used by the compile-time synthesis kernels only; everything else (analysis, run-time kernel) keeps blu_P
-    std::vector<int32_t> h_blu3_P;                        // [nside]: 0 = none
-    int64_t *d_blu3_foff = nullptr;
-    double2 *d_bfilt3 = nullptr;
+    // second set of Bluestein filters, stored in the order of the compile-time passes: for the rings whose compile-time
+    // kernel (synthesis or analysis) runs a length with filters of its own (fft_shapes.h, RING_BLU rows marked `own`: a
+    // 3 / 5 / 7 * 2^k length that still holds 2 h - 1, or 8192, whose pass order differs from the generic one).  The
+    // run-time kernels, and the compile-time kernels of the other lengths, keep blu_P and the first set.
+    std::vector<int32_t> h_ctfilt_len;                    // [nside]: 0 = none
+    int64_t *d_ctfilt_off = nullptr;
+    double2 *d_ctfilt = nullptr;
     // fold phases of the cap rings for the compile-time Bluestein kernels: e^{i t phi0(ring)}, t < 512, and the steps
     // e^{i 256 phi0}, e^{i 512 phi0}, by north-cap ring number i - 1
     double2 *d_foldph = nullptr, *d_foldstep = nullptr;
     int max_fft_len = 0;                                  // largest LDS FFT buffer (complex elems)
     // K5 launch classes: rings grouped by transform kind/length so each launch sizes its LDS
     struct ring_class {
-        int P = 0;        // Bluestein length, 0 = direct power-of-two transform
-        int N = 0;        // direct classes: the half length h of the rings (all equal), 0 = mixed (run-time length)
-        int P3 = 0;       // Bluestein length the compile-time kernels take for the class, filters in d_bfilt3 (0 = none):
-                          // 3 * 2^k (1536, 3072, 6144) where it holds 2 h - 1, or P = 8192 in the compile-time pass order
-        int nch = 4;      // channels transformed together per workgroup
+        bool blu = false; // Bluestein (cap rings whose length is no power of two); false = direct power-of-two transform
+        int len = 0;      // what the run-time kernel runs: Bluestein length P (a power of two, filters in d_bfilt) / direct:
+                          // the half length h of the rings if they share one (the belt), 0 = mixed (power-of-two cap rings)
+        int ct_len = 0;   // length of the compile-time kernel that takes the class (fft_shapes.h), 0 = none
+        bool ct_own = false;   // that kernel reads the second filter set (d_ctfilt); then ct_len may differ from len
+        int length() const { return ct_len ? ct_len : len; }   // of the transform the synthesis runs
+        int nch = 4;      // channels transformed together per workgroup (the compile-time kernel's NCH where there is one)
         int threads = 0;  // workgroup size (0: K5_THREADS)
         int bstride = 0;  // complex elements per channel buffer in LDS
         int count = 0;
@@ -545,8 +549,8 @@ double sht_ringfft_item_weight(const corahip_sht_plan::ring_class &c);
 // every launch of a ticketed class
 #define K5_NTICKETS 8
 int sht_k5_tickets(corahip_ctx *ctx, hipStream_t stream);
-// plan time: filters of the 3 * 2^k Bluestein lengths (fills p->d_bfilt3; h_blu3_P / d_blu3_foff / d_bchirp must be set)
-int sht_blu3_tables(corahip_ctx *ctx, corahip_sht_plan *p, int64_t total);
+// plan time: the second filter set (fills p->d_ctfilt; h_ctfilt_len / d_ctfilt_off / d_bchirp must be set)
+int sht_ctfilt_tables(corahip_ctx *ctx, corahip_sht_plan *p);
 // creates ctx->stream2 and the fork / join events on first use
 int sht_second_stream(corahip_ctx *ctx);
 // Guard of the per-class launch loops of sht_ringfft / sht_ringana, which switch ctx->stream per launch: puts the
@@ -557,6 +561,23 @@ struct StreamRestore {
     corahip_ctx *c;
     hipStream_t s;
     bool forked = false;
+    // the second stream starts behind everything the caller's stream holds so far
+    int fork() {
+        const int rc = sht_second_stream(c);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(c->ev_fork, s));
+        HIP_TRY(hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
+        forked = true;
+        return 0;
+    }
+    // the caller's stream is current again and waits for the second one (on an error here the destructor tries again)
+    int join() {
+        c->stream = s;
+        HIP_TRY(hipEventRecord(c->ev_join, c->stream2));
+        HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
+        forked = false;
+        return 0;
+    }
     ~StreamRestore() {
         c->stream = s;
         if (forked && (hipEventRecord(c->ev_join, c->stream2) != hipSuccess || hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess))

@@ -2,6 +2,9 @@
 // polar seed table (first contributing l and the two recurrence values there), per-(m, ring block) first-l table,
 // per-ring m cut-off, twiddles, Bluestein chirps / filters and the K5 launch classes.  See sht_internal.h.
 #include "sht_internal.h"
+#include "fft_shapes.h"
+
+#include <array>
 
 // ------------------------------------------------------------------------------------
 // plan-time kernels
@@ -478,6 +481,13 @@ int sht_k4_segseed(corahip_ctx *ctx, const corahip_sht_plan *cp, int rt, const d
     return 0;
 }
 
+// the Bluestein length of the run-time kernels for a cap ring of half length h: the power of two that holds 2 h - 1
+static int blu_pow2_length(int h) {
+    int P = 1;
+    while (P < 2 * h - 1) P <<= 1;
+    return P;
+}
+
 extern "C" {
 
 int corahip_sht_plan_destroy(corahip_ctx *ctx, corahip_sht_plan *p) {
@@ -504,8 +514,8 @@ int corahip_sht_plan_destroy(corahip_ctx *ctx, corahip_sht_plan *p) {
     (void)hipFree(p->d_blu_P);
     (void)hipFree(p->d_blu_boff);
     (void)hipFree(p->d_blu_foff);
-    (void)hipFree(p->d_blu3_foff);
-    (void)hipFree(p->d_bfilt3);
+    (void)hipFree(p->d_ctfilt_off);
+    (void)hipFree(p->d_ctfilt);
     (void)hipFree(p->d_bchirp);
     (void)hipFree(p->d_bfilt);
     (void)hipFree(p->d_foldph);
@@ -718,8 +728,7 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
         for (int i = 1; i < nside; i++) {
             const int h = 2 * i;
             if (is_pow2(h)) continue;
-            int P = 1;
-            while (P < 2 * h - 1) P <<= 1;
+            const int P = blu_pow2_length(h);
             bp[i - 1] = P;
             bo[i - 1] = nb;
             fo[i - 1] = nf;
@@ -749,73 +758,68 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
         fold_phase_kernel<<<nside - 1, 512, 0, s>>>(p->d_phi0, p->d_foldph, p->d_foldstep);
         LAUNCH_CHECK();
     }
-    // 3 * 2^k Bluestein lengths for the compile-time synthesis kernels: 3 P / 4 where it still holds 2 h - 1
+    // the second filter set: the rings whose compile-time kernel runs a length with filters of its own
     {
-        p->h_blu3_P.assign(nside, 0);
-        std::vector<int64_t> fo3(nside, 0);
-        int64_t nf3 = 0;
+        p->h_ctfilt_len.assign(nside, 0);
+        std::vector<int64_t> fo(nside, 0);
+        int64_t nf = 0;
         for (int i = 1; i < nside; i++) {
             const int h = 2 * i;
             if (is_pow2(h)) continue;
-            int P = 1;
-            while (P < 2 * h - 1) P <<= 1;
-            // the length the compile-time kernels take for this ring, with a filter in THEIR storage order: 3 P / 4 where
-            // it still holds 2 h - 1, and P = 8192 itself (their 16 x 16 x 32 schedule differs from the generic passes)
-            const int P3 = 3 * (P / 4);
-            int alt = 0;
-            if (P == 4096 && 2560 >= 2 * h - 1) alt = 2560;          // 5 * 2^9
-            else if ((P3 == 1536 || P3 == 3072 || P3 == 6144) && P3 >= 2 * h - 1) alt = P3;
-            else if (P == 4096 && 3584 >= 2 * h - 1) alt = 3584;     // 7 * 2^9
-            else if (P == 8192) alt = P;
-            if (alt) {
-                p->h_blu3_P[i - 1] = alt;
-                fo3[i - 1] = nf3;
-                nf3 += alt;
+            const int own = fft_shapes::ring_own_length(h, blu_pow2_length(h));
+            if (own) {
+                p->h_ctfilt_len[i - 1] = own;
+                fo[i - 1] = nf;
+                nf += own;
             }
         }
-        if ((rc = dev_upload(&p->d_blu3_foff, fo3, s))) return rc;
-        HIP_TRY(hipMalloc((void **)&p->d_bfilt3, sizeof(double2) * std::max<int64_t>(1, nf3)));
-        if (nf3 && (rc = sht_blu3_tables(ctx, p, nf3))) return rc;
+        if ((rc = dev_upload(&p->d_ctfilt_off, fo, s))) return rc;
+        HIP_TRY(hipMalloc((void **)&p->d_ctfilt, sizeof(double2) * std::max<int64_t>(1, nf)));
+        if (nf && (rc = sht_ctfilt_tables(ctx, p))) return rc;
     }
     // K5 ring classes
     {
-        // key: Bluestein length P, or -h for the belt (direct transform of the one length 2 nside: its own class so
-        // that the compile-time kernel can take it); the few power-of-two cap rings share the run-time class 0
-        std::map<int, std::vector<int32_t>> by_len;
+        // One class per (kind, run-time length, own compile-time length).  The classes are launched in the order of this
+        // key, alternating two streams, and cost ties of the scheduler fall back on it, so it is part of the behaviour:
+        // the belt (direct transform of the one length 2 nside: its own class so that the compile-time kernel can take
+        // it), the few power-of-two cap rings (one run-time class), then the Bluestein lengths P ascending; within one P
+        // the rings without a length of their own, then 3/4 P, P itself in the compile-time order, 5/8 P, 7/8 P.
+        static const int eighths_rank[9] = {0, 0, 0, 0, 0, 3, 1, 4, 2};
+        std::map<std::array<int, 3>, std::vector<int32_t>> by_key;     // (P or -1 belt / 0 mixed, rank, own length)
         for (int r = 0; r < nring; r++) {
             const int i = r + 1;
             int icap = 0;
             if (i < nside) icap = i;
             else if (i > 3 * nside) icap = 4 * nside - i;
-            int P = icap ? 0 : -2 * nside;
-            if (icap) {
-                const int h = 2 * icap;
-                if (!is_pow2(h)) {
-                    P = 1;
-                    while (P < 2 * h - 1) P <<= 1;
-                    // rings with a compile-time length of their own (3 P / 4: code 1; P in the compile-time order: 2;
-                    // 5 P / 8: 3; 7 P / 8: 4)
-                    const int alt = p->h_blu3_P[icap - 1];
-                    P = 8 * P + (alt == 0 ? 0 : (alt == P ? 2 : (alt == 3 * (P / 4) ? 1 : (alt == 5 * (P / 8) ? 3 : 4))));
-                }
+            std::array<int, 3> key = {icap ? 0 : -1, 0, 0};
+            if (icap && !is_pow2(2 * icap)) {
+                const int P = blu_pow2_length(2 * icap), own = p->h_ctfilt_len[icap - 1];
+                key = {P, eighths_rank[own / (P / 8)], own};
             }
-            by_len[P].push_back(r);
+            by_key[key].push_back(r);
         }
         const size_t lds_budget = 160 * 1024;
-        for (auto &kv : by_len) {
+        for (auto &kv : by_key) {
             corahip_sht_plan::ring_class c;
-            c.P = kv.first > 0 ? kv.first / 8 : 0;
-            {
-                const int code = kv.first > 0 ? (kv.first & 7) : 0;
-                c.P3 = code == 1 ? 3 * (c.P / 4) : (code == 2 ? c.P : (code == 3 ? 5 * (c.P / 8) : (code == 4 ? 7 * (c.P / 8) : 0)));
-            }
-            c.N = kv.first < 0 ? -kv.first : 0;
-            c.bstride = fpad_len(c.P ? c.P : 2 * nside + 1) + K5_CH_SKEW;
+            const int own = kv.first[2];
+            c.blu = kv.first[0] > 0;
+            c.len = c.blu ? kv.first[0] : (kv.first[0] < 0 ? 2 * nside : 0);
+            const fft_shapes::ring_shape *ct = c.blu ? fft_shapes::find(fft_shapes::RING_BLU, own ? own : c.len)
+                                                     : fft_shapes::find(fft_shapes::RING_DIRECT, c.len);
+            c.ct_len = ct ? ct->len : 0;
+            c.ct_own = own != 0;
+            c.bstride = fpad_len(c.blu ? c.len : 2 * nside + 1) + K5_CH_SKEW;
             c.nch = 4;
             while (c.nch > 1 && (size_t)c.nch * c.bstride * sizeof(double2) > lds_budget) c.nch >>= 1;
             if ((size_t)c.nch * c.bstride * sizeof(double2) > lds_budget) {
                 corahip_set_error("nside %d: ring FFT of length %d does not fit in LDS", nside, c.bstride);
                 return CORAHIP_ENOMEM;
+            }
+            // the scheduler costs and aligns a class by c.nch, the compile-time kernel runs its own NCH: one number
+            if (ct && ct->nch != c.nch) {
+                corahip_set_error("ring FFT length %d: %d channels per item in the shape table, %d by the LDS budget", ct->len,
+                                  ct->nch, c.nch);
+                return CORAHIP_ESTATE;
             }
             // (measured and rejected for the P = 4096 class: one channel per 4-wave workgroup, two workgroups per CU,
             //  so that LDS and FP64 phases of different workgroups overlap: 12.8 -> 13.6 ms, the cells are read 4x)
@@ -823,7 +827,7 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             // workgroups of 64 / 128 threads instead of 512: a 512-point transform of four channels has 128 radix-16
             // butterflies per pass - most of a 512-thread workgroup only attended the barriers (P = 512 0.41 -> 0.19 ms,
             // P = 256 0.19 -> 0.05 ms, K5 -0.5 ms at cfg 3).
-            if (c.P > 0 && c.P <= 512) c.threads = c.P >= 512 ? 128 : 64;
+            if (c.blu && c.len <= 512) c.threads = c.len >= 512 ? 128 : 64;
             c.count = (int)kv.second.size();
             c.h_list = kv.second;
             if ((rc = dev_upload(&c.d_list, kv.second, s))) return rc;
@@ -851,7 +855,7 @@ int corahip_sht_plan_rings(const corahip_sht_plan *p, int64_t *host_start, int32
 int corahip_sht_plan_ring_classes(const corahip_sht_plan *p, int32_t *host_len) {
     ARG_CHECK(p != nullptr && host_len != nullptr);
     for (const auto &c : p->classes)
-        for (int32_t r : c.h_list) host_len[r] = c.P3 ? c.P3 : c.P;   // (the 3 * 2^k kernels take the classes that admit them)
+        for (int32_t r : c.h_list) host_len[r] = c.blu ? c.length() : 0;
     return 0;
 }
 

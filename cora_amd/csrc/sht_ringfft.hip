@@ -451,6 +451,32 @@ ringana_kernel(const int32_t *__restrict__ ring_list, int nlist, int nside, int 
         }
     }
 }
+// CORAHIP_K5_TIMES (diagnostics): the time of one class launch on `stream`, event to event, on stderr
+namespace {
+struct ClassTimer {
+    bool on;
+    hipStream_t stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ClassTimer(bool on_, hipStream_t stream_) : on(on_), stream(stream_) {
+        if (!on) return;
+        (void)hipEventCreate(&e0);
+        (void)hipEventCreate(&e1);
+        (void)hipEventRecord(e0, stream);
+    }
+    void report(const char *kernel, const corahip_sht_plan::ring_class &c, int cus) {
+        if (!on) return;
+        float ms = 0.f;
+        (void)hipEventRecord(e1, stream);
+        (void)hipEventSynchronize(e1);
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        fprintf(stderr, "%s class P=%d (length %d) nch=%d rings=%d: %.3f ms on %d CUs\n", kernel, c.blu ? c.len : 0, c.length(), c.nch,
+                c.count, ms, cus);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+};
+}  // namespace
+
 // One class of K5 on ctx->stream, its persistent grid limited to cu_limit CUs
 static int ringfft_launch_class(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c,
                                 const double *inter, int G, int nnu_valid, double *maps, int cu_limit) {
@@ -471,7 +497,7 @@ static int ringfft_launch_class(corahip_ctx *ctx, const corahip_sht_plan *p, con
                                                          p->d_nphi, p->d_start, p->d_phi0, inter, maps, p->d_tw, \
                                                          p->pmax, p->d_blu_P, p->d_blu_boff, p->d_blu_foff,      \
                                                          p->d_bchirp, p->d_bfilt, c.bstride, p->d_mcut)
-    if (c.P == 0) {
+    if (!c.blu) {
         if (c.nch == 4) { RINGFFT_LAUNCH(4, false); }
         else if (c.nch == 2) { RINGFFT_LAUNCH(2, false); }
         else { RINGFFT_LAUNCH(1, false); }
@@ -546,24 +572,16 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
             }
         }
         if (W > 0) {
-            int rc2 = sht_second_stream(ctx);
-            if (rc2) return rc2;
-            HIP_TRY(hipEventRecord(ctx->ev_fork, main_stream));
-            HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-            restore.forked = true;
-            int rc = ringfft_launch_class(ctx, p, *belt, inter, G, nnu_valid, maps, W);
+            int rc = restore.fork();
             if (rc) return rc;
+            if ((rc = ringfft_launch_class(ctx, p, *belt, inter, G, nnu_valid, maps, W))) return rc;
             ctx->stream = ctx->stream2;
             std::stable_sort(side.begin(), side.end(), [](const auto &a, const auto &b) { return a.first > b.first; });   // longest first
             for (const auto &sc : side)
                 if ((rc = ringfft_launch_class(ctx, p, *sc.second, inter, G, nnu_valid, maps, ncu - W))) return rc;
             // helper: the belt kernel again, on the CUs the caps leave - it exits at once if no tickets are left
             if ((rc = ringfft_launch_class(ctx, p, *belt, inter, G, nnu_valid, maps, ncu - W))) return rc;
-            ctx->stream = main_stream;
-            HIP_TRY(hipEventRecord(ctx->ev_join, ctx->stream2));
-            HIP_TRY(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
-            restore.forked = false;                 // (joined here: nothing left for the guard)
-            return 0;
+            return restore.join();                  // (joined here: nothing left for the guard)
         }
 
         // ---- the alternating schedule: every class is a persistent grid that fills the chip, launched on two streams in
@@ -571,52 +589,28 @@ int sht_ringfft(corahip_ctx *ctx, const corahip_sht_plan *p, const double *inter
         // class start on the CUs the finishing one frees (12 launches, 0.1-0.3 ms of tail each on one stream).  The
         // per-class timing switch keeps everything on the context's stream (and, with CORAHIP_K5_BELT_WGS = n, runs
         // the belt on n CUs: the reduced-width figure the weight table wants).
-        if (two) {
-            int rc2 = sht_second_stream(ctx);
-            if (rc2) return rc2;
-            HIP_TRY(hipEventRecord(ctx->ev_fork, main_stream));
-            HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-            restore.forked = true;
-        }
+        int rc = two ? restore.fork() : 0;
+        if (rc) return rc;
         int launch_no = 0;
         for (const auto &c : p->classes) {
             if (two) ctx->stream = (launch_no++ & 1) ? ctx->stream2 : main_stream;   // (restored below; every launch of the loop uses ctx->stream)
-            hipEvent_t ce0 = nullptr, ce1 = nullptr;
-            if (class_times) {
-                (void)hipEventCreate(&ce0);
-                (void)hipEventCreate(&ce1);
-                (void)hipEventRecord(ce0, ctx->stream);
-            }
+            ClassTimer timer(class_times, ctx->stream);
             const int cus = (class_times && sw > 0 && &c == belt) ? std::min(sw, ncu) : ncu;
-            const int rc = ringfft_launch_class(ctx, p, c, inter, G, nnu_valid, maps, cus);
-            if (rc) return rc;   // (StreamRestore puts the caller's stream back)
-            if (class_times) {
-                float ms = 0.f;
-                (void)hipEventRecord(ce1, ctx->stream);
-                (void)hipEventSynchronize(ce1);
-                (void)hipEventElapsedTime(&ms, ce0, ce1);
-                fprintf(stderr, "K5 class P=%d (length %d) rings=%d: %.3f ms on %d CUs\n", c.P, c.P3 ? c.P3 : (c.P ? c.P : c.N), c.count, ms, cus);
-                (void)hipEventDestroy(ce0);
-                (void)hipEventDestroy(ce1);
-            }
+            if ((rc = ringfft_launch_class(ctx, p, c, inter, G, nnu_valid, maps, cus))) return rc;   // (StreamRestore puts the caller's stream back)
+            timer.report("K5", c, cus);
 #if K5_STAMPS
             {
                 unsigned long long hs[8];
                 HIP_TRY(hipStreamSynchronize(ctx->stream));
                 HIP_TRY(hipMemcpyFromSymbol(hs, HIP_SYMBOL(g_k5_stamps), sizeof(hs)));
-                fprintf(stderr, "K5 class P=%d nch=%d rings=%d: pre %llu zero %llu fold %llu z %llu fft %llu out %llu mid %llu dit %llu\n", c.P,
-                        c.nch, c.count, hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7]);
+                fprintf(stderr, "K5 class P=%d nch=%d rings=%d: pre %llu zero %llu fold %llu z %llu fft %llu out %llu mid %llu dit %llu\n",
+                        c.blu ? c.len : 0, c.nch, c.count, hs[0], hs[1], hs[2], hs[3], hs[4], hs[5], hs[6], hs[7]);
                 unsigned long long z8[8] = {0};
                 HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_k5_stamps), z8, sizeof(z8)));
             }
 #endif
         }
-        ctx->stream = main_stream;
-        if (two) {
-            HIP_TRY(hipEventRecord(ctx->ev_join, ctx->stream2));
-            HIP_TRY(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
-            restore.forked = false;                 // (joined here: nothing left for the guard)
-        }
+        if (two) return restore.join();             // (joined here: nothing left for the guard)
     }
     return 0;
 }
@@ -633,22 +627,12 @@ int sht_ringana(corahip_ctx *ctx, const corahip_sht_plan *p, const double *maps,
     const bool two = !class_times && p->classes.size() > 1;
     hipStream_t const main_stream = ctx->stream;
     StreamRestore restore{ctx, main_stream};
-    if (two) {
-        int rc2 = sht_second_stream(ctx);
-        if (rc2) return rc2;
-        HIP_TRY(hipEventRecord(ctx->ev_fork, main_stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        restore.forked = true;
-    }
+    const int rc = two ? restore.fork() : 0;
+    if (rc) return rc;
     int launch_no = 0;
     for (const auto &c : p->classes) {
         if (two) ctx->stream = (launch_no++ & 1) ? ctx->stream2 : main_stream;
-        hipEvent_t ce0 = nullptr, ce1 = nullptr;
-        if (class_times) {
-            (void)hipEventCreate(&ce0);
-            (void)hipEventCreate(&ce1);
-            (void)hipEventRecord(ce0, ctx->stream);
-        }
+        ClassTimer timer(class_times, ctx->stream);
         bool took = false;   // compile-time kernel for this class?
         const int rct = sht_ringana_ct(ctx, p, c, maps, nnu, nnu_pad8, ring_w, G, inter, &took);
         if (rct) return rct;
@@ -668,21 +652,7 @@ int sht_ringana(corahip_ctx *ctx, const corahip_sht_plan *p, const double *maps,
         else { RINGANA_LAUNCH(1); }
 #undef RINGANA_LAUNCH
         LAUNCH_CHECK();
-        if (class_times) {
-            float ms = 0.f;
-            (void)hipEventRecord(ce1, ctx->stream);
-            (void)hipEventSynchronize(ce1);
-            (void)hipEventElapsedTime(&ms, ce0, ce1);
-            fprintf(stderr, "K5^T class P=%d (length %d) nch=%d rings=%d: %.3f ms\n", c.P, c.P3 ? c.P3 : (c.P ? c.P : c.N), c.nch, c.count, ms);
-            (void)hipEventDestroy(ce0);
-            (void)hipEventDestroy(ce1);
-        }
+        timer.report("K5^T", c, ctx->num_cu);
     }
-    ctx->stream = main_stream;
-    if (two) {
-        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->stream2));
-        HIP_TRY(hipStreamWaitEvent(main_stream, ctx->ev_join, 0));
-        restore.forked = false;
-    }
-    return 0;
+    return two ? restore.join() : 0;
 }

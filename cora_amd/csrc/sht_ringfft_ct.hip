@@ -42,6 +42,9 @@ __device__ unsigned long long g_ct_stamps[12];
 #endif
 
 #include "fft_ct.h"
+#include "fft_shapes.h"
+static_assert(fft_shapes::scheduled<Sch, fft_shapes::RING_DIRECT>() && fft_shapes::scheduled<Sch, fft_shapes::RING_BLU>(),
+              "every ring shape has its three-pass schedule");
 
 // ---- register prefetch of the F_m cells of one (ring, NCH channels) item ---------------------------------------
 template <int NCH>
@@ -801,14 +804,12 @@ static int launch_direct(corahip_ctx *ctx, hipStream_t stream, const corahip_sht
 }
 template <int P, int NCH, int MC, int T>
 static int launch_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_plan *p,
-                      const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps, int cu_limit,
-                      const int64_t *d_foff = nullptr, const double2 *d_filt = nullptr) {
-    if (!d_foff) {
-        d_foff = p->d_blu_foff;
-        d_filt = p->d_bfilt;
-    }
+                      const corahip_sht_plan::ring_class &c, const double *inter, int G, int nnu, double *maps, int cu_limit) {
+    const int64_t *d_foff = c.ct_own ? p->d_ctfilt_off : p->d_blu_foff;
+    const double2 *d_filt = c.ct_own ? p->d_ctfilt : p->d_bfilt;
     constexpr int PK = K5_PK_BLU;
     constexpr int BS = fpc(P) + K5_CH_SKEW;
+    static_assert(sizeof(double2) * (size_t)NCH * BS <= 160 * 1024, "channel buffers fit the LDS");
     const long nitems = (long)c.count * ((nnu + NCH - 1) / NCH);
     const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 0, nitems, cu_limit);
     HIP_TRY(hipFuncSetAttribute((const void *)ringfft_blu_ct<P, NCH, MC, T>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -833,36 +834,17 @@ static int launch_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_pl
 }
 
 // *took = true if the class was launched here, false if the generic kernel has to take it; the return value is the
-// error status only (0 = OK, CORAHIP_E* < 0 or a positive hipError_t): hipErrorInvalidValue is 1, so "launched" must
-// never share the int with the status
+// error status only (0 = OK, CORAHIP_E* < 0 or a positive hipError_t): see fft_shapes::dispatch
 int sht_ringfft_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c, const double *inter,
                    int G, int nnu, double *maps, int cu_limit, bool *took) {
-    *took = false;
-    int rc = -1;
-    hipStream_t st = ctx->stream;
-    if (c.P == 0) {
-        if (c.N == 2048) rc = launch_direct<2048, 4, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
-        else if (c.N == 4096) rc = launch_direct<4096, 2, 8, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
-        else return 0;
-    } else {
-        // P3 = 8192 / 6144: one channel fills the LDS.  Measured at the cfg-5 rank share (128 channels; the generic kernel
-        // took 30.6 ms for the two classes): 512 threads (two waves per SIMD, but the radix-32 / 24 butterflies then spill:
-        // 268 / 72 bytes) 16.5 / 10.1 ms, 256 threads (one wave per SIMD, no spill) 13.8 / 10.8 ms for P = 8192 / 6144:
-        // each takes the faster form.
-        if (c.P3 == 8192) rc = launch_blu<8192, 1, 16, 256>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 6144) rc = launch_blu<6144, 1, 8, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 2560) rc = launch_blu<2560, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 3584) rc = launch_blu<3584, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 3072) rc = launch_blu<3072, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P3 == 1536) rc = launch_blu<1536, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit, p->d_blu3_foff, p->d_bfilt3);
-        else if (c.P == 4096) rc = launch_blu<4096, 2, 4, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
-        else if (c.P == 2048) rc = launch_blu<2048, 4, 2, 512>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);
-        else if (c.P == 1024) rc = launch_blu<1024, 4, 2, 256>(ctx, st, p, c, inter, G, nnu, maps, cu_limit);   // (256 threads, two workgroups per CU: 0.61 -> 0.54 ms)
-        else return 0;
-    }
-    if (rc) return rc;
-    *took = true;
-    return 0;
+    const auto len_is = [&](const fft_shapes::ring_shape &s) { return s.len == c.ct_len; };
+    if (!c.blu)
+        return fft_shapes::dispatch<fft_shapes::RING_DIRECT>(len_is, [&](auto shape) {
+            return launch_direct<shape.row.len, shape.row.nch, shape.row.mc, shape.row.t>(ctx, ctx->stream, p, c, inter, G, nnu, maps, cu_limit);
+        }, took);
+    return fft_shapes::dispatch<fft_shapes::RING_BLU>(len_is, [&](auto shape) {
+        return launch_blu<shape.row.len, shape.row.nch, shape.row.mc, shape.row.t>(ctx, ctx->stream, p, c, inter, G, nnu, maps, cu_limit);
+    }, took);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1065,6 +1047,7 @@ static int launch_ana_direct(corahip_ctx *ctx, hipStream_t stream, const corahip
                              const double *maps, int nvalid, int nnu_pad, const double *ring_w, int G, double *inter) {
     constexpr int PK = K5_PK_DIRECT;
     constexpr int BS = fpc(N) + 1 + K5_CH_SKEW;
+    static_assert(sizeof(double2) * (size_t)NCH * BS <= 160 * 1024, "channel buffers fit the LDS");
     const long nitems = (long)c.count * ((nnu_pad + NCH - 1) / NCH);
     const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 0, nitems, ctx->num_cu);
     HIP_TRY(hipFuncSetAttribute((const void *)ringana_direct_ct<N, NCH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1075,15 +1058,16 @@ static int launch_ana_direct(corahip_ctx *ctx, hipStream_t stream, const corahip
 }
 template <int P, int NCH, int T>
 static int launch_ana_blu(corahip_ctx *ctx, hipStream_t stream, const corahip_sht_plan *p, const corahip_sht_plan::ring_class &c,
-                          const double *maps, int nvalid, int nnu_pad, const double *ring_w, int G, double *inter, bool blu3) {
+                          const double *maps, int nvalid, int nnu_pad, const double *ring_w, int G, double *inter) {
     constexpr int PK = K5_PK_BLU;
     constexpr int BS = fpc(P) + K5_CH_SKEW;
+    static_assert(sizeof(double2) * (size_t)NCH * BS <= 160 * 1024, "channel buffers fit the LDS");
     const long nitems = (long)c.count * ((nnu_pad + NCH - 1) / NCH);
     const auto [shm, grid] = ct_launch_geom(NCH, BS, 0, 0, nitems, ctx->num_cu);
     HIP_TRY(hipFuncSetAttribute((const void *)ringana_blu_ct<P, NCH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     ringana_blu_ct<P, NCH, T><<<grid, T, shm, stream>>>(c.d_list, c.count, p->nside, p->lmax, G, nnu_pad, nvalid, p->npix, p->d_nphi,
-                                                        p->d_start, maps, inter, p->d_blu_boff, blu3 ? p->d_blu3_foff : p->d_blu_foff,
-                                                        p->d_bchirp, blu3 ? p->d_bfilt3 : p->d_bfilt, p->d_mcut, p->d_foldph,
+                                                        p->d_start, maps, inter, p->d_blu_boff, c.ct_own ? p->d_ctfilt_off : p->d_blu_foff,
+                                                        p->d_bchirp, c.ct_own ? p->d_ctfilt : p->d_bfilt, p->d_mcut, p->d_foldph,
                                                         p->d_foldstep, ring_w);
     LAUNCH_CHECK();
     return 0;
@@ -1092,28 +1076,21 @@ int sht_ringana_ct(corahip_ctx *ctx, const corahip_sht_plan *p, const corahip_sh
                    int nnu_pad, const double *ring_w, int G, double *inter, bool *took) {
     *took = false;
     if (nvalid < 1) return 0;
-    hipStream_t st = ctx->stream;
-    int rc;
-#define ANA_ARGS ctx, st, p, c, maps, nvalid, nnu_pad, ring_w, G, inter
+    const auto len_is = [&](const fft_shapes::ring_shape &s) { return s.len == c.ct_len; };
+    if (c.blu)
+        return fft_shapes::dispatch<fft_shapes::RING_BLU, fft_shapes::has_analysis>(len_is, [&](auto shape) {
+            return launch_ana_blu<shape.row.len, shape.row.nch, shape.row.ana_t>(ctx, ctx->stream, p, c, maps, nvalid, nnu_pad, ring_w, G, inter);
+        }, took);
     // (the direct kernels store m <= N only: with lmax > N - the aliased lmax = 3 nside - 1 - the belt's cells
     //  N < m < mcut hold aliases they do not write, and the class goes to the run-time ringana_kernel, which folds them)
-    if (c.P == 0 && c.N == 2048 && p->lmax <= c.N) rc = launch_ana_direct<2048, 4, 512>(ANA_ARGS);
-    else if (c.P == 0 && c.N == 4096 && p->lmax <= c.N) rc = launch_ana_direct<4096, 2, 512>(ANA_ARGS);
-    else if (c.P3 == 2560) rc = launch_ana_blu<2560, 2, 512>(ANA_ARGS, true);
-    else if (c.P3 == 3584) rc = launch_ana_blu<3584, 2, 512>(ANA_ARGS, true);
-    else if (c.P3 == 3072) rc = launch_ana_blu<3072, 2, 512>(ANA_ARGS, true);
-    else if (c.P3 == 1536) rc = launch_ana_blu<1536, 4, 512>(ANA_ARGS, true);
-    else if (c.P == 4096 && c.P3 <= 4096) rc = launch_ana_blu<4096, 2, 512>(ANA_ARGS, false);
-    else if (c.P == 2048) rc = launch_ana_blu<2048, 4, 512>(ANA_ARGS, false);
-    else if (c.P == 1024) rc = launch_ana_blu<1024, 4, 256>(ANA_ARGS, false);
-    else return 0;
-#undef ANA_ARGS
-    if (rc) return rc;
-    *took = true;
-    return 0;
+    if (p->lmax > c.len) return 0;
+    return fft_shapes::dispatch<fft_shapes::RING_DIRECT, fft_shapes::has_analysis>(len_is, [&](auto shape) {
+        return launch_ana_direct<shape.row.len, shape.row.nch, shape.row.ana_t>(ctx, ctx->stream, p, c, maps, nvalid, nnu_pad, ring_w, G, inter);
+    }, took);
 }
 
-bool sht_ringfft_ticketed(const corahip_sht_plan::ring_class &c) { return c.P == 0 && (c.N == 2048 || c.N == 4096); }
+// (both belt kernels draw their items from the context's tickets)
+bool sht_ringfft_ticketed(const corahip_sht_plan::ring_class &c) { return !c.blu && c.ct_len != 0; }
 
 // CU microseconds per item of each kernel instantiation, for the split of the CUs between the belt and the cap classes
 // (sht_ringfft).  Measured on one MI355X with the per-class diagnostic (CORAHIP_K5_TIMES=1, tools/k5_probe.py): time of
@@ -1122,19 +1099,10 @@ bool sht_ringfft_ticketed(const corahip_sht_plan::ring_class &c) { return c.P ==
 // (CORAHIP_K5_BELT_WGS=96 beside CORAHIP_K5_TIMES: 13.55 / 34.65 ms), where HBM does not limit it; on the whole chip
 // an item costs 11.8 / 14.2.  HISTORY.md ("K5: belt and cap classes side by side") has the measurement.
 double sht_ringfft_item_weight(const corahip_sht_plan::ring_class &c) {
-    struct W { int len; double us; };
-    static const W direct[] = {{2048, 9.9}, {4096, 12.7}};
-    static const W blu[] = {{8192, 26.1}, {6144, 20.5}, {4096, 15.0}, {3584, 14.3}, {3072, 13.3}, {2560, 12.4},
-                            {2048, 12.6}, {1536, 10.6}, {1024, 6.8}};
-    if (c.P == 0) {
-        for (const W &w : direct)
-            if (w.len == c.N) return w.us;
-        return 13.0;      // the power-of-two cap rings (run-time kernel, a few items)
-    }
-    const int len = c.P3 ? c.P3 : c.P;
-    for (const W &w : blu)
-        if (w.len == len) return w.us;
-    return len > 4096 ? 26.1 * len / 8192 : 5.7;   // run-time kernel: lengths <= 512 at the plans in use
+    if (const fft_shapes::ring_shape *s = c.blu ? fft_shapes::find(fft_shapes::RING_BLU, c.ct_len) : fft_shapes::find(fft_shapes::RING_DIRECT, c.ct_len))
+        return s->us;
+    if (!c.blu) return 13.0;      // the power-of-two cap rings (run-time kernel, a few items)
+    return c.len > 4096 ? 26.1 * c.len / 8192 : 5.7;   // run-time kernel: lengths <= 512 at the plans in use
 }
 
 int sht_k5_tickets(corahip_ctx *ctx, hipStream_t stream) {
@@ -1153,7 +1121,8 @@ int sht_second_stream(corahip_ctx *ctx) {
 }
 
 // ------------------------------------------------------------------------------------
-// plan time: Bluestein filters of the 3 * 2^k lengths, in the storage order of the forward passes above
+// plan time: the second filter set - Bluestein filters of the lengths marked `own` in fft_shapes.h, in the storage order
+// of the forward passes above
 // ------------------------------------------------------------------------------------
 template <int P>
 __global__ void __launch_bounds__(CT_T)
@@ -1178,29 +1147,28 @@ blu3_filter_kernel(int nside, const int32_t *__restrict__ p3_of, const int64_t *
     for (int j = tid; j < P; j += CT_T) f[j] = sm[fpad(j)];
 }
 
-int sht_blu3_tables(corahip_ctx *ctx, corahip_sht_plan *p, int64_t total) {
-    (void)total;
-    int32_t *d_p3 = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_p3, sizeof(int32_t) * p->h_blu3_P.size()));
-    HIP_TRY(hipMemcpyAsync(d_p3, p->h_blu3_P.data(), sizeof(int32_t) * p->h_blu3_P.size(), hipMemcpyHostToDevice, ctx->stream));
-    const int nb = p->nside - 1;
-#define BLU3_LAUNCH(PP)                                                                                                   \
-    {                                                                                                                     \
-        const size_t shm = sizeof(double2) * (size_t)(fpk<K5_PK_BLU>(PP) + K5_CH_SKEW);                                              \
-        HIP_TRY(hipFuncSetAttribute((const void *)blu3_filter_kernel<PP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        blu3_filter_kernel<PP><<<nb, CT_T, shm, ctx->stream>>>(p->nside, d_p3, p->d_blu_boff, p->d_blu3_foff, p->d_bchirp, p->d_bfilt3); \
-        LAUNCH_CHECK();                                                                                                   \
+// one launch per length with filters of its own that some ring of the plan uses (a workgroup per cap ring: those of
+// other lengths return at once)
+int sht_ctfilt_tables(corahip_ctx *ctx, corahip_sht_plan *p) {
+    int32_t *d_len = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_len, sizeof(int32_t) * p->h_ctfilt_len.size()));
+    HIP_TRY(hipMemcpyAsync(d_len, p->h_ctfilt_len.data(), sizeof(int32_t) * p->h_ctfilt_len.size(), hipMemcpyHostToDevice, ctx->stream));
+    for (const fft_shapes::ring_shape &s : fft_shapes::RING_BLU) {
+        if (std::find(p->h_ctfilt_len.begin(), p->h_ctfilt_len.end(), s.len) == p->h_ctfilt_len.end()) continue;
+        bool took;
+        const int rc = fft_shapes::dispatch<fft_shapes::RING_BLU, fft_shapes::own_filter>(
+            [&](const fft_shapes::ring_shape &r) { return r.len == s.len; },
+            [&](auto shape) {
+                constexpr int P = shape.row.len;
+                const size_t shm = sizeof(double2) * (size_t)(fpk<K5_PK_BLU>(P) + K5_CH_SKEW);
+                HIP_TRY(hipFuncSetAttribute((const void *)blu3_filter_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                blu3_filter_kernel<P><<<p->nside - 1, CT_T, shm, ctx->stream>>>(p->nside, d_len, p->d_blu_boff, p->d_ctfilt_off, p->d_bchirp, p->d_ctfilt);
+                LAUNCH_CHECK();
+                return 0;
+            }, &took);
+        if (rc) return rc;
     }
-    BLU3_LAUNCH(1536)
-    BLU3_LAUNCH(2560)
-    BLU3_LAUNCH(3072)
-    BLU3_LAUNCH(3584)
-    if (p->nside > 1024) {
-        BLU3_LAUNCH(6144)
-        BLU3_LAUNCH(8192)
-    }
-#undef BLU3_LAUNCH
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_p3);
+    (void)hipFree(d_len);
     return 0;
 }

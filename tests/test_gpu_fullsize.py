@@ -13,28 +13,56 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
+def _ring_length_rule(icap):
+    """The transform length of cap ring ``icap`` (1-based from the pole; 0: a belt ring), restated from the rule the
+    plan implements: 0 = direct transform (belt, and h = 2 icap a power of two), else the Bluestein length - with P the
+    smallest power of two >= 2 h - 1: 5 * 2^9 where P = 4096 and it holds 2 h - 1, else 3 P / 4 where that is 1536,
+    3072 or 6144 and holds 2 h - 1, else 7 * 2^9 where P = 4096 and it holds 2 h - 1, else P."""
+    h = 2 * icap
+    if icap == 0 or h & (h - 1) == 0:
+        return 0
+    need = 2 * h - 1
+    P = 1
+    while P < need:
+        P *= 2
+    if P == 4096 and need <= 2560:
+        return 2560
+    if 3 * P // 4 in (1536, 3072, 6144) and 3 * P // 4 >= need:
+        return 3 * P // 4
+    if P == 4096 and need <= 3584:
+        return 3584
+    return P
+
+
 def _ring_classes(nside, lmax):
     """K5 transform class of every ring (0-based, north to south) AS THE PLAN LAUNCHES IT
     (corahip_sht_plan_ring_classes): 0 = direct transform (belt and the cap rings with 4i a power of two), else the
-    Bluestein length of the kernel that takes the ring - a power of two >= 2 h - 1 (h = 2 i) or, for the rings whose
-    2 h - 1 fits it, 3 * 2^k (ringfft_blu_ct<3072> / <1536>) or 5 * 2^9 / 7 * 2^9."""
+    Bluestein length of the kernel that takes the ring - exactly the length of _ring_length_rule."""
     from cora_amd import _lib
 
     cls = _lib.get_context().sht_ring_classes(nside, lmax).astype(np.int64)
-    # the plan's classes against the rule they implement
     for r in range(4 * nside - 1):
         i = r + 1
         icap = i if i < nside else (4 * nside - i if i > 3 * nside else 0)
-        h = 2 * icap
-        if icap == 0 or h & (h - 1) == 0:
-            assert cls[r] == 0, (r, cls[r])
-        else:
-            # a Bluestein length that holds the ring: 2^k, 3 * 2^k, or 5 * 2^9 / 7 * 2^9 (ringfft_blu_ct<2560> / <3584>)
-            odd = int(cls[r])
-            while odd % 2 == 0:
-                odd //= 2
-            assert cls[r] >= 2 * h - 1 and (odd in (1, 3) or cls[r] in (2560, 3584)), (r, cls[r])
+        assert cls[r] == _ring_length_rule(icap), (r, cls[r], _ring_length_rule(icap))
     return cls
+
+
+_CAP_COUNTS_512 = {0: 9, 16: 1, 32: 3, 64: 7, 128: 15, 256: 31, 512: 63, 1024: 127, 1536: 128, 2048: 127}
+_CAP_COUNTS_1024 = {**_CAP_COUNTS_512, 0: 10, 2560: 128, 3072: 128, 3584: 128, 4096: 127}
+_CAP_COUNTS_2048 = {**_CAP_COUNTS_1024, 0: 11, 6144: 512, 8192: 511}
+
+
+def test_ring_classes_exact_lengths_and_counts(ctx):
+    """The plan's ring classes at nside 512 / 1024 / 2048 (they do not depend on lmax: plan creation only, at lmax 0):
+    every ring at exactly the length of the rule, and the number of rings per length - the table above over the north
+    cap, the same again in the south, the 2 nside + 1 belt rings direct."""
+    for nside, north in ((512, _CAP_COUNTS_512), (1024, _CAP_COUNTS_1024), (2048, _CAP_COUNTS_2048)):
+        cls = _ring_classes(nside, 0)
+        got = dict(zip(*(x.tolist() for x in np.unique(cls, return_counts=True))))
+        want = {length: 2 * n for length, n in north.items()}
+        want[0] += 2 * nside + 1
+        assert got == want, (nside, got, want)
 
 
 def _per_class_error(dev_map, ref, nside, lmax, skip_polar=0):
