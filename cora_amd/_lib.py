@@ -154,7 +154,10 @@ SIGNATURES = {
     "corahip_sht_lambda": (c_int, [c_void_p, c_void_p, c_int, c_int, PTR]),
     "corahip_sht_lambda_entry": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, PTR]),
     "corahip_sht_lambda_segment_entry": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, PTR, PTR]),
+    "corahip_debug_poison_scratch": (c_int, [c_void_p, c_int, ctypes.POINTER(c_size_t)]),
 }
+
+DEBUG_NSCRATCH = 13          # include/corahip.h: CORAHIP_DEBUG_NSCRATCH, the scratch slots of a context
 
 
 class CoraHipError(RuntimeError):
@@ -2119,6 +2122,15 @@ class Context:
         info = self.empty((4,), dtype=torch.int32)
         _check(self.lib.corahip_sht_lambda_segment_entry(self.h, plan, rt, m, ring_pair, kq, self._f64(out), self._p(info)))
         return out, tuple(int(v) for v in info.cpu().tolist())
+
+    def debug_poison_scratch(self, byte):
+        """Test hook (``corahip_debug_poison_scratch``): fills every scratch slot the library holds on this context with
+        ``byte`` (0 .. 255), marks its caches in those slots invalid and has later scratch growth and the per-call
+        allocations of the eigen routes filled with it; ``byte < 0`` ends that.  Returns the bytes of each slot at the
+        call.  CoraHipError (status CORAHIP_ESTATE) while a draw session is pending."""
+        sizes = (c_size_t * DEBUG_NSCRATCH)()
+        _check(self.lib.corahip_debug_poison_scratch(self.h, int(byte), sizes))
+        return [int(v) for v in sizes]
 
 
 _contexts = {}

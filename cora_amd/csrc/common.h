@@ -63,9 +63,15 @@ struct corahip_ctx {
     //        4 Legendre matrix of legendre_project, 5 its zero-padded operand, 6 block tables of normals_pcg64 /
     //        segment tables of normals_mt19937_legacy, 7 the two-slot ring of the l-range pipeline (drawstream.hip),
     //        8 barrier words of the cooperative Cholesky, 9 position lists of the MT19937 jump polynomials,
-    //        10 block partials of complex_variance (faraday.hip), 11 per-pixel source offsets of pointsource_paint
+    //        10 block partials of complex_variance (faraday.hip), 11 per-pixel source offsets of pointsource_paint,
+    //        12 spline records + interval lookup table of xi_multi_average (corrfunc.hip)
+    //  written whole by every call that reads them: 1, 3, 4, 5, 6, 7, 8, 10, 11, 12; caches behind a host flag: 0
+    //  (tt_valid), 2 (pairs_key / pairs_ptr), 9 (mt_plist_ready)
     void *scratch[CORAHIP_NSCRATCH] = {};
     size_t scratch_bytes[CORAHIP_NSCRATCH] = {};
+    // corahip_debug_poison_scratch (tests): the byte every newly allocated scratch slot and per-call device allocation
+    // is filled with, -1 = none (the default)
+    int debug_poison = -1;
     // K1 transposed tables resident in scratch slot 0: valid for the pinned (dd, dv, vv, generation) only
     // (corahip_clarray_tables_pin: the caller vouches that the tables do not change under that generation)
     const void *tt_pin[3] = {nullptr, nullptr, nullptr};
@@ -81,6 +87,8 @@ struct corahip_ctx {
 
 // returns a device buffer of at least `bytes` for `slot`, reallocating only when it must grow
 int corahip_ctx_scratch(corahip_ctx *ctx, int slot, size_t bytes, void **out);
+// fills a per-call device allocation with the poison byte of corahip_debug_poison_scratch, if one is set (tests)
+int corahip_debug_fill(corahip_ctx *ctx, void *p, size_t bytes);
 
 // RAII: HIP-event pair around the launches of one named stage when profiling is on.
 struct StageTimer {

@@ -564,6 +564,15 @@ int corahip_eig_top_batched(corahip_ctx *ctx, const double *C, int nl, int F, in
         corahip_set_error("eig_top_batched: no memory for the scratch of the full decomposition (%zu bytes)", per * batch);
         return CORAHIP_ENOMEM;
     }
+    {
+        int rcf = corahip_debug_fill(ctx, dlist, sizeof(int32_t) * list.size());
+        if (!rcf) rcf = corahip_debug_fill(ctx, scratch, per * batch);
+        if (rcf) {
+            (void)hipFree(dlist);
+            (void)hipFree(scratch);
+            return rcf;
+        }
+    }
     HIP_TRY(hipMemcpyAsync(dlist, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));
     const size_t shj = sizeof(double) * (2 * (F / 2 + 1) + JAC_NT + F) + sizeof(int) * (F + 4) + 16;
     for (size_t b0 = 0; b0 < list.size(); b0 += batch) {

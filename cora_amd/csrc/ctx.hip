@@ -20,8 +20,18 @@ int corahip_ctx_scratch(corahip_ctx *ctx, int slot, size_t bytes, void **out) {
         ctx->scratch_bytes[slot] = 0;
         HIP_TRY(hipMalloc(&ctx->scratch[slot], bytes));
         ctx->scratch_bytes[slot] = bytes;
+        int rc = corahip_debug_fill(ctx, ctx->scratch[slot], bytes);
+        if (rc) return rc;
     }
     *out = ctx->scratch[slot];
+    return 0;
+}
+
+// (waited for: the library's side streams use some of these buffers without an event behind the context's stream)
+int corahip_debug_fill(corahip_ctx *ctx, void *p, size_t bytes) {
+    if (ctx->debug_poison < 0 || !p || !bytes) return 0;
+    HIP_TRY(hipMemsetAsync(p, ctx->debug_poison, bytes, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }
 
@@ -187,6 +197,34 @@ int corahip_memcpy_h2d(corahip_ctx *ctx, void *dst, const void *host_src, size_t
 int corahip_memcpy_d2h(corahip_ctx *ctx, void *host_dst, const void *src, size_t bytes) {
     ARG_CHECK(ctx != nullptr);
     HIP_TRY(hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+static_assert(CORAHIP_DEBUG_NSCRATCH == CORAHIP_NSCRATCH, "include/corahip.h states the number of scratch slots");
+
+int corahip_debug_poison_scratch(corahip_ctx *ctx, int byte, size_t *slot_bytes) {
+    ARG_CHECK(ctx != nullptr && byte <= 255);
+    if (ctx->draw_pending) {
+        corahip_set_error("corahip_debug_poison_scratch: a draw session is pending on this context (its launches use the scratch slots)");
+        return CORAHIP_ESTATE;
+    }
+    if (slot_bytes)
+        for (int i = 0; i < CORAHIP_NSCRATCH; i++) slot_bytes[i] = ctx->scratch_bytes[i];
+    ctx->debug_poison = byte < 0 ? -1 : byte;
+    if (byte < 0) return 0;
+    // nothing queued may still read a slot: the side streams are joined by every entry point, the context's is drained here
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (ctx->gen_stream) HIP_TRY(hipStreamSynchronize(ctx->gen_stream));
+    if (ctx->stream2) HIP_TRY(hipStreamSynchronize(ctx->stream2));
+    for (int i = 0; i < CORAHIP_NSCRATCH; i++)
+        if (ctx->scratch[i] && ctx->scratch_bytes[i])
+            HIP_TRY(hipMemsetAsync(ctx->scratch[i], byte, ctx->scratch_bytes[i], ctx->stream));
+    // the cached slots no longer hold what their host flags vouch for
+    ctx->tt_valid = false;                                   // slot 0
+    for (auto &k : ctx->pairs_key) k = -1;                   // slot 2
+    ctx->pairs_ptr = nullptr;
+    ctx->mt_plist_ready = false;                             // slot 9
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -842,6 +842,11 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
     dev_mem dlist_mem, scratch_mem;       // (freed behind the last kernel, or on an error return)
     HIP_TRY(hipMalloc(&dlist_mem.p, sizeof(int32_t) * list.size()));
     HIP_TRY(hipMalloc(&scratch_mem.p, per * batch));
+    {
+        int rcf = corahip_debug_fill(ctx, dlist_mem.p, sizeof(int32_t) * list.size());
+        if (!rcf) rcf = corahip_debug_fill(ctx, scratch_mem.p, per * batch);
+        if (rcf) return rcf;
+    }
     int32_t *dlist = static_cast<int32_t *>(dlist_mem.p);
     double *scratch = static_cast<double *>(scratch_mem.p);
     HIP_TRY(hipMemcpyAsync(dlist, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));

@@ -55,6 +55,11 @@ def test_abi_symbols_present():
         assert n[len("corahip_"):] in header.split("#define CORAHIP_ABI_MINOR")[1].split("\n")[0]
     for m in ("eig_top_batched", "eig_top_max_f", "constrained_weights", "alm_mix_l"):
         assert callable(getattr(_lib.Context, m))
+    # the test hook that fills the scratch of the context (and the per-call scratch of the eigen routes) with a poison byte
+    n = "corahip_debug_poison_scratch"
+    assert n in _lib.SIGNATURES and hasattr(lib, n) and ("int %s(corahip_ctx *ctx, int byte, size_t *slot_bytes);" % n) in header
+    assert "debug_poison_scratch (test hook)" in header.split("#define CORAHIP_ABI_MINOR")[1].split("\n")[0]
+    assert len(_lib.SIGNATURES[n][1]) == 3 and callable(_lib.Context.debug_poison_scratch)
     from cora_amd.core import skysim
 
     for f in ("constrained_weights_device", "mkconstrained_device", "mkconstrained"):
