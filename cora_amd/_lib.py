@@ -147,6 +147,8 @@ SIGNATURES = {
     "corahip_alm_mix_l": (c_int, [c_void_p, PTR, c_int, c_int, PTR, c_int, PTR]),
     "corahip_sinc_romb": (c_int, [c_void_p, PTR, PTR, c_int, c_double, PTR, c_int, PTR]),
     "corahip_fftlog_phase": (c_int, [c_void_p, c_double, c_double, ctypes.c_int64, PTR]),
+    "corahip_jl_romb": (c_int, [c_void_p, PTR, c_int, ctypes.POINTER(c_int), PTR, c_int, c_double, PTR, c_int, PTR]),
+    "corahip_xi_rsd": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, PTR, PTR, ctypes.c_long, PTR, ctypes.c_long, PTR]),
     "corahip_logconv": (c_int, [c_void_p, PTR, PTR, ctypes.c_int64, c_int, c_int]),
     "corahip_logconv_split": (c_int, [ctypes.c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
@@ -1404,6 +1406,63 @@ class Context:
                 raise ValueError("sinc_romb: out overlaps %s" % name)
         _check(self.lib.corahip_sinc_romb(self.h, self._f64(g), self._f64(ka), k, float(dlk), self._f64(r), nr,
                                           self._f64(out)))
+        return out
+
+    def jl_romb(self, g, ka, dlk, r, lmask=None, out=None):
+        """``out[s, i, j] = dlk * scipy.integrate.romb(g[s] * j_l(ka * r[j]))`` for ``l = 2 i`` = 0, 2, 4 (spherical Bessel
+        functions) in one pass: ``g`` [nspec, 2^k + 1] with nspec 1 to 3 (or [2^k + 1]), ``ka`` [2^k + 1], ``r`` [nr] on the
+        device -> [nspec, 3, nr].  ``lmask`` (host, one int per integrand, default 7): bit i set = order 2 i wanted; the
+        other slots are +0.0.  The l = 0 slot has the bits of :meth:`sinc_romb`; a repeated call returns the same bits."""
+        torch = _torch()
+        if isinstance(g, torch.Tensor) and g.dim() == 1:
+            g = g.unsqueeze(0)
+        if (not isinstance(g, torch.Tensor) or g.dim() != 2 or g.dtype != torch.float64 or g.device != self.device
+                or not g.is_contiguous()):
+            raise ValueError("jl_romb: g must be a contiguous float64 [nspec, 2^k + 1] tensor on %s" % (self.device,))
+        nspec, n = int(g.shape[0]), int(g.shape[1])
+        k = (n - 1).bit_length() - 1
+        if n < 3 or n != (1 << k) + 1 or k > 24:
+            raise ValueError("jl_romb: g must have 2^k + 1 samples with 1 <= k <= 24 (got %d)" % n)
+        if not 1 <= nspec <= 3:
+            raise ValueError("jl_romb takes 1 to 3 integrands (got %d)" % nspec)
+        masks = [7] * nspec if lmask is None else [int(m) for m in np.atleast_1d(lmask)]
+        if len(masks) != nspec or any(m < 0 or m > 7 for m in masks):
+            raise ValueError("jl_romb: lmask must hold one value 0 .. 7 per integrand (got %r)" % (lmask,))
+        self._dev1d(ka, "ka", n)
+        nr = self._dev1d(r, "r")
+        out = self._out_like(out, (nspec, 3, nr), "jl_romb")
+        for t, name in ((g, "g"), (ka, "ka"), (r, "r")):
+            if self._overlap(out, out.numel() * 8, t, t.numel() * 8):
+                raise ValueError("jl_romb: out overlaps %s" % name)
+        _check(self.lib.corahip_jl_romb(self.h, self._f64(g), nspec, (c_int * nspec)(*masks), self._f64(ka), k, float(dlk),
+                                        self._f64(r), nr, self._f64(out)))
+        return out
+
+    def xi_rsd(self, kx, ky, ky2, pi, sigma, coef, out=None):
+        """``corahip_xi_rsd``: the redshift-space correlation function at the points (``pi``, ``sigma``) [n] from the
+        multipole tables ``ky``, ``ky2`` [nfun, nk] (nfun 3: vv0 vv2 vv4; 6: + dd0 dv0 dv2) on the knots ``kx`` [nk] and
+        the coefficient rows ``coef`` [ncoef, 4] = (b1 b2, (b1 f2 + b2 f1) / 2, f1 f2, D1 D2 pf1 pf2); point i reads row
+        i % ncoef.  Everything on the device -> [n]."""
+        nk = self._dev1d(kx, "kx")
+        if ky.dim() != 2 or ky.shape[1] != nk or tuple(ky2.shape) != tuple(ky.shape):
+            raise ValueError("xi_rsd: ky and ky2 must be [nfun, %d] (got %s, %s)" % (nk, tuple(ky.shape), tuple(ky2.shape)))
+        if not (ky.is_contiguous() and ky2.is_contiguous()):
+            raise ValueError("xi_rsd: ky and ky2 must be contiguous")
+        nfun = int(ky.shape[0])
+        if nfun not in (3, 6):
+            raise ValueError("xi_rsd takes 3 tables (vv0 vv2 vv4) or 6 (+ dd0 dv0 dv2), got %d" % nfun)
+        if nk < 4:
+            raise ValueError("the spline tables need at least 4 knots (got %d)" % nk)
+        n = self._dev1d(pi, "pi")
+        self._dev1d(sigma, "sigma", n)
+        if coef.dim() != 2 or coef.shape[1] != 4 or coef.shape[0] < 1 or not coef.is_contiguous():
+            raise ValueError("xi_rsd: coef must be a contiguous [ncoef >= 1, 4] tensor (got %s)" % (tuple(coef.shape),))
+        out = self._out_like(out, (n,), "xi_rsd")
+        for t, name in ((pi, "pi"), (sigma, "sigma"), (coef, "coef"), (kx, "kx"), (ky, "ky"), (ky2, "ky2")):
+            if self._overlap(out, n * 8, t, t.numel() * 8):
+                raise ValueError("xi_rsd: out overlaps %s" % name)
+        _check(self.lib.corahip_xi_rsd(self.h, self._f64(kx), self._f64(ky), self._f64(ky2), nk, nfun, self._f64(pi),
+                                       self._f64(sigma), n, self._f64(coef), int(coef.shape[0]), self._f64(out)))
         return out
 
     def fftlog_phase(self, mu, L, N, out=None):

@@ -10,6 +10,7 @@
 //   dgemm_nn_kernel      C[L x N] = A[L x M] B[M x N] on FP64 MFMA: gemm_nn_128 of mfma_tile.h as it is
 #include "common.h"
 #include "mfma_tile.h"
+#include "spline_dev.h"
 
 #include "rng_dev.h"   // fast_log01, fast_sqrt_pos (both hold their accuracy over every positive normal argument met here)
 
@@ -23,21 +24,7 @@ struct spline_lds {
     int n, nlut;
     double x0, inv_dx;
 };
-// the three expressions of one evaluation (cubicspline.pyx:126-175), on values: xi_table_kernel takes them from LDS,
-// xi_multi_kernel from the interval records it reads through the caches
-__device__ static inline double spline_below(double x0, double x1, double y0, double y1, double z1, double x) {
-    const double h = x1 - x0;
-    return ((y1 - y0) / h - h * z1 / 6.0) * (x - x0) + y0;
-}
-__device__ static inline double spline_above(double xm, double xn, double ym, double yn, double zm, double x) {
-    const double h = xn - xm;
-    return ((yn - ym) / h + h * zm / 6.0) * (x - xn) + yn;
-}
-__device__ static inline double spline_interp(double xk, double xk1, double ih, double h2o6, double yk, double yk1,
-                                              double zk, double zk1, double x) {
-    const double a = (xk1 - x) * ih, b = (x - xk) * ih;
-    return a * yk + b * yk1 + ((a * a * a - a) * zk + (b * b * b - b) * zk1) * h2o6;
-}
+// the three expressions of one evaluation and the bisection of a look-up cell: spline_dev.h
 // interval of xs[0] <= x < xs[n-1]: the last knot with xs[k] <= x, from the look-up cell walked both ways;
 // knot(k) = xs[k], next(k) = xs[k + 1]
 template <class Knot, class Next>
@@ -48,16 +35,6 @@ __device__ static inline int spline_interval(Knot knot, Next next, const int *lu
     int kl = lut[g];
     while (kl > 0 && knot(kl) > x) kl--;            // (rounding of the cell index at a cell edge)
     while (kl + 2 < n && next(kl) <= x) kl++;
-    return kl;
-}
-// lut[g]: bisection for the last knot at or before the left edge of cell g
-__device__ static inline int spline_lut_cell(const double *xs, int nk, double xl) {
-    int kl = 0, kh = nk;
-    while (kh - kl > 1) {
-        const int kn = (kh + kl) >> 1;
-        if (xs[kn] > xl) kh = kn;
-        else kl = kn;
-    }
     return kl;
 }
 __device__ static inline double spline_eval(const spline_lds &S, double x) {

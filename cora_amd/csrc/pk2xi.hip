@@ -73,6 +73,122 @@ sinc_romb_kernel(const double *__restrict__ g, const double *__restrict__ ka, in
     }
 }
 
+// ---- j_0, j_2, j_4 in one pass ------------------------------------------------------------------------------------
+// One sine and one cosine of x serve the three orders.  j_0 = sinc_of(x), the bits of sinc_romb.  j_2 and j_4: above
+// the switch argument the closed forms in y = 1 / x,
+//   j_2 = ((3 y^2 - 1) sin x - 3 y cos x) y,   j_4 = ((105 y^4 - 45 y^2 + 1) sin x - (105 y^3 - 10 y) cos x) y,
+// whose terms are of size 3 / x^2 (105 / x^4) where the result is x^2 / 15 (x^4 / 945): each rounding of a term shows
+// in the result, so the absolute error is 6 eps (3 y^3 + 3 y^2 + y) and 7 eps (105 y^5 + 105 y^4 + 45 y^3 + 10 y^2 + y),
+// 9.75 eps at x = 2 and 14.7 eps at x = 4 and falling from there.  Below the switch the ascending series
+//   j_l = x^l / (2l + 1)!! sum_m prod_{i <= m} (-x^2 / (2 i (2 i + 2 l + 1))),
+// Horner in x^2 from the last term in: no cancellation (every ratio is below 1 for x^2 < 2 (2 l + 3)), the first term
+// left out is 1.2e-18 (l = 2, 11 terms, x = 2) and 1.6e-18 (l = 4, 13 terms, x = 4) absolutely.  tests/_rsdcorr_oracle.py
+// derives the constants and restates the arithmetic.  x = 0: j_0 = 1 and j_2 = j_4 = +0.0.
+#define JL_SWITCH2 2.0
+#define JL_SWITCH4 4.0
+#define JL_TERMS2 11
+#define JL_TERMS4 13
+#define JL_MAXSPEC 3
+
+template <int L, int NT>
+__device__ static inline double jl_series(double x2) {
+    double acc = 1.0;
+#pragma unroll
+    for (int m = NT; m >= 1; m--) acc = fma(-(x2 * (1.0 / (2.0 * m * (2.0 * m + 2 * L + 1)))), acc, 1.0);
+    return acc;
+}
+
+__device__ static inline void jl_024(double x, double &j0, double &j2, double &j4) {
+    j0 = sinc_of(x);                               // sinc_romb's own function: the l = 0 slot has its bits by construction
+    const double s = sin(x), c = cos(x);           // (the sine is the one sinc_of has just computed: same call, same argument)
+    const double ax = fabs(x), x2 = x * x;
+    const double y = 1.0 / x, y2 = y * y;          // (inf at x = 0: only the series branches are taken there)
+    if (ax < JL_SWITCH2) j2 = x2 * (1.0 / 15.0) * jl_series<2, JL_TERMS2>(x2);
+    else j2 = (fma(3.0, y2, -1.0) * s - 3.0 * y * c) * y;
+    if (ax < JL_SWITCH4) j4 = (x2 * x2) * (1.0 / 945.0) * jl_series<4, JL_TERMS4>(x2);
+    else j4 = (fma(fma(105.0, y2, -45.0), y2, 1.0) * s - fma(105.0, y2, -10.0) * y * c) * y;
+}
+
+// out[s][i][j] = dlk * romb_n(g[s][n] j_{2i}(ka[n] r[j])): sinc_romb_kernel with 3 NS accumulators per thread - the same
+// ownership of the samples, the same class sums, the same table, per slot q = 3 s + i; thread q runs the table of slot q.
+// A slot whose bit in lmask[s] is clear is written as +0.0, and so are the l = 2, 4 slots at r = 0.
+struct jl_masks {
+    int m[JL_MAXSPEC];
+};
+
+template <int NS>
+__global__ void __launch_bounds__(PX_THREADS)
+jl_romb_kernel(const double *__restrict__ g, jl_masks lmask, const double *__restrict__ ka, int k, double dlk,
+               const double *__restrict__ r, int nr, double *__restrict__ out) {
+    constexpr int NQ = 3 * NS;
+    __shared__ double part[NQ][PX_THREADS];
+    __shared__ double S[NQ][PX_MAXK + 1];
+    __shared__ double tab[NQ][2][PX_MAXK + 1];
+    const int tid = threadIdx.x;
+    const long K = 1L << k;
+    const double rj = r[blockIdx.x];
+    for (int e = tid; e < NQ * (PX_MAXK + 1); e += PX_THREADS) S[e / (PX_MAXK + 1)][e % (PX_MAXK + 1)] = 0.0;
+    __syncthreads();
+    double acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) acc[q] = 0.0;
+    if (tid) {
+        for (long i = tid; i < K; i += PX_THREADS) {
+            double j[3];
+            jl_024(ka[i] * rj, j[0], j[1], j[2]);
+#pragma unroll
+            for (int q = 0; q < NQ; q++) acc[q] += g[(q / 3) * (K + 1) + i] * j[q % 3];
+        }
+    } else {
+        for (long i = PX_THREADS; i < K; i += PX_THREADS) {
+            double j[3];
+            jl_024(ka[i] * rj, j[0], j[1], j[2]);
+            const int t = __ffsll((long long)i) - 1;
+#pragma unroll
+            for (int q = 0; q < NQ; q++) S[q][t] += g[(q / 3) * (K + 1) + i] * j[q % 3];
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; q++) part[q][tid] = acc[q];
+    __syncthreads();
+    if (tid < 64) {
+#pragma unroll
+        for (int q = 0; q < NQ; q++) {
+            for (int t = 0; t < 8; t++) {
+                const int cnt = 128 >> t;
+                double v = 0.0;
+                for (int j = tid; j < cnt; j += 64) v += part[q][(2 * j + 1) << t];
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) v += __shfl_down(v, o, 64);
+                if (tid == 0) S[q][t] = v;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < NQ) {
+        const int s = tid / 3, l = tid % 3;
+        const double *gs = g + (size_t)s * (K + 1);
+        double j0[3], jK[3];
+        jl_024(ka[0] * rj, j0[0], j0[1], j0[2]);
+        jl_024(ka[K] * rj, jK[0], jK[1], jK[2]);
+        double c = 0.5 * (gs[0] * j0[l] + gs[K] * jK[l]);
+        int cur = 0;
+        for (int i = 0; i <= k; i++, cur ^= 1) {
+            if (i) c += S[tid][k - i];
+            double *row = tab[tid][cur];
+            const double *prv = tab[tid][cur ^ 1];
+            row[0] = ldexp(c, k - i);
+            double p4 = 1.0;
+            for (int j = 1; j <= i; j++) {
+                p4 *= 4.0;
+                row[j] = row[j - 1] + (row[j - 1] - prv[j - 1]) / (p4 - 1.0);
+            }
+        }
+        const bool on = ((lmask.m[s] >> l) & 1) && !(l > 0 && rj == 0.0);
+        out[(size_t)tid * nr + blockIdx.x] = on ? dlk * tab[tid][cur ^ 1][k] : 0.0;
+    }
+}
+
 __device__ static inline double2 px_cmul(double2 a, double2 b) {
     return make_double2(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
 }
@@ -161,6 +277,22 @@ int corahip_sinc_romb(corahip_ctx *ctx, const double *g, const double *ka, int k
     if (nr == 0) return 0;
     StageTimer t(ctx, "sinc_romb");
     sinc_romb_kernel<<<nr, PX_THREADS, 0, ctx->stream>>>(g, ka, k, dlk, r, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_jl_romb(corahip_ctx *ctx, const double *g, int nspec, const int *lmask, const double *ka, int k, double dlk,
+                    const double *r, int nr, double *out) {
+    ARG_CHECK(ctx != nullptr && g && lmask && ka && r && out && nr >= 0);
+    ARG_CHECK(nspec >= 1 && nspec <= JL_MAXSPEC && k >= 1 && k <= PX_MAXK);
+    jl_masks m;
+    for (int s = 0; s < JL_MAXSPEC; s++) m.m[s] = s < nspec ? lmask[s] : 0;
+    for (int s = 0; s < nspec; s++) ARG_CHECK(m.m[s] >= 0 && m.m[s] <= 7);
+    if (nr == 0) return 0;
+    StageTimer t(ctx, "jl_romb");
+    if (nspec == 1) jl_romb_kernel<1><<<nr, PX_THREADS, 0, ctx->stream>>>(g, m, ka, k, dlk, r, nr, out);
+    else if (nspec == 2) jl_romb_kernel<2><<<nr, PX_THREADS, 0, ctx->stream>>>(g, m, ka, k, dlk, r, nr, out);
+    else jl_romb_kernel<3><<<nr, PX_THREADS, 0, ctx->stream>>>(g, m, ka, k, dlk, r, nr, out);
     LAUNCH_CHECK();
     return 0;
 }

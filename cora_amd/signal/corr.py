@@ -12,10 +12,15 @@ The flat-sky redshift-space cube (``_realisation_dv`` / ``realisation``, corr.py
 the GPU through csrc/flatsky.hip: Gaussian field draw, the mu^2 velocity field by rfftn / irfftn,
 per-slice growth factors and the ray-traced trilinear resampling.
 
-The multipole correlation functions and ``angular_powerspectrum_full`` of the reference's corr.py
-are outside this package's scope.
+The redshift-space correlation function xi(pi, sigma; z1, z2) (corr.py:242-446) runs through
+csrc/rsdcorr.hip (``corahip_xi_rsd``: the six multipole splines and the Legendre combination fused, one pass over the
+points) on tables that ``gen_cache`` makes on the device (``corrfunc.ps_to_multipoles``: ``corahip_jl_romb`` and FFTLog) or
+``_load_cache`` reads from a file.  ``powerspectrum`` / ``powerspectrum_1D`` call Python spectra and stay host numpy.
+
+``angular_powerspectrum_full`` of the reference's corr.py is dead code there and outside this package's scope.
 """
 import math
+from os.path import exists
 
 import numpy as np
 
@@ -49,6 +54,8 @@ class RedshiftCorrelation(object):
     bias = 1.0
     _vv_only = False
 
+    _cached = False
+
     kperpmin = 1e-4
     kperpmax = 40.0
     nkperp = 500
@@ -66,6 +73,179 @@ class RedshiftCorrelation(object):
         self._vv_only = False if ps_dd and ps_dv else True
         self.cosmology = Cosmology()
         self._dev_tables = {}
+
+    @classmethod
+    def from_file_matterps(cls, fname, redshift=0.0, bias=1.0):
+        """Initialise from a cached 4-column multipole file of a single power spectrum (corr.py:114-132)."""
+        rc = cls(redshift=redshift, bias=bias)
+        rc._vv_only = True
+        rc._load_cache(fname)
+        return rc
+
+    @classmethod
+    def from_file_fullps(cls, fname, redshift=0.0):
+        """Initialise from a cached 7-column multipole file of the three power spectra (corr.py:134-150)."""
+        rc = cls(redshift=redshift)
+        rc._vv_only = False
+        rc._load_cache(fname)
+        return rc
+
+    # ---- power spectra (corr.py:152-240): Python spectra, host numpy --------------------------
+    def powerspectrum(self, kpar, kperp, z1=None, z2=None):
+        """The redshift-space power spectrum at (kpar, kperp) (corr.py:152-201): ``ps_vv (b1 + mu^2 f1)(b2 + mu^2 f2)``
+        (``ps_vv(k, mu)`` with ``ps_2d``), or the three-spectrum form, times D1 D2 pf1 pf2.  A redshift left ``None`` is
+        ``ps_redshift``."""
+        if z1 is None:
+            z1 = self.ps_redshift
+        if z2 is None:
+            z2 = self.ps_redshift
+        b1, b2 = self.bias_z(z1), self.bias_z(z2)
+        f1, f2 = self.growth_rate(z1), self.growth_rate(z2)
+        D1 = self.growth_factor(z1) / self.growth_factor(self.ps_redshift)
+        D2 = self.growth_factor(z2) / self.growth_factor(self.ps_redshift)
+        pf1, pf2 = self.prefactor(z1), self.prefactor(z2)
+        k2 = kpar**2 + kperp**2
+        k = k2**0.5
+        mu = kpar / k
+        mu2 = kpar**2 / k2
+        if self._vv_only:
+            if self.ps_2d:
+                ps = self.ps_vv(k, mu) * (b1 + mu2 * f1) * (b2 + mu2 * f2)
+            else:
+                ps = self.ps_vv(k) * (b1 + mu2 * f1) * (b2 + mu2 * f2)
+        else:
+            ps = b1 * b2 * self.ps_dd(k) + mu2 * self.ps_dv(k) * (f1 * b2 + f2 * b1) + mu2**2 * f1 * f2 * self.ps_vv(k)
+        return D1 * D2 * pf1 * pf2 * ps
+
+    def powerspectrum_1D(self, k_vec, z1, z2, numz):
+        """The real-space power spectrum ``ps_vv(k)`` times the square of the mean of D(z) pf(z) b(z) over ``numz + 1``
+        slices equally spaced in comoving distance between ``z1`` and ``z2`` (corr.py:203-240)."""
+        c1 = self.cosmology.comoving_distance(z1)
+        c2 = self.cosmology.comoving_distance(z2)
+        comoving_inv = inverse_approx(self.cosmology.comoving_distance, z1, z2)
+        za = comoving_inv(np.linspace(c1, c2, numz + 1, endpoint=True))
+        Dz = self.growth_factor(za) / self.growth_factor(self.ps_redshift)
+        dfactor = np.mean(Dz * self.prefactor(za) * self.bias_z(za))
+        return self.ps_vv(k_vec) * dfactor * dfactor
+
+    # ---- xi(pi, sigma; z1, z2) (corr.py:242-446) ------------------------------------------------
+    _MULTIPOLES = ("_vv0i", "_vv2i", "_vv4i", "_dd0i", "_dv0i", "_dv2i")
+
+    def _set_multipoles(self, ra, cols):
+        """``cols``: vv0 vv2 vv4 (dd0 dv0 dv2) on ``ra`` -> the interpolaters of the reference and the knot arrays
+        (knots, y [nfun, nk], y'' [nfun, nk]) the device evaluator takes."""
+        ra = np.ascontiguousarray(ra, dtype=np.float64)
+        for name, col in zip(self._MULTIPOLES, cols):
+            setattr(self, name, cs.Interpolater(ra, np.asarray(col, dtype=np.float64)))
+        sp = [getattr(self, name) for name in self._MULTIPOLES[: len(cols)]]
+        self._xi_knots = (ra, np.stack([i._data[:, 1] for i in sp]), np.stack([i._y2 for i in sp]))
+        self.__dict__.pop("_xi_knots_dev", None)
+        self._cached = True
+
+    def _load_cache(self, fname):
+        """Load a multipole table ``r vv0 vv2 vv4 [dd0 dv0 dv2]`` written by :meth:`gen_cache` or by the reference
+        (corr.py:372-397)."""
+        if not exists(fname):
+            raise Exception("Cache file does not exist.")
+        a = np.loadtxt(fname)
+        if not self._vv_only and a.shape[1] != 7:
+            raise Exception("Cache file has wrong number of columns.")
+        self._set_multipoles(a[:, 0], [a[:, i] for i in range(1, 4 if self._vv_only else 7)])
+
+    def gen_cache(self, fname=None, rmin=1e-3, rmax=1e4, rnum=1000):
+        """Tabulate the multipoles xi_0, xi_2, xi_4 of ``ps_vv`` - and xi_0 of ``ps_dd``, xi_0, xi_2 of ``ps_dv`` when the
+        three spectra are given - on ``logspace(log10 rmin, log10 rmax, rnum)`` and keep them as the interpolaters the
+        correlation function reads (corr.py:399-446).  With ``fname`` the 4- or 7-column text file of the reference is
+        written, unless it exists.
+
+        The integrals run on the device (``corrfunc.ps_to_multipoles``) and are the clean ones over k in (0, inf).  The
+        reference's ``_integrate`` (corr.py:994-1050, dead there: it imports a module that does not exist) integrated
+        between 1e-4 pi / r and 1e3 pi / r with a smoothed upper edge, and so did the table the reference ships for the 21cm
+        model: that table differs from the clean integral below r ~ 0.05 and above r ~ 30.  ``_load_cache`` of that file
+        reproduces the reference's numbers."""
+        from . import corrfunc
+
+        ra = np.logspace(np.log10(rmin), np.log10(rmax), rnum)
+        ps, ls = [self.ps_vv], [(0, 2, 4)]
+        if not self._vv_only:
+            ps, ls = ps + [self.ps_dd, self.ps_dv], ls + [(0,), (0, 2)]
+        xi = corrfunc.ps_to_multipoles(ps, ls, ra)
+        cols = [xi[0][0], xi[0][2], xi[0][4]]
+        if not self._vv_only:
+            cols += [xi[1][0], xi[2][0], xi[2][2]]
+        if fname and not exists(fname):
+            np.savetxt(fname, np.dstack([ra] + cols)[0])
+        self._set_multipoles(ra, cols)
+
+    def _z_coefficients(self, z1, z2):
+        """The coefficient rows (b1 b2, (b1 f2 + b2 f1) / 2, f1 f2, D1 D2 pf1 pf2) of the model hooks on the broadcast
+        redshifts -> (rows [nz, 4], the shape the redshifts broadcast to)."""
+        z1, z2 = np.broadcast_arrays(np.asarray(z1, dtype=np.float64), np.asarray(z2, dtype=np.float64))
+        b1, b2 = self.bias_z(z1), self.bias_z(z2)
+        f1, f2 = self.growth_rate(z1), self.growth_rate(z2)
+        D1 = self.growth_factor(z1) / self.growth_factor(self.ps_redshift)
+        D2 = self.growth_factor(z2) / self.growth_factor(self.ps_redshift)
+        pf1, pf2 = self.prefactor(z1), self.prefactor(z2)
+        one = np.ones(z1.shape)
+        rows = np.stack([one * (b1 * b2), one * (0.5 * (b1 * f2 + b2 * f1)), one * (f1 * f2), one * (D1 * D2 * pf1 * pf2)], axis=-1)
+        return np.ascontiguousarray(rows.reshape(-1, 4), dtype=np.float64), z1.shape
+
+    def redshiftspace_correlation_device(self, pi, sigma, z1=None, z2=None):
+        """:meth:`redshiftspace_correlation` on float64 device tensors ``pi``, ``sigma`` (broadcast against each other and
+        against the redshifts) -> device tensor.  The redshifts are host scalars or arrays."""
+        import torch
+
+        ctx = _lib.get_context()
+        if z1 is None and z2 is None:
+            z1 = z2 = self.ps_redshift
+        elif z2 is None:
+            z2 = z1
+        elif z1 is None:
+            z1 = self.ps_redshift
+        if not self._cached:
+            self.gen_cache()
+        rows, zshape = self._z_coefficients(z1, z2)
+        pi, sigma = torch.broadcast_tensors(torch.as_tensor(pi, dtype=torch.float64, device=ctx.device),
+                                            torch.as_tensor(sigma, dtype=torch.float64, device=ctx.device))
+        shape = tuple(np.broadcast_shapes(tuple(pi.shape), zshape))
+        if len(rows) > 1:
+            # point i reads row i % ncoef: true as it is when the redshifts lie on the trailing axes of the result
+            full = np.broadcast_to(np.arange(len(rows)).reshape(zshape), shape).reshape(-1)
+            if not np.array_equal(full, np.arange(full.size) % len(rows)):
+                rows = rows[full]
+        pi, sigma = (t.expand(shape).contiguous().reshape(-1) for t in (pi, sigma))
+        dev = self.__dict__.get("_xi_knots_dev")
+        if dev is None or dev[0] != ctx.device.index:
+            dev = self._xi_knots_dev = (ctx.device.index,) + tuple(ctx.to_device(a) for a in self._xi_knots)
+        out = ctx.xi_rsd(dev[1], dev[2], dev[3], pi, sigma, ctx.to_device(rows))
+        return out.reshape(shape)
+
+    def redshiftspace_correlation(self, pi, sigma, z1=None, z2=None):
+        """The correlation function in the flat-sky approximation at radial separation ``pi`` and transverse separation
+        ``sigma`` (h^-1 Mpc), numpy in and out (corr.py:242-348); ``pi`` and ``sigma`` broadcast to a common shape.
+
+        With neither redshift given both points are at ``ps_redshift``; with only ``z1`` the second point is at ``z1``.
+        The model hooks ``bias_z``, ``growth_rate``, ``growth_factor`` and ``prefactor`` are evaluated on the host on the
+        redshifts only; the multipole splines and the Legendre combination run on the device (``corahip_xi_rsd``).
+
+        With only ``ps_vv`` known, dd0 = dv0 = vv0 and dv2 = vv2 enter the formula of the reference's docstring.  (The
+        reference itself does that for scalar arguments only: for arrays it scales the three names in place although they
+        are one array, so each ends up times b1 b2 (b1 f2 + b2 f1) / 2 f1 f2.  That is not reproduced.)
+
+        Extension: the redshifts may be arrays that broadcast against the points (the reference tests ``z == None``, which
+        fails for arrays of more than one element).  Without a cache the call runs :meth:`gen_cache` with its defaults
+        first, where the reference would enter its dead ``_integrate`` at every r."""
+        out = self.redshiftspace_correlation_device(np.asarray(pi, dtype=np.float64), np.asarray(sigma, dtype=np.float64),
+                                                    z1, z2).cpu().numpy()
+        return out if out.ndim else float(out)
+
+    def angular_correlation(self, theta, z1, z2):
+        """Angular correlation function in the flat-sky approximation: ``theta`` in radians between points at ``z1``
+        and ``z2`` (corr.py:350-370)."""
+        za = (z1 + z2) / 2.0
+        sigma = theta * self.cosmology.proper_distance(za)
+        pi = self.cosmology.comoving_distance(z2) - self.cosmology.comoving_distance(z1)
+        return self.redshiftspace_correlation(pi, sigma, z1, z2)
 
     # ---- model hooks (corr.py:448-530) --------------------------------------------------
     def bias_z(self, z):

@@ -3,6 +3,11 @@
 Supplies T_b(z), Pade growth factor / rate and the frequency -> redshift wrapper around the
 table model of :mod:`cora_amd.signal.corr`; inherits ``Sky3d`` so ``getsky()`` runs the
 whole hot path on the GPU.
+
+The multipole table behind ``redshiftspace_correlation`` is built lazily, by ``gen_cache()`` on the first correlation
+call (the reference loads a shipped table in ``__init__``).  It holds the clean integrals over k in (0, inf); the
+reference's shipped table was integrated between 1e-4 pi / r and 1e3 pi / r with a smoothed upper edge and differs from
+them below r ~ 0.05 and above r ~ 30.  ``_load_cache(file)`` of the reference's table reproduces the reference's numbers.
 """
 from os.path import dirname, join
 
@@ -105,6 +110,19 @@ class Corr21cm(corr.RedshiftCorrelation, maps.Sky3d):
         z1, z2 = self._band_redshifts()
         return self.realisation(z1, z2, self.x_width, self.y_width, self.nu_num, self.x_num, self.y_num,
                                 refinement=refinement, zspace=False, seed=seed)
+
+
+    def get_pwrspec(self, k_vec):
+        """The real-space power spectrum of the signal over the band, averaged over 256 slices (corr21cm.py:278-285)."""
+        z1, z2 = self._band_redshifts()
+        return self.powerspectrum_1D(k_vec, z1, z2, 256)
+
+    def get_kiyo_field_physical(self, refinement=1, density_only=False, no_mean=False, no_evolution=False, seed=None):
+        """A realisation in K with the physical box: ``(cube, rsf, (c1, c2, dx, dy))`` (corr21cm.py:287-310)."""
+        z1, z2 = self._band_redshifts()
+        return self.realisation(z1, z2, self.x_width, self.y_width, self.nu_num, self.x_num, self.y_num,
+                                refinement=refinement, zspace=False, report_physical=True, density_only=density_only,
+                                no_mean=no_mean, no_evolution=no_evolution, seed=seed)
 
 
 class EoR21cm(Corr21cm):

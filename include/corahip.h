@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook) */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -478,6 +478,21 @@ int corahip_xi_multi_average(corahip_ctx *ctx, const double *knots_x, const doub
                              int nm_rows, double *out);
 int corahip_cl_blocks(corahip_ctx *ctx, const double *packed, long L, int nfun, int F, double *out);
 
+/* ---- xi(pi, sigma; z1, z2) (csrc/rsdcorr.hip) -------------------------------------------------
+ * The flat-sky redshift-space correlation function of cora/signal/corr.py:274-348 at n points:
+ *   r = sqrt(pi^2 + sigma^2), mu = pi / (r + 1e-100), the nfun natural cubic splines on the shared knots knots_x [nk]
+ *   (knots_y, knots_y2 [nfun][nk]; all three on the device) at r - one interval search for all of them, the arithmetic
+ *   of xi_table_average kind 0, end-slope extrapolation below knots_x[0] and from knots_x[nk - 1] on - then
+ *     out = ((c0 dd0 + 2/3 c1 dv0 + 1/5 c2 vv0) - (4/3 c1 dv2 + 4/7 c2 vv2) P_2(mu) + 8/35 c2 vv4 P_4(mu)) c3.
+ *   nfun = 3: tables vv0 vv2 vv4, and dd0 = dv0 = vv0, dv2 = vv2.  nfun = 6: + dd0 dv0 dv2.  Any other nfun, nk < 4 or
+ *   nk > 2^24, ncoef < 1: CORAHIP_EINVAL.  coef [ncoef][4] (device) holds the rows (c0, c1, c2, c3) = (b1 b2,
+ *   (b1 f2 + b2 f1) / 2, f1 f2, D1 D2 pf1 pf2); point i reads row i % ncoef.  The tables are read through the caches from
+ *   interval records in context scratch (slot 12), rebuilt by every call; no LDS table.  One writer per element, no
+ *   atomics, the same bits from call to call; nothing is allocated once the scratch slot has its size. */
+int corahip_xi_rsd(corahip_ctx *ctx, const double *knots_x, const double *knots_y, const double *knots_y2, int nk,
+                   int nfun, const double *pi, const double *sigma, long n, const double *coef, long ncoef,
+                   double *out);
+
 /* ---- P(k) -> xi(r) (csrc/pk2xi.hip) --------------------------------------------------------
  * The numerical halves of corrfunc.ps_to_corr (cora/signal/corrfunc.py:72-84, 150-264).
  * sinc_romb:     out[j] = dlk romb_i(g[i] sinc(ka[i] r[j])) over the 2^k + 1 samples i, 1 <= k <= 24, unit spacing
@@ -494,6 +509,17 @@ int corahip_cl_blocks(corahip_ctx *ctx, const double *packed, long L, int nfun, 
 int corahip_sinc_romb(corahip_ctx *ctx, const double *g, const double *ka, int k, double dlk, const double *r,
                       int nr, double *out);
 int corahip_fftlog_phase(corahip_ctx *ctx, double mu, double L, int64_t N, double *u);
+
+/* jl_romb: the direct integral of sinc_romb for the orders l = 0, 2, 4 and nspec (1 to 3) integrands in one pass:
+ *   out[s][i][j] = dlk romb_n(g[s][n] j_{2i}(ka[n] r[j])), g [nspec][2^k + 1], out [nspec][3][nr] (device), 1 <= k <= 24.
+ *   lmask [nspec] (host): bit i set = order 2 i wanted; a slot whose bit is clear is written as +0.0.  x = ka r is
+ *   rounded once, its sine and cosine are computed once and shared by the orders and the integrands.  The l = 0 slot
+ *   has the bits of sinc_romb for the same g.  j_2, j_4: closed forms in sin / cos from x = 2 (4) on, the ascending
+ *   series below (11 and 13 terms): absolute error of one evaluation below 9.75 (14.7) x 2^-52.  r = 0 gives
+ *   dlk romb(g) for l = 0 and +0.0 for l = 2, 4.  Structure and summation order are sinc_romb's: a function of k alone,
+ *   a repeated call returns the same bits, nothing of size nr x 2^k is stored. */
+int corahip_jl_romb(corahip_ctx *ctx, const double *g, int nspec, const int *lmask, const double *ka, int k,
+                    double dlk, const double *r, int nr, double *out);
 int corahip_logconv(corahip_ctx *ctx, double *data, const double *u, int64_t N, int N1, int N2);
 int corahip_logconv_split(int64_t N, int *N1, int *N2);
 
