@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/corahip.h"
+#include "dev_buf.h"
 
 void corahip_set_error(const char *fmt, ...);
 
@@ -24,15 +25,15 @@ struct corahip_pending_event {
     hipEvent_t e0, e1;
 };
 
-// tables of one line-FFT length of the flat-sky engine (flatsky.hip); device pointers
+// tables of one line-FFT length of the flat-sky engine (flatsky.hip); device buffers
 struct corahip_linefft_plan {
     int n = 0, P = 0, logP = 0, blu = 0;
     int Pct = 0;               // Bluestein lengths: convolution length of the compile-time passes (flatsky_ct.hip), 0 = none
-    double2 *filt_ct = nullptr;   // [Pct] its filter, in the passes' storage order
-    double2 *tw = nullptr;     // [P]  exp(-2 pi i k / P)
-    double2 *chirp = nullptr;  // [n]  exp(-i pi k^2 / n)                       (Bluestein lengths only)
-    double2 *filt = nullptr;   // [P]  FFT_P(wrapped conj chirp) / P, bit-reversed (Bluestein lengths only)
-    double2 *rtw = nullptr;    // [n/2 + 1]  e^{+2 pi i k / 2n}: (un)packing of a real transform of length 2n
+    dev_buf<double2> filt_ct;     // [Pct] its filter, in the passes' storage order
+    dev_buf<double2> tw;       // [P]  exp(-2 pi i k / P)
+    dev_buf<double2> chirp;    // [n]  exp(-i pi k^2 / n)                       (Bluestein lengths only)
+    dev_buf<double2> filt;     // [P]  FFT_P(wrapped conj chirp) / P, bit-reversed (Bluestein lengths only)
+    dev_buf<double2> rtw;      // [n/2 + 1]  e^{+2 pi i k / 2n}: (un)packing of a real transform of length 2n
 };
 
 #define CORAHIP_NSCRATCH 13
@@ -41,9 +42,9 @@ struct corahip_ctx {
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;                 // second stream for kernels that run beside those of `stream` (K5 pair)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int *k5_tickets = nullptr;                     // K5: the item counters of the ticketed belt kernel (8 words, zeroed per call)
+    dev_buf<int> k5_tickets;                       // K5: the item counters of the ticketed belt kernel (8 words, zeroed per call)
     // the l-range pipeline of the numpy-stream draw (drawstream.hip): its generator stream and the ring's events
-    unsigned *draw_slot_tab = nullptr;             // K3: (l, m block) of every work slot of 0 .. draw_slot_lmax (draw.hip)
+    dev_buf<unsigned> draw_slot_tab;               // K3: (l, m block) of every work slot of 0 .. draw_slot_lmax (draw.hip)
     int draw_slot_lmax = -1;
     bool mt_plist_ready = false;                   // scratch slot 9 holds the position lists (mtlegacy.hip)
     hipStream_t gen_stream = nullptr;
@@ -58,7 +59,7 @@ struct corahip_ctx {
     std::vector<corahip_pending_event> pending;
     int num_cu = 256;
     size_t total_mem = 0;                          // device memory (bytes)
-    // grow-only device scratch slots owned by the context (freed by ctx_destroy)
+    // grow-only device scratch slots owned by the context
     // slots: 0 K1 transposed tables, 1 K1 pair results / odd-F normal stream, 2 K1 pair list, 3 zeros,
     //        4 Legendre matrix of legendre_project, 5 its zero-padded operand, 6 block tables of normals_pcg64 /
     //        segment tables of normals_mt19937_legacy, 7 the two-slot ring of the l-range pipeline (drawstream.hip),
@@ -67,7 +68,7 @@ struct corahip_ctx {
     //        12 spline records + interval lookup table of xi_multi_average (corrfunc.hip)
     //  written whole by every call that reads them: 1, 3, 4, 5, 6, 7, 8, 10, 11, 12; caches behind a host flag: 0
     //  (tt_valid), 2 (pairs_key / pairs_ptr), 9 (mt_plist_ready)
-    void *scratch[CORAHIP_NSCRATCH] = {};
+    dev_buf<char> scratch[CORAHIP_NSCRATCH];
     size_t scratch_bytes[CORAHIP_NSCRATCH] = {};
     // corahip_debug_poison_scratch (tests): the byte every newly allocated scratch slot and per-call device allocation
     // is filled with, -1 = none (the default)

@@ -556,22 +556,17 @@ int corahip_eig_top_batched(corahip_ctx *ctx, const double *C, int nl, int F, in
     if (list.empty()) return 0;
     const size_t per = (size_t)2 * F * F * sizeof(double);
     const size_t batch = std::max<size_t>(1, std::min<size_t>(list.size(), ((size_t)1 << 31) / per));
-    int32_t *dlist = nullptr;
-    double *scratch = nullptr;
-    HIP_TRY(hipMalloc((void **)&dlist, sizeof(int32_t) * list.size()));
-    if (hipMalloc((void **)&scratch, per * batch) != hipSuccess) {
-        (void)hipFree(dlist);
+    dev_buf<int32_t> dlist;
+    dev_buf<double> scratch;
+    HIP_TRY(dlist.alloc(list.size()));
+    if (scratch.alloc(per * batch / sizeof(double)) != hipSuccess) {
         corahip_set_error("eig_top_batched: no memory for the scratch of the full decomposition (%zu bytes)", per * batch);
         return CORAHIP_ENOMEM;
     }
     {
         int rcf = corahip_debug_fill(ctx, dlist, sizeof(int32_t) * list.size());
         if (!rcf) rcf = corahip_debug_fill(ctx, scratch, per * batch);
-        if (rcf) {
-            (void)hipFree(dlist);
-            (void)hipFree(scratch);
-            return rcf;
-        }
+        if (rcf) return rcf;
     }
     HIP_TRY(hipMemcpyAsync(dlist, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));
     const size_t shj = sizeof(double) * (2 * (F / 2 + 1) + JAC_NT + F) + sizeof(int) * (F + 4) + 16;
@@ -581,8 +576,6 @@ int corahip_eig_top_batched(corahip_ctx *ctx, const double *C, int nl, int F, in
         LAUNCH_CHECK();
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(dlist);
-    (void)hipFree(scratch);
     return 0;
 }
 

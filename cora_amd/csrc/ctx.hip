@@ -2,6 +2,7 @@
 #include "common.h"
 
 #include <cstring>
+#include <memory>
 
 static thread_local char g_err[512] = "";
 
@@ -15,10 +16,9 @@ void corahip_set_error(const char *fmt, ...) {
 int corahip_ctx_scratch(corahip_ctx *ctx, int slot, size_t bytes, void **out) {
     if (ctx->scratch_bytes[slot] < bytes) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch[slot]) HIP_TRY(hipFree(ctx->scratch[slot]));
-        ctx->scratch[slot] = nullptr;
         ctx->scratch_bytes[slot] = 0;
-        HIP_TRY(hipMalloc(&ctx->scratch[slot], bytes));
+        HIP_TRY(ctx->scratch[slot].reset());
+        HIP_TRY(ctx->scratch[slot].alloc(bytes));
         ctx->scratch_bytes[slot] = bytes;
         int rc = corahip_debug_fill(ctx, ctx->scratch[slot], bytes);
         if (rc) return rc;
@@ -62,13 +62,18 @@ int corahip_ctx_create(int device_id, corahip_ctx **out) {
                           prop.gcnArchName);
         return CORAHIP_ESTATE;
     }
-    corahip_ctx *c = new corahip_ctx();
+    std::unique_ptr<corahip_ctx> c(new corahip_ctx());
     c->device = device_id;
     c->num_cu = prop.multiProcessorCount;
     c->total_mem = prop.totalGlobalMem;
     HIP_TRY(hipEventCreate(&c->t0));
-    HIP_TRY(hipEventCreate(&c->t1));
-    *out = c;
+    const hipError_t e = hipEventCreate(&c->t1);
+    if (e != hipSuccess) {
+        (void)hipEventDestroy(c->t0);
+        corahip_set_error("hipEventCreate(&c->t1) failed: %s (%s:%d)", hipGetErrorString(e), __FILE__, __LINE__);
+        return (int)e;
+    }
+    *out = c.release();
     return 0;
 }
 
@@ -93,18 +98,7 @@ int corahip_ctx_destroy(corahip_ctx *ctx) {
         for (auto &e : ctx->ev_ring)
             if (e) (void)hipEventDestroy(e);
     }
-    for (int i = 0; i < CORAHIP_NSCRATCH; i++)
-        if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
-    if (ctx->draw_slot_tab) (void)hipFree(ctx->draw_slot_tab);
-    if (ctx->k5_tickets) (void)hipFree(ctx->k5_tickets);
-    for (auto &kv : ctx->linefft) {
-        if (kv.second.tw) (void)hipFree(kv.second.tw);
-        if (kv.second.chirp) (void)hipFree(kv.second.chirp);
-        if (kv.second.filt) (void)hipFree(kv.second.filt);
-        if (kv.second.filt_ct) (void)hipFree(kv.second.filt_ct);
-        if (kv.second.rtw) (void)hipFree(kv.second.rtw);
-    }
-    delete ctx;
+    delete ctx;   // its dev_buf members free the scratch slots and the cached tables
     return 0;
 }
 

@@ -515,15 +515,14 @@ static int draw_slot_table(corahip_ctx *ctx, int lmax, const unsigned **tab) {
     h.reserve((size_t)draw_slots(0, lmax));
     for (int l = lmax; l >= 0; l--)
         for (int mb = 0; mb <= l / DRAW_MB; mb++) h.push_back(((unsigned)l << 8) | (unsigned)mb);
-    if (ctx->draw_slot_tab) (void)hipFree(ctx->draw_slot_tab);
-    ctx->draw_slot_tab = nullptr;
+    (void)ctx->draw_slot_tab.reset();
     ctx->draw_slot_lmax = -1;
-    unsigned *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, sizeof(unsigned) * h.size()));
+    dev_buf<unsigned> d;
+    HIP_TRY(d.alloc(h.size()));
     HIP_TRY(hipMemcpy(d, h.data(), sizeof(unsigned) * h.size(), hipMemcpyHostToDevice));   // (synchronous: visible to every stream)
-    ctx->draw_slot_tab = d;
+    ctx->draw_slot_tab = std::move(d);
     ctx->draw_slot_lmax = lmax;
-    *tab = d;
+    *tab = ctx->draw_slot_tab;
     return 0;
 }
 

@@ -731,15 +731,6 @@ jacobi_root_kernel(const double *__restrict__ C, const int32_t *__restrict__ lis
     }
 }
 
-// device memory that is freed on every way out of the function that allocated it
-struct dev_mem {
-    void *p = nullptr;
-    dev_mem() = default;
-    dev_mem(const dev_mem &) = delete;
-    dev_mem &operator=(const dev_mem &) = delete;
-    ~dev_mem() { (void)hipFree(p); }
-};
-
 extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl, int F, double jitter_rel,
                                       double eig_thresh, double *T, int32_t *info) {
     ARG_CHECK(ctx != nullptr && C != nullptr && T != nullptr && info != nullptr);
@@ -839,16 +830,15 @@ extern "C" int corahip_factor_batched(corahip_ctx *ctx, const double *C, int nl,
     // process in batches bounded by scratch size (2 F^2 doubles per matrix)
     const size_t per = (size_t)2 * F * F * sizeof(double);
     const size_t batch = std::max<size_t>(1, std::min<size_t>(list.size(), ((size_t)1 << 31) / per));
-    dev_mem dlist_mem, scratch_mem;       // (freed behind the last kernel, or on an error return)
-    HIP_TRY(hipMalloc(&dlist_mem.p, sizeof(int32_t) * list.size()));
-    HIP_TRY(hipMalloc(&scratch_mem.p, per * batch));
+    dev_buf<int32_t> dlist;               // (both freed behind the last kernel, or on an error return)
+    dev_buf<double> scratch;
+    HIP_TRY(dlist.alloc(list.size()));
+    HIP_TRY(scratch.alloc(per * batch / sizeof(double)));
     {
-        int rcf = corahip_debug_fill(ctx, dlist_mem.p, sizeof(int32_t) * list.size());
-        if (!rcf) rcf = corahip_debug_fill(ctx, scratch_mem.p, per * batch);
+        int rcf = corahip_debug_fill(ctx, dlist, sizeof(int32_t) * list.size());
+        if (!rcf) rcf = corahip_debug_fill(ctx, scratch, per * batch);
         if (rcf) return rcf;
     }
-    int32_t *dlist = static_cast<int32_t *>(dlist_mem.p);
-    double *scratch = static_cast<double *>(scratch_mem.p);
     HIP_TRY(hipMemcpyAsync(dlist, list.data(), sizeof(int32_t) * list.size(), hipMemcpyHostToDevice, ctx->stream));
     const size_t shm = sizeof(double) * (2 * (F / 2 + 1) + JAC_NT + F) + sizeof(int) * (F + 4) + 16;
     for (size_t b0 = 0; b0 < list.size(); b0 += batch) {

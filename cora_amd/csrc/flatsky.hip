@@ -536,7 +536,7 @@ static int get_linefft_plan(corahip_ctx *ctx, int n, const corahip_linefft_plan 
         const long double a = -2.0L * PI * (long double)k / (long double)P;
         tw[k] = make_double2((double)cosl(a), (double)sinl(a));
     }
-    HIP_TRY(hipMalloc((void **)&pl.tw, sizeof(double2) * P));
+    HIP_TRY(pl.tw.alloc(P));
     HIP_TRY(hipMemcpy(pl.tw, tw.data(), sizeof(double2) * P, hipMemcpyHostToDevice));
     if (pl.blu) {
         std::vector<double2> chirp(n), filt(P);
@@ -555,9 +555,9 @@ static int get_linefft_plan(corahip_ctx *ctx, int n, const corahip_linefft_plan 
             for (int bit = 0; bit < pl.logP; bit++) r |= ((i >> bit) & 1u) << (pl.logP - 1 - bit);
             filt[i] = make_double2((double)(b[r].real() / P), (double)(b[r].imag() / P));
         }
-        HIP_TRY(hipMalloc((void **)&pl.chirp, sizeof(double2) * n));
+        HIP_TRY(pl.chirp.alloc(n));
         HIP_TRY(hipMemcpy(pl.chirp, chirp.data(), sizeof(double2) * n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void **)&pl.filt, sizeof(double2) * P));
+        HIP_TRY(pl.filt.alloc(P));
         HIP_TRY(hipMemcpy(pl.filt, filt.data(), sizeof(double2) * P, hipMemcpyHostToDevice));
         int rcb = flat_blu_plan(ctx, n, pl.chirp, &pl.Pct, &pl.filt_ct);   // (the compile-time convolution, where a schedule holds 2 n - 1)
         if (rcb) return rcb;
@@ -568,10 +568,10 @@ static int get_linefft_plan(corahip_ctx *ctx, int n, const corahip_linefft_plan 
             const long double a = PI * (long double)k / (long double)n;
             rtw[k] = make_double2((double)cosl(a), (double)sinl(a));
         }
-        HIP_TRY(hipMalloc((void **)&pl.rtw, sizeof(double2) * rtw.size()));
+        HIP_TRY(pl.rtw.alloc(rtw.size()));
         HIP_TRY(hipMemcpy(pl.rtw, rtw.data(), sizeof(double2) * rtw.size(), hipMemcpyHostToDevice));
     }
-    auto ins = ctx->linefft.emplace(n, pl);
+    auto ins = ctx->linefft.emplace(n, std::move(pl));
     *out = &ins.first->second;
     return 0;
 }

@@ -5,7 +5,7 @@
 #include "common.h"
 
 // plan time: the compile-time convolution length for an n-point Bluestein line and its filter; *Pct = 0: none
-int flat_blu_plan(corahip_ctx *ctx, int n, const double2 *chirp, int *Pct, double2 **filt_ct);
+int flat_blu_plan(corahip_ctx *ctx, int n, const double2 *chirp, int *Pct, dev_buf<double2> *filt_ct);
 // contiguous passes of an even real length 2 h
 int flat_c2r_ct(corahip_ctx *ctx, const double *spec, double *out, long nlines, int h, double scale, bool *took);
 int flat_r2c_ct(corahip_ctx *ctx, const double *in, double *spec, long nlines, int h, bool *took);

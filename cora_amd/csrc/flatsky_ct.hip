@@ -982,22 +982,19 @@ static int blu_filter_build(corahip_ctx *ctx, int n, const double2 *chirp, doubl
 }
 // plan time (flatsky.hip, get_linefft_plan of a Bluestein length): the compile-time convolution length for n and its
 // filter; *Pct = 0 when no schedule holds it
-int flat_blu_plan(corahip_ctx *ctx, int n, const double2 *chirp, int *Pct, double2 **filt_ct) {
+int flat_blu_plan(corahip_ctx *ctx, int n, const double2 *chirp, int *Pct, dev_buf<double2> *filt_ct) {
     *Pct = 0;
-    *filt_ct = nullptr;
+    (void)filt_ct->reset();
     const int P = flat_blu_length(n);
     if (!P || n < 17) return 0;
-    double2 *f = nullptr;
-    HIP_TRY(hipMalloc((void **)&f, sizeof(double2) * P));
+    dev_buf<double2> f;
+    HIP_TRY(f.alloc(P));
     bool built;
     const int rc = fft_shapes::dispatch<fft_shapes::LINE_BLU>([&](const line_shape &s) { return s.len == P; },
-                                                              [&](auto shape) { return blu_filter_build<shape.row.len>(ctx, n, chirp, f); }, &built);
-    if (rc) {
-        (void)hipFree(f);
-        return rc;
-    }
+                                                              [&](auto shape) { return blu_filter_build<shape.row.len>(ctx, n, chirp, f.get()); }, &built);
+    if (rc) return rc;
     *Pct = P;
-    *filt_ct = f;
+    *filt_ct = std::move(f);
     return 0;
 }
 template <int P, int NCH, int T>

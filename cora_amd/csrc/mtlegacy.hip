@@ -32,6 +32,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
@@ -567,7 +568,8 @@ int mt_stream_prepare(corahip_ctx *ctx, hipStream_t stream, corahip_mt_state *st
     ARG_CHECK(state != nullptr && n > 0 && state->pos >= 0 && state->pos <= MTN);
     ARG_CHECK(bounds.size() >= 2 && bounds.front() == 0 && bounds.back() == (unsigned long long)n);
     const bool other = stream != ctx->stream;
-    mt_session *s = new mt_session();
+    std::unique_ptr<mt_session> owner(new mt_session());     // freed on every failure below; handed out at the end
+    mt_session *s = owner.get();
     s->n = (unsigned long long)n;
     s->bounds = bounds;
     s->nr = (int)bounds.size() - 1;
@@ -586,7 +588,6 @@ int mt_stream_prepare(corahip_ctx *ctx, hipStream_t stream, corahip_mt_state *st
     if (levels > MT_NLEV) {
         corahip_set_error("normals_mt19937_legacy: %lld normals need %ld segments, the jump table holds %d radix-8 levels", (long long)n,
                           s->nseg, MT_NLEV);
-        delete s;
         return CORAHIP_EINVAL;
     }
     // the window at the generator's position: x[pos .. pos + 623] (host: at most 624 steps)
@@ -602,10 +603,7 @@ int mt_stream_prepare(corahip_ctx *ctx, hipStream_t stream, corahip_mt_state *st
     const size_t off_st = (off_first + sizeof(long) * nb + 15) & ~(size_t)15;
     char *ws = nullptr;
     int rc = corahip_ctx_scratch(ctx, 6, off_st + sizeof(mt_status), (void **)&ws);
-    if (rc) {
-        delete s;
-        return rc;
-    }
+    if (rc) return rc;
     s->seg_state = (unsigned *)ws;
     s->sub_state = (unsigned *)(ws + off_sub);
     s->sub_cnt = (unsigned *)(ws + off_cnt);
@@ -615,7 +613,6 @@ int mt_stream_prepare(corahip_ctx *ctx, hipStream_t stream, corahip_mt_state *st
     s->st = (mt_status *)(ws + off_st);
     auto fail = [&](hipError_t e, const char *what) {
         corahip_set_error("normals_mt19937_legacy: %s failed: %s", what, hipGetErrorString(e));
-        delete s;
         return (int)e;
     };
     hipError_t e;
@@ -629,10 +626,7 @@ int mt_stream_prepare(corahip_ctx *ctx, hipStream_t stream, corahip_mt_state *st
     {
         const size_t pb = sizeof(unsigned) * ((size_t)MT_NPOLY * MT_PLIST_STRIDE + MT_NPOLY);
         const bool fresh = ctx->scratch_bytes[9] < pb;
-        if (corahip_ctx_scratch(ctx, 9, pb, (void **)&plist_all)) {
-            delete s;
-            return CORAHIP_ENOMEM;
-        }
+        if (corahip_ctx_scratch(ctx, 9, pb, (void **)&plist_all)) return CORAHIP_ENOMEM;
         if (fresh || !ctx->mt_plist_ready) {
             mt_plist_kernel<<<MT_NPOLY, MT_JUMP_T, 0, stream>>>(plist_all, plist_all + (size_t)MT_NPOLY * MT_PLIST_STRIDE);
             // (later calls may run on another stream: the list must be complete before any of them can start)
@@ -672,7 +666,7 @@ int mt_stream_prepare(corahip_ctx *ctx, hipStream_t stream, corahip_mt_state *st
     }
     if ((e = hipGetLastError()) != hipSuccess) return fail(e, "a launch of the count pass");
     // numpy hands the cached value back and clears it; the state is rewritten by finish
-    *out = s;
+    *out = owner.release();
     return 0;
 }
 

@@ -40,6 +40,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <memory>
 
 #include "stream_internal.h"
 
@@ -1229,7 +1230,8 @@ struct zig_session {
 int zig_stream_prepare(corahip_ctx *ctx, hipStream_t stream, const uint64_t state[2], const uint64_t inc[2], int64_t n,
                        const std::vector<unsigned long long> &bounds, zig_session **out) {
     ARG_CHECK(n > 0 && bounds.size() >= 2 && bounds.front() == 0 && bounds.back() == (unsigned long long)n);
-    zig_session *s = new zig_session();
+    std::unique_ptr<zig_session> owner(new zig_session());   // freed on every failure below; handed out at the end
+    zig_session *s = owner.get();
     s->n = (unsigned long long)n;
     s->bounds = bounds;
     s->nr = (int)bounds.size() - 1;
@@ -1248,17 +1250,13 @@ int zig_stream_prepare(corahip_ctx *ctx, hipStream_t stream, const uint64_t stat
         hipError_t e = hipMemcpyAsync(s->d_bounds, s->bounds.data(), sizeof(unsigned long long) * nb, hipMemcpyHostToDevice, stream);
         if (e != hipSuccess) rc = (int)e;
     }
-    if (rc) {
-        delete s;
-        return rc;
-    }
+    if (rc) return rc;
     zig_range_kernel<<<(s->nr + 63) / 64, 64, 0, stream>>>(s->rd.entry, s->rd.nblk, s->d_bounds, s->nr, s->d_first);
     if (hipGetLastError() != hipSuccess) {
-        delete s;
         corahip_set_error("zig_range_kernel launch failed");
         return CORAHIP_ESTATE;
     }
-    *out = s;
+    *out = owner.release();
     return 0;
 }
 

@@ -34,48 +34,48 @@ struct corahip_sht_plan {
     int nside = 0, lmax = 0, L = 0, npair = 0, nring = 0;
     int cut_exp = 0;                                      // terms of the Legendre sums with |lambda_lm| < 2^cut_exp are dropped
     std::map<int, uint64_t> k4_macro_steps;               // by RT: macro-steps legendre_kernel executes per column group (lazy)
-    std::map<std::pair<int, int>, std::pair<int2 *, int>> k4_items;   // by (RT, column groups): legendre_kernel's list of non-empty items (lazy, sht_k4_items)
+    std::map<std::pair<int, int>, std::pair<dev_buf<int2>, int>> k4_items;   // by (RT, column groups): legendre_kernel's list of non-empty items (lazy, sht_k4_items)
     std::vector<int32_t> h_lmin;                          // host copy of d_lmin (lazy)
     long npix = 0, nalm = 0;
     std::vector<int64_t> h_start;
     std::vector<int32_t> h_nphi;
     std::vector<double> h_z, h_sth, h_phi0;
     // device
-    double *d_z = nullptr, *d_sth = nullptr;              // [npair] (north rings + equator)
-    int32_t *d_nphi = nullptr;                            // [nring]
-    int64_t *d_start = nullptr;                           // [nring]
-    double *d_phi0 = nullptr;                             // [nring]
-    double2 *d_coef = nullptr;                            // [nalm]: (A_l, B_l) at alm_idx(l,m)
-    int32_t *d_lstart = nullptr;                          // [L][npair]
-    double2 *d_seed = nullptr;                            // [L][npair]: (lambda_{lstart-1}, lambda_{lstart})
+    dev_buf<double> d_z, d_sth;                           // [npair] (north rings + equator)
+    dev_buf<int32_t> d_nphi;                              // [nring]
+    dev_buf<int64_t> d_start;                             // [nring]
+    dev_buf<double> d_phi0;                               // [nring]
+    dev_buf<double2> d_coef;                              // [nalm]: (A_l, B_l) at alm_idx(l,m)
+    dev_buf<int32_t> d_lstart;                            // [L][npair]
+    dev_buf<double2> d_seed;                              // [L][npair]: (lambda_{lstart-1}, lambda_{lstart})
     // the scalar synthesis kernel runs the recurrence in its two-instruction form mu_l = (alpha_l x) mu_{l-1} - mu_{l-2},
     // lambda_l = s_l mu_l (s_m = s_{m+1} = 1, s_l = B_l s_{l-2}, alpha_l = A_l s_{l-1} / s_l): its own coefficient and
     // seed tables (the spin-2 and the analysis kernels keep the (A, B) form)
-    double2 *d_coefmu = nullptr;                          // [nalm]: (alpha_l, s_l) at alm_idx(l,m)
-    double2 *d_seedmu = nullptr;                          // [L][npair]: (mu_{lstart-1}, mu_{lstart})
-    double2 *d_seed4 = nullptr;                           // [L][npair][4]: (mu_{R-2}, mu_{R-1}) in front of lane group kq's entry row R (seed_kernel)
-    std::map<int, double2 *> k4_segseed;                  // by RT: [L][npair][4] (mu_{R-2}, mu_{R-1}) in front of the entry row of legendre_kernel's lane group kq (lazy, sht_k4_segseed)
-    int32_t *d_lmin = nullptr;                            // [L][ntile] first l per (m, ring tile)
-    unsigned *d_queue = nullptr;                          // K4 work-queue head
-    int32_t *d_mcut = nullptr;                            // [nring] number of m with any non-negligible lambda_lm
-    double *d_polc = nullptr;                             // [nalm + 64][4] spin-2 coefficients (g1..g4), built on first use
-    double *d_zeros = nullptr;                            // 4 KiB of zeros (source of padding rows for LDS-DMA)
-    double2 *d_tw = nullptr;                              // e^{+2 pi i k/pmax}, k < pmax/2
+    dev_buf<double2> d_coefmu;                            // [nalm]: (alpha_l, s_l) at alm_idx(l,m)
+    dev_buf<double2> d_seedmu;                            // [L][npair]: (mu_{lstart-1}, mu_{lstart})
+    dev_buf<double2> d_seed4;                             // [L][npair][4]: (mu_{R-2}, mu_{R-1}) in front of lane group kq's entry row R (seed_kernel)
+    std::map<int, dev_buf<double2>> k4_segseed;           // by RT: [L][npair][4] (mu_{R-2}, mu_{R-1}) in front of the entry row of legendre_kernel's lane group kq (lazy, sht_k4_segseed)
+    dev_buf<int32_t> d_lmin;                              // [L][ntile] first l per (m, ring tile)
+    dev_buf<unsigned> d_queue;                            // K4 work-queue head
+    dev_buf<int32_t> d_mcut;                              // [nring] number of m with any non-negligible lambda_lm
+    dev_buf<double> d_polc;                               // [nalm + 64][4] spin-2 coefficients (g1..g4), built on first use
+    dev_buf<double> d_zeros;                              // 4 KiB of zeros (source of padding rows for LDS-DMA)
+    dev_buf<double2> d_tw;                                // e^{+2 pi i k/pmax}, k < pmax/2
     int pmax = 0, log_pmax = 0;
     // Bluestein tables, indexed by north-cap ring number i-1 (i = 1..nside-1)
-    int32_t *d_blu_P = nullptr;                           // [nside]: 0 = power-of-two ring
-    int64_t *d_blu_boff = nullptr, *d_blu_foff = nullptr; // offsets into chirp / filter arrays
-    double2 *d_bchirp = nullptr, *d_bfilt = nullptr;
+    dev_buf<int32_t> d_blu_P;                             // [nside]: 0 = power-of-two ring
+    dev_buf<int64_t> d_blu_boff, d_blu_foff;              // offsets into chirp / filter arrays
+    dev_buf<double2> d_bchirp, d_bfilt;
     // second set of Bluestein filters, stored in the order of the compile-time passes: for the rings whose compile-time
     // kernel (synthesis or analysis) runs a length with filters of its own (fft_shapes.h, RING_BLU rows marked `own`: a
     // 3 / 5 / 7 * 2^k length that still holds 2 h - 1, or 8192, whose pass order differs from the generic one).  The
     // run-time kernels, and the compile-time kernels of the other lengths, keep blu_P and the first set.
     std::vector<int32_t> h_ctfilt_len;                    // [nside]: 0 = none
-    int64_t *d_ctfilt_off = nullptr;
-    double2 *d_ctfilt = nullptr;
+    dev_buf<int64_t> d_ctfilt_off;
+    dev_buf<double2> d_ctfilt;
     // fold phases of the cap rings for the compile-time Bluestein kernels: e^{i t phi0(ring)}, t < 512, and the steps
     // e^{i 256 phi0}, e^{i 512 phi0}, by north-cap ring number i - 1
-    double2 *d_foldph = nullptr, *d_foldstep = nullptr;
+    dev_buf<double2> d_foldph, d_foldstep;
     int max_fft_len = 0;                                  // largest LDS FFT buffer (complex elems)
     // K5 launch classes: rings grouped by transform kind/length so each launch sizes its LDS
     struct ring_class {
@@ -89,7 +89,7 @@ struct corahip_sht_plan {
         int threads = 0;  // workgroup size (0: K5_THREADS)
         int bstride = 0;  // complex elements per channel buffer in LDS
         int count = 0;
-        int32_t *d_list = nullptr;
+        dev_buf<int32_t> d_list;
         std::vector<int32_t> h_list;   // host copy of the ring list (corahip_sht_plan_ring_classes)
     };
     std::vector<ring_class> classes;

@@ -788,9 +788,9 @@ static int ensure_polc(corahip_ctx *ctx, corahip_sht_plan *p) {
             o[2] = l > m ? (double)(n2 * (2.0L * ll + 1.0L) / al) : 0.0;
             o[3] = (double)(n2 * mm * (ll - 1.0L));
         }
-    HIP_TRY(hipMalloc((void **)&p->d_polc, sizeof(double) * g.size()));
-    HIP_TRY(hipMemcpyAsync(p->d_polc, g.data(), sizeof(double) * g.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    dev_buf<double> polc;
+    HIP_TRY(polc.upload(g, ctx->stream));
+    p->d_polc = std::move(polc);   // the guard above sees the table only once it is complete
     return 0;
 }
 

@@ -5,6 +5,7 @@
 #include "fft_shapes.h"
 
 #include <array>
+#include <memory>
 
 // ------------------------------------------------------------------------------------
 // plan-time kernels
@@ -419,16 +420,6 @@ bluestein_table_kernel(const int32_t *__restrict__ blu_P, const int64_t *__restr
 // ------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------
-template <typename T>
-static int dev_upload(T **dptr, const std::vector<T> &h, hipStream_t s) {
-    HIP_TRY(hipMalloc((void **)dptr, std::max<size_t>(1, h.size()) * sizeof(T)));
-    if (!h.empty()) {
-        HIP_TRY(hipMemcpyAsync(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-
 int sht_k4_items(corahip_ctx *ctx, const corahip_sht_plan *cp, int rt, int ncg, const int2 **items, int *nitems) {
     corahip_sht_plan *p = const_cast<corahip_sht_plan *>(cp);      // (lazy caches of the plan)
     const auto key = std::make_pair(rt, ncg);
@@ -454,11 +445,9 @@ int sht_k4_items(corahip_ctx *ctx, const corahip_sht_plan *cp, int rt, int ncg, 
                     for (int t128 = t_first; t128 <= t_last; t128++) lmin = std::min(lmin, p->h_lmin[(size_t)m * ntile128 + t128]);
                     if (lmin <= p->lmax) list.push_back(make_int2(m | (t << 15) | (cg << 23), lmin));
                 }
-        int2 *d = nullptr;
-        HIP_TRY(hipMalloc((void **)&d, sizeof(int2) * std::max<size_t>(1, list.size())));
-        HIP_TRY(hipMemcpyAsync(d, list.data(), sizeof(int2) * list.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        it = p->k4_items.emplace(key, std::make_pair(d, (int)list.size())).first;
+        dev_buf<int2> d;
+        HIP_TRY(d.upload(list, ctx->stream));
+        it = p->k4_items.emplace(key, std::make_pair(std::move(d), (int)list.size())).first;
     }
     *items = it->second.first;
     *nitems = it->second.second;
@@ -469,13 +458,13 @@ int sht_k4_segseed(corahip_ctx *ctx, const corahip_sht_plan *cp, int rt, const d
     corahip_sht_plan *p = const_cast<corahip_sht_plan *>(cp);      // (lazy caches of the plan)
     auto it = p->k4_segseed.find(rt);
     if (it == p->k4_segseed.end()) {
-        double2 *d = nullptr;
-        HIP_TRY(hipMalloc((void **)&d, sizeof(double2) * 4 * (size_t)p->L * p->npair));
-        it = p->k4_segseed.emplace(rt, d).first;                  // (owned by the plan from here on)
+        dev_buf<double2> d;
+        HIP_TRY(d.alloc(4 * (size_t)p->L * p->npair));
         dim3 grid((p->npair + 63) / 64, p->L);
         segseed_kernel<<<grid, 64, 0, ctx->stream>>>(p->lmax, p->npair, rt, p->d_z, p->d_coefmu, p->d_lstart, p->d_seed4,
                                                      p->d_lmin, d);
         LAUNCH_CHECK();
+        it = p->k4_segseed.emplace(rt, std::move(d)).first;
     }
     *segseed = it->second;
     return 0;
@@ -491,37 +480,7 @@ static int blu_pow2_length(int h) {
 extern "C" {
 
 int corahip_sht_plan_destroy(corahip_ctx *ctx, corahip_sht_plan *p) {
-    if (!p) return 0;
-    (void)hipFree(p->d_z);
-    (void)hipFree(p->d_sth);
-    (void)hipFree(p->d_nphi);
-    (void)hipFree(p->d_start);
-    (void)hipFree(p->d_phi0);
-    (void)hipFree(p->d_coef);
-    (void)hipFree(p->d_lstart);
-    (void)hipFree(p->d_seed);
-    (void)hipFree(p->d_coefmu);
-    (void)hipFree(p->d_seedmu);
-    (void)hipFree(p->d_seed4);
-    for (auto &kv : p->k4_items) (void)hipFree(kv.second.first);
-    for (auto &kv : p->k4_segseed) (void)hipFree(kv.second);
-    (void)hipFree(p->d_tw);
-    (void)hipFree(p->d_zeros);
-    (void)hipFree(p->d_lmin);
-    (void)hipFree(p->d_queue);
-    (void)hipFree(p->d_mcut);
-    (void)hipFree(p->d_polc);
-    (void)hipFree(p->d_blu_P);
-    (void)hipFree(p->d_blu_boff);
-    (void)hipFree(p->d_blu_foff);
-    (void)hipFree(p->d_ctfilt_off);
-    (void)hipFree(p->d_ctfilt);
-    (void)hipFree(p->d_bchirp);
-    (void)hipFree(p->d_bfilt);
-    (void)hipFree(p->d_foldph);
-    (void)hipFree(p->d_foldstep);
-    for (auto &c : p->classes) (void)hipFree(c.d_list);
-    delete p;
+    delete p;   // every device table is a dev_buf member
     return 0;
 }
 
@@ -545,8 +504,9 @@ int corahip_sht_plan_k4_mfma_count(corahip_ctx *ctx, const corahip_sht_plan *p, 
     auto it = p->k4_macro_steps.find(RT);
     if (it == p->k4_macro_steps.end()) {
         HIP_TRY(hipSetDevice(ctx->device));
-        unsigned long long *d_n = nullptr, h_n = 0;
-        HIP_TRY(hipMalloc((void **)&d_n, sizeof(h_n)));
+        unsigned long long h_n = 0;
+        dev_buf<unsigned long long> d_n;
+        HIP_TRY(d_n.alloc(1));
         HIP_TRY(hipMemsetAsync(d_n, 0, sizeof(h_n), ctx->stream));
         const int ntile = (p->npair + LEG_RINGS * RT - 1) / (LEG_RINGS * RT);
         const long total = (long)p->L * ntile * LEG_WAVES;
@@ -554,7 +514,6 @@ int corahip_sht_plan_k4_mfma_count(corahip_ctx *ctx, const corahip_sht_plan *p, 
         LAUNCH_CHECK();
         HIP_TRY(hipMemcpyAsync(&h_n, d_n, sizeof(h_n), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        (void)hipFree(d_n);
         it = const_cast<corahip_sht_plan *>(p)->k4_macro_steps.emplace(RT, (uint64_t)h_n).first;
     }
     *mfma_instructions = it->second * (uint64_t)(2 * NT * RT) * (uint64_t)(ncols / (16 * NT));
@@ -568,14 +527,9 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
     ARG_CHECK(cut_exp <= 0 && cut_exp >= -1000);
     if (cut_exp == 0) cut_exp = SEED_MIN_EXP;
     HIP_TRY(hipSetDevice(ctx->device));
-    corahip_sht_plan *p = new corahip_sht_plan();
     // every early return below (HIP_TRY / rc checks) releases what was allocated so far
-    struct plan_guard {
-        corahip_sht_plan *p;
-        ~plan_guard() {
-            if (p) corahip_sht_plan_destroy(nullptr, p);
-        }
-    } guard{p};
+    std::unique_ptr<corahip_sht_plan> guard(new corahip_sht_plan());
+    corahip_sht_plan *p = guard.get();
     p->nside = nside;
     p->lmax = lmax;
     p->cut_exp = cut_exp;
@@ -624,12 +578,12 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
     {
         std::vector<double> zz(p->h_z.begin(), p->h_z.begin() + p->npair);
         std::vector<double> ss(p->h_sth.begin(), p->h_sth.begin() + p->npair);
-        if ((rc = dev_upload(&p->d_z, zz, s))) return rc;
-        if ((rc = dev_upload(&p->d_sth, ss, s))) return rc;
+        HIP_TRY(p->d_z.upload(zz, s));
+        HIP_TRY(p->d_sth.upload(ss, s));
     }
-    if ((rc = dev_upload(&p->d_nphi, p->h_nphi, s))) return rc;
-    if ((rc = dev_upload(&p->d_start, p->h_start, s))) return rc;
-    if ((rc = dev_upload(&p->d_phi0, p->h_phi0, s))) return rc;
+    HIP_TRY(p->d_nphi.upload(p->h_nphi, s));
+    HIP_TRY(p->d_start.upload(p->h_start, s));
+    HIP_TRY(p->d_phi0.upload(p->h_phi0, s));
 
     // recurrence coefficients: lambda_l = A_l x lambda_{l-1} - B_l lambda_{l-2},
     // A_l = alpha_lm, B_l = alpha_lm/alpha_{l-1,m}, alpha_lm = sqrt((4l^2-1)/(l^2-m^2))
@@ -649,7 +603,7 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
                 aprev = al;
             }
         }
-        if ((rc = dev_upload(&p->d_coef, coef, s))) return rc;
+        HIP_TRY(p->d_coef.upload(coef, s));
         // scaled form: s_m = s_{m+1} = 1, s_l = B_l s_{l-2}; alpha_l = A_l s_{l-1} / s_l (alpha_m = 0: never used, the
         // recurrence starts from the seed at l >= m).  s_l stays within [~0.15, 1] (it tends to sqrt(A_inf / A_{m+1})).
         std::vector<double2> cmu(p->nalm + 32, make_double2(0.0, 0.0));
@@ -670,10 +624,10 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
                 s1 = sl;
             }
         }
-        if ((rc = dev_upload(&p->d_coefmu, cmu, s))) return rc;
+        HIP_TRY(p->d_coefmu.upload(cmu, s));
     }
     // |lambda_mm| prefactor sqrt((2m+1)!!/(4 pi (2m)!!))
-    double *d_pref = nullptr;
+    dev_buf<double> d_pref;
     {
         std::vector<double> pref(p->L);
         long double pr = 1.0L / sqrtl(4.0L * acosl(-1.0L));
@@ -682,12 +636,12 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             pr *= sqrtl((2.0L * m + 1.0L) / (2.0L * m));
             pref[m] = (double)pr;
         }
-        if ((rc = dev_upload(&d_pref, pref, s))) return rc;
+        HIP_TRY(d_pref.upload(pref, s));
     }
-    HIP_TRY(hipMalloc((void **)&p->d_lstart, sizeof(int32_t) * (size_t)p->L * p->npair));
-    HIP_TRY(hipMalloc((void **)&p->d_seed, sizeof(double2) * (size_t)p->L * p->npair));
-    HIP_TRY(hipMalloc((void **)&p->d_seedmu, sizeof(double2) * (size_t)p->L * p->npair));
-    HIP_TRY(hipMalloc((void **)&p->d_seed4, sizeof(double2) * 4 * (size_t)p->L * p->npair));
+    HIP_TRY(p->d_lstart.alloc((size_t)p->L * p->npair));
+    HIP_TRY(p->d_seed.alloc((size_t)p->L * p->npair));
+    HIP_TRY(p->d_seedmu.alloc((size_t)p->L * p->npair));
+    HIP_TRY(p->d_seed4.alloc(4 * (size_t)p->L * p->npair));
     {
         dim3 grid((p->npair + 63) / 64, p->L);
         seed_kernel<<<grid, 64, 0, s>>>(lmax, p->npair, cut_exp, p->d_z, p->d_sth, d_pref, p->d_coef, p->d_coefmu, p->d_lstart,
@@ -696,18 +650,18 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
     }
     {
         const int ntile = (p->npair + LMIN_RINGS - 1) / LMIN_RINGS;
-        HIP_TRY(hipMalloc((void **)&p->d_queue, 1024));   // 8 queue heads, 128 bytes apart
-        HIP_TRY(hipMalloc((void **)&p->d_mcut, sizeof(int32_t) * (size_t)p->nring));
+        HIP_TRY(p->d_queue.alloc(1024 / sizeof(unsigned)));   // 8 queue heads, 128 bytes apart
+        HIP_TRY(p->d_mcut.alloc((size_t)p->nring));
         mcut_kernel<<<(p->npair + 63) / 64, 64, 0, s>>>(lmax, p->npair, p->nring, p->d_lstart, p->d_mcut);
         LAUNCH_CHECK();
-        HIP_TRY(hipMalloc((void **)&p->d_lmin, sizeof(int32_t) * (size_t)p->L * ntile));
+        HIP_TRY(p->d_lmin.alloc((size_t)p->L * ntile));
         lmin_kernel<<<p->L, 64 * ((ntile + 63) / 64), 0, s>>>(lmax, p->npair, ntile, p->d_lstart, p->d_lmin);
         LAUNCH_CHECK();
     }
     HIP_TRY(hipStreamSynchronize(s));
-    (void)hipFree(d_pref);
+    (void)d_pref.reset();
 
-    HIP_TRY(hipMalloc((void **)&p->d_zeros, 4096));
+    HIP_TRY(p->d_zeros.alloc(4096 / sizeof(double)));
     HIP_TRY(hipMemsetAsync(p->d_zeros, 0, 4096, s));
     // FFT twiddles and Bluestein tables
     p->pmax = std::max(4 * nside, 4);
@@ -718,7 +672,7 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             const long double a = 2.0L * acosl(-1.0L) * k / p->pmax;
             tw[k] = make_double2((double)cosl(a), (double)sinl(a));
         }
-        if ((rc = dev_upload(&p->d_tw, tw, s))) return rc;
+        HIP_TRY(p->d_tw.upload(tw, s));
     }
     {
         std::vector<int32_t> bp(nside, 0);
@@ -737,11 +691,11 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             maxlen = std::max(maxlen, P);
         }
         p->max_fft_len = maxlen;
-        if ((rc = dev_upload(&p->d_blu_P, bp, s))) return rc;
-        if ((rc = dev_upload(&p->d_blu_boff, bo, s))) return rc;
-        if ((rc = dev_upload(&p->d_blu_foff, fo, s))) return rc;
-        HIP_TRY(hipMalloc((void **)&p->d_bchirp, sizeof(double2) * std::max<int64_t>(1, nb)));
-        HIP_TRY(hipMalloc((void **)&p->d_bfilt, sizeof(double2) * std::max<int64_t>(1, nf)));
+        HIP_TRY(p->d_blu_P.upload(bp, s));
+        HIP_TRY(p->d_blu_boff.upload(bo, s));
+        HIP_TRY(p->d_blu_foff.upload(fo, s));
+        HIP_TRY(p->d_bchirp.alloc(std::max<int64_t>(1, nb)));
+        HIP_TRY(p->d_bfilt.alloc(std::max<int64_t>(1, nf)));
         if (nside > 1) {
             const int tl_off = fpad_len(maxlen) + 1;
             const size_t shm = sizeof(double2) * (size_t)tl_off;
@@ -752,8 +706,8 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             LAUNCH_CHECK();
         }
     }
-    HIP_TRY(hipMalloc((void **)&p->d_foldph, sizeof(double2) * 512 * (size_t)nside));
-    HIP_TRY(hipMalloc((void **)&p->d_foldstep, sizeof(double2) * 2 * (size_t)nside));
+    HIP_TRY(p->d_foldph.alloc(512 * (size_t)nside));
+    HIP_TRY(p->d_foldstep.alloc(2 * (size_t)nside));
     if (nside > 1) {
         fold_phase_kernel<<<nside - 1, 512, 0, s>>>(p->d_phi0, p->d_foldph, p->d_foldstep);
         LAUNCH_CHECK();
@@ -773,8 +727,8 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
                 nf += own;
             }
         }
-        if ((rc = dev_upload(&p->d_ctfilt_off, fo, s))) return rc;
-        HIP_TRY(hipMalloc((void **)&p->d_ctfilt, sizeof(double2) * std::max<int64_t>(1, nf)));
+        HIP_TRY(p->d_ctfilt_off.upload(fo, s));
+        HIP_TRY(p->d_ctfilt.alloc(std::max<int64_t>(1, nf)));
         if (nf && (rc = sht_ctfilt_tables(ctx, p))) return rc;
     }
     // K5 ring classes
@@ -830,13 +784,12 @@ int corahip_sht_plan_create_ex(corahip_ctx *ctx, int nside, int lmax, int cut_ex
             if (c.blu && c.len <= 512) c.threads = c.len >= 512 ? 128 : 64;
             c.count = (int)kv.second.size();
             c.h_list = kv.second;
-            if ((rc = dev_upload(&c.d_list, kv.second, s))) return rc;
-            p->classes.push_back(c);
+            HIP_TRY(c.d_list.upload(kv.second, s));
+            p->classes.push_back(std::move(c));
         }
     }
     HIP_TRY(hipStreamSynchronize(s));
-    guard.p = nullptr;
-    *out = p;
+    *out = guard.release();
     return 0;
 }
 

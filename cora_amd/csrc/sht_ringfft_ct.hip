@@ -1106,7 +1106,7 @@ double sht_ringfft_item_weight(const corahip_sht_plan::ring_class &c) {
 }
 
 int sht_k5_tickets(corahip_ctx *ctx, hipStream_t stream) {
-    if (!ctx->k5_tickets) HIP_TRY(hipMalloc((void **)&ctx->k5_tickets, sizeof(int) * K5_NTICKETS));
+    if (!ctx->k5_tickets) HIP_TRY(ctx->k5_tickets.alloc(K5_NTICKETS));
     HIP_TRY(hipMemsetAsync(ctx->k5_tickets, 0, sizeof(int) * K5_NTICKETS, stream));
     return 0;
 }
@@ -1150,8 +1150,8 @@ blu3_filter_kernel(int nside, const int32_t *__restrict__ p3_of, const int64_t *
 // one launch per length with filters of its own that some ring of the plan uses (a workgroup per cap ring: those of
 // other lengths return at once)
 int sht_ctfilt_tables(corahip_ctx *ctx, corahip_sht_plan *p) {
-    int32_t *d_len = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_len, sizeof(int32_t) * p->h_ctfilt_len.size()));
+    dev_buf<int32_t> d_len;
+    HIP_TRY(d_len.alloc(p->h_ctfilt_len.size()));
     HIP_TRY(hipMemcpyAsync(d_len, p->h_ctfilt_len.data(), sizeof(int32_t) * p->h_ctfilt_len.size(), hipMemcpyHostToDevice, ctx->stream));
     for (const fft_shapes::ring_shape &s : fft_shapes::RING_BLU) {
         if (std::find(p->h_ctfilt_len.begin(), p->h_ctfilt_len.end(), s.len) == p->h_ctfilt_len.end()) continue;
@@ -1169,6 +1169,5 @@ int sht_ctfilt_tables(corahip_ctx *ctx, corahip_sht_plan *p) {
         if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(d_len);
     return 0;
 }
