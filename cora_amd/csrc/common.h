@@ -44,8 +44,8 @@ struct corahip_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     dev_buf<int> k5_tickets;                       // K5: the item counters of the ticketed belt kernel (8 words, zeroed per call)
     // the l-range pipeline of the numpy-stream draw (drawstream.hip): its generator stream and the ring's events
-    dev_buf<unsigned> draw_slot_tab;               // K3: (l, m block) of every work slot of 0 .. draw_slot_lmax (draw.hip)
-    int draw_slot_lmax = -1;
+    dev_buf<unsigned> draw_slot_tab[2];            // K3: (l, m block) of every work slot of 0 .. draw_slot_lmax, for blocks of
+    int draw_slot_lmax[2] = {-1, -1};              //     128 m ([0]) and of 64 m ([1], the wide shape) (draw.hip)
     bool mt_plist_ready = false;                   // scratch slot 9 holds the position lists (mtlegacy.hip)
     hipStream_t gen_stream = nullptr;
     hipEvent_t ev_ring[8] = {};

@@ -167,6 +167,17 @@ __device__ static inline void draw_glds16(const void *gsrc, unsigned lds_byte_ad
                  : "memory");
 }
 
+// same, with the source as a wave-uniform base (SGPR pair) + a 32-bit per-lane byte offset: the address of a piece is
+// then scalar arithmetic (every vector instruction next to the FP64 MFMAs costs issue time)
+__device__ static inline void draw_glds16_s(const void *sbase, unsigned lane_byte_off, unsigned lds_byte_addr) {
+    unsigned keep;
+    const unsigned dst = __builtin_amdgcn_readfirstlane(lds_byte_addr);
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(lane_byte_off), "s"(sbase), "s"(dst)
+                 : "memory");
+}
+
 #ifndef DRAW_STAMPS
 #define DRAW_STAMPS 0   // diagnostic build (make ab ... DEFS=-DDRAW_STAMPS=1): s_memtime per phase, summed over all waves
 #endif
@@ -181,10 +192,16 @@ __device__ unsigned long long g_draw_stamps[8];
 #define DRAW_MB (16 * DRAW_WAVES)    // m per work item
 #define DRAW_NBUF 3                  // stages in the LDS ring
 
-// number of (l, m-block) slots of the multipoles l_lo .. l_hi: l in band j = l >> 7 has j + 1 blocks of 128 m
-static inline long draw_slots(int l_lo, int l_hi) {
+#define DRAW_WNCT 16                 // column tiles of the wide shape (draw_wide_kernel): 256 channels per item
+#define DRAW_WMB (8 * DRAW_WAVES)    // m per work item of the wide shape
+#ifndef DRAW_WIDE
+#define DRAW_WIDE 1   // 0 (make ab ... DEFS=-DDRAW_WIDE=0): launches of more than 128 columns stay on the 128-column shape
+#endif
+
+// number of (l, m-block) slots of the multipoles l_lo .. l_hi: l has l / mb + 1 blocks of mb m
+static inline long draw_slots(int l_lo, int l_hi, int mb = DRAW_MB) {
     long n = 0;
-    for (int l = l_lo; l <= l_hi; l++) n += (l / DRAW_MB) + 1;
+    for (int l = l_lo; l <= l_hi; l++) n += (l / mb) + 1;
     return n;
 }
 
@@ -498,42 +515,290 @@ draw_rng_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int3
 #endif
 }
 
+// ------------------------------------------------------------------------------------
+// The wide shape of the fused-RNG kernel (Philox mode, launches whose widest channel chunk has more than 128 columns):
+// every normal is generated ONCE for 256 channels, where the 128-column shape generates nu' < 128 for its first column
+// group and nu' < 256 again for its second (1.5 x the normals at F = 256, 2.5 x at F = 512).
+//
+// Work item = (l, block of 64 m, column group of 256 channels).  Wave tile = 16 MFMA rows x 16 column tiles, the rows
+// being 8 m x (re, im) INTERLEAVED: row 2 m_local + c.  The real and the imaginary plane share one MFMA tile, so the
+// accumulators are d4_t acc[16] - the 128 registers the 128-column shape spends on acc0[8] + acc1[8] (two planes of 256
+// columns need 256 and spilled: HISTORY.md, round 6).
+//
+// One Philox / Box-Muller pair per lane serves TWO k-steps: for the k-step pair j lane (ri, kq) generates
+// (m = mw + (ri >> 1), nu' = k0 + 8 j + 4 (ri & 1) + kq) and trades one double with lane ri ^ 1 (DPP quad_perm [1,0,3,2]):
+// the even (real) row takes (own re, partner's re) as the A operands of k-steps 2 j and 2 j + 1, the odd (imaginary)
+// row (partner's im, own im).  Slot kq of k-step kk therefore holds nu' = k0 + 4 kk + kq and the k-steps run in
+// ascending order, exactly as in the 128-column shape: every a_lm value has the bits it has there (the sharded ranks,
+// which run the narrow shapes, and the 1-rank step agree bit for bit).
+//
+// T_l: two stages of 64 KB (256 channels x 32 nu'), same swizzle as above.  The wait in front of a chunk is vmcnt(0);
+// stage c + 1 is requested right behind the barrier of chunk c (every wave has then finished chunk c - 1, whose slot it
+// takes) and has the whole chunk to land; the first stage of the next item is requested ahead of this item's stores.
+// The waits being uncounted, a chunk of the triangular tail stages only the row quads of the tiles it multiplies.
+// Epilogue: lane (ri, kq) holds c = kq & 1 of m = mw + (kq >> 1) + 2 r, channel 16 t + ri: one 8-byte store instruction
+// of a wave writes 2 m x 4 whole 64-byte cells.
+// ------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64 * DRAW_WAVES, 2)
+draw_wide_kernel(const double *__restrict__ T, size_t t_ldl, int rows, const int32_t *__restrict__ info,
+                 const double *__restrict__ zeros, uint64_t seed, int lmax, int F, int nu0, int nu1, int cw, int nnu, int Gout,
+                 int nslots, int ncg0, int ncg, double *__restrict__ alm, unsigned *__restrict__ queue,
+                 const unsigned *__restrict__ slot_tab) {
+    constexpr int NCT = DRAW_WNCT, NC = 16 * NCT;
+    constexpr int ROWD = DRAW_KC;            // doubles per channel row in LDS (as in draw_rng_kernel, with its swizzle)
+    constexpr int BUF = NC * ROWD;           // doubles per stage
+    constexpr int QPW = NC / 4 / DRAW_WAVES; // row quads (= DMA instructions) a wave issues per full stage
+    extern __shared__ __attribute__((aligned(16))) double lds[];  // [2][NC][ROWD]
+    __shared__ double2 lg_s[257], sc_s[256];   // LDS copies of the Box-Muller tables (rng_dev.h): 8 KB
+    __shared__ int s_next[2];                  // next work item, double-buffered (written one item ahead)
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ri = lane & 15, kq = lane >> 4;
+    const bool odd = ri & 1;                   // this lane's MFMA row is an imaginary part
+    const int nitems = nslots * ncg;
+    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) double *)lds;
+#if DRAW_STAMPS
+    unsigned long long d_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, d_last;
+    { unsigned long long _t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory"); d_last = _t; }
+#endif
+
+    // items, channels and column groups as in draw_rng_kernel, with 256-channel groups and blocks of 64 m
+    struct item_t {
+        int l, mb, base0, lbase, lend, kmax, nchunk, c_full;
+        bool tri_tail;
+        const double *Tl;
+    };
+    auto decode = [&](int it) {
+        item_t w;
+        const int cg = ncg - 1 - it / nslots;          // the column groups with the longest nu' range first
+        const int s = it - (it / nslots) * nslots;
+        const unsigned e = slot_tab[s];
+        const int l = (int)(e >> 8), mb = (int)(e & 255u);
+        w.l = l;
+        w.mb = mb;
+        const bool second = cg >= ncg0;
+        w.lbase = second ? cw + (cg - ncg0) * NC : cg * NC;
+        w.lend = second ? nnu : min(cw, nnu);
+        w.base0 = second ? nu1 + (cg - ncg0) * NC : nu0 + cg * NC;
+        const bool dense = (info == nullptr) || (info[l] != 0);
+        w.kmax = dense ? F : min(F, w.base0 + NC);
+        w.nchunk = (w.kmax + DRAW_KC - 1) / DRAW_KC;
+        // the triangular tail: chunk c_full + J multiplies the tiles 2 J .. (first half) and 2 J + 1 .. (second half)
+        w.tri_tail = !dense && (w.base0 % DRAW_KC) == 0;
+        w.c_full = w.tri_tail ? min(w.nchunk, w.base0 / DRAW_KC) : w.nchunk;
+        w.Tl = T + (size_t)l * t_ldl + (size_t)(rows ? w.lbase : w.base0) * F;
+        return w;
+    };
+    // stage chunk c of the item into ring slot `slot`, from piece FIRST on: piece `it` of a wave holds the rows
+    // 4 (wave + 8 it) .. + 3, and chunk c_full + J of the triangular tail multiplies no tile below 2 J, i.e. needs no
+    // piece below J.  Row n & 15 - the swizzle - does not depend on `it`, so a lane's source is a wave-uniform base (row
+    // 32 it of the item, nu' k0) plus a byte offset that is fixed for the kernel: a stage whose 256 rows all hold channels
+    // and whose 32 nu' are all below F - every stage of an F = 256 or 512 step - is issued from scalar arithmetic alone
+    // (every vector instruction next to the FP64 MFMAs costs issue time).  The other stages go lane by lane as in
+    // draw_rng_kernel.
+    const int n_lane = 4 * wave + (lane >> 4), slot_lane = (lane & 15) ^ (n_lane & 15);
+    const unsigned src_lane_off = (unsigned)(((size_t)n_lane * F + 2 * slot_lane) * sizeof(double));
+    auto stage = [&](const item_t &w, int c, int slot, auto first_c) {
+        constexpr int FIRST = decltype(first_c)::value;
+        const int k0 = c * DRAW_KC;
+        const int n_valid = min(w.lend - w.lbase, F - w.base0);            // rows of the item that hold channels
+        const unsigned dst = lds_base + (unsigned)((slot * BUF + 4 * wave * ROWD) * sizeof(double));
+        constexpr unsigned DST_STEP = 4 * DRAW_WAVES * ROWD * sizeof(double);
+        if (n_valid >= NC && k0 + DRAW_KC <= F) {
+            const double *src = w.Tl + k0;
+#pragma unroll
+            for (int it = FIRST; it < QPW; it++) draw_glds16_s(src + (size_t)(4 * DRAW_WAVES * it) * F, src_lane_off, dst + it * DST_STEP);
+        } else {
+#pragma unroll
+            for (int it = FIRST; it < QPW; it++) {
+                const int n = n_lane + 4 * DRAW_WAVES * it;     // row of this lane
+                const int k = k0 + 2 * slot_lane;
+                const double *src = zeros;  // F is even on this path (host wrapper), so k + 1 < F whenever k < F
+                if (n < n_valid && k + 1 < F) src = w.Tl + (size_t)n * F + k;
+                draw_glds16(src, dst + it * DST_STEP);
+            }
+        }
+    };
+    constexpr std::integral_constant<int, 0> whole_stage{};
+
+    for (int i = tid; i < 257; i += 64 * DRAW_WAVES) lg_s[i] = RNG_LOG_TAB[i];   // (visible after the first barrier)
+    for (int i = tid; i < 256; i += 64 * DRAW_WAVES) sc_s[i] = RNG_SC_TAB[i];
+
+    int item = blockIdx.x;      // the first gridDim.x items are pre-assigned; the queue starts behind them
+    if (item >= nitems) return;
+    item_t w = decode(item);
+    int ring = 0, par = 0;
+    stage(w, 0, 0, whole_stage);
+    DSTAMP(0);                           // prologue + first stage issued
+
+    for (;;) {
+        if (tid == 0) s_next[par] = (int)(gridDim.x + atomicAdd(queue, 1u));   // latency hidden behind this item
+        const int l = w.l, lp1 = w.l + 1;
+        const int mw = w.mb * DRAW_WMB + 8 * wave;     // first m of this wave
+        const bool wave_has_rows = mw < lp1;
+        const int m_lane = mw + (ri >> 1);             // the m of this lane's A-operand row
+        const int kmax = w.kmax, nchunk = w.nchunk;
+        d4_t acc[NCT];                                 // rows 2 m_local + c = kq + 4 r, channel 16 t + ri
+#pragma unroll
+        for (int t = 0; t < NCT; t++) acc[t] = (d4_t){0.0, 0.0, 0.0, 0.0};
+        // the two k-step pairs of one half (16 nu') of the chunk in buffer `sb`, multiplying the tiles TMIN .. NCT-1
+        auto half_steps = [&](auto tmin_c, const double *sb, int k0, auto half_c) {
+            constexpr int TMIN = decltype(tmin_c)::value;
+            constexpr int half = decltype(half_c)::value;
+#pragma unroll
+            for (int j = 2 * half; j < 2 * half + 2; j++) {
+                // (rows past l and nu' >= F are generated like any other: their products meet staged zeros or are never stored)
+                const double2 g = philox_normal_pair(seed, l, F, k0 + 8 * j + (odd ? 4 : 0) + kq, m_lane, lg_s, sc_s);
+                const double give = odd ? g.x : g.y;
+                int lo = __double2loint(give), hi = __double2hiint(give);
+                lo = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xF, 0xF, false);   // quad_perm [1, 0, 3, 2]: lane ri ^ 1
+                hi = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xF, 0xF, false);
+                const double got = __hiloint2double(hi, lo);
+                const double a[2] = {odd ? got : g.x, odd ? g.y : got};
+#pragma unroll
+                for (int s = 0; s < 2; s++) {
+                    const int kl = 8 * j + 4 * s + kq;   // k within the chunk
+                    const double *brow = sb + ri * ROWD + 2 * ((kl >> 1) ^ ri) + (kl & 1);
+                    // the B operands in two groups of eight tiles (all sixteen up front do not fit the register budget)
+#pragma unroll
+                    for (int t0 = 0; t0 < NCT; t0 += 8) {
+                        double bv[8];
+#pragma unroll
+                        for (int t = t0; t < t0 + 8; t++)
+                            if (t >= TMIN) bv[t - t0] = brow[16 * t * ROWD];
+#pragma unroll
+                        for (int t = t0; t < t0 + 8; t++)
+                            if (t >= TMIN) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], bv[t - t0], acc[t], 0, 0, 0);
+                    }
+                }
+            }
+        };
+        // Chunk c of the item sits in ring slot (ring + c) % 2 and was requested one chunk (or one item end) ago
+        // (next_first: the first piece of stage c + 1, see stage)
+        auto chunk_begin = [&](int c, auto next_first) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+#if DRAW_STAMPS
+            if (c == 0) { DSTAMP(6); } else
+#endif
+            DSTAMP(1);                       // wait for the stage + barrier (stamp 6: the first chunk of an item, which also waits for the previous item's stores)
+            if (c + 1 < nchunk) stage(w, c + 1, (ring + c + 1) & 1, next_first);
+            DSTAMP(2);                       // issue of the next stage
+        };
+        int c = 0;
+        for (; c < w.c_full; c++) {
+            chunk_begin(c, whole_stage);     // (the next chunk is a full one or chunk 0 of the tail)
+            if (!wave_has_rows) continue;
+            const double *sb = lds + ((ring + c) & 1) * BUF;
+            half_steps(std::integral_constant<int, 0>{}, sb, c * DRAW_KC, std::integral_constant<int, 0>{});
+            if (c * DRAW_KC + 16 < kmax) half_steps(std::integral_constant<int, 0>{}, sb, c * DRAW_KC, std::integral_constant<int, 1>{});
+            DSTAMP(3);                       // generator + exchange + MFMAs of the chunk
+        }
+        static_for<NC / DRAW_KC>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            if (c >= nchunk) return;         // (uniform; also the dense / unaligned case, where c == nchunk here)
+            chunk_begin(c, std::integral_constant<int, (J + 1 < QPW ? J + 1 : QPW)>{});
+            if (wave_has_rows) {
+                const double *sb = lds + ((ring + c) & 1) * BUF;
+                half_steps(std::integral_constant<int, 2 * J>{}, sb, c * DRAW_KC, std::integral_constant<int, 0>{});
+                if (c * DRAW_KC + 16 < kmax)
+                    half_steps(std::integral_constant<int, 2 * J + 1>{}, sb, c * DRAW_KC, std::integral_constant<int, 1>{});
+                DSTAMP(3);
+            }
+            c++;
+        });
+
+        // ---- next item: its first stage is requested now, ahead of this item's stores.  Every wave has passed the barrier
+        //      of the last chunk, so the slot of the chunk before it is free.
+        ring = (ring + nchunk) & 1;
+        const int cur_lbase = w.lbase, cur_lend4 = (w.lend + 3) & ~3;
+        item = __builtin_amdgcn_readfirstlane(s_next[par]);   // (written before this item's first barrier)
+        par ^= 1;
+        const bool have_next = item < nitems;
+        if (have_next) {
+            w = decode(item);
+            stage(w, 0, ring, whole_stage);
+        }
+        DSTAMP(4);                           // next item decoded, its first stage issued
+
+        // ---- epilogue: 1/sqrt(2) of complex_std_normal.  One row pointer per r, the tiles at immediate offsets (a tile is
+        //      four cells = 256 bytes on); the channel test of a tile is made once for its four stores.
+        if (wave_has_rows) {
+            const double sc = 0.70710678118654752440;
+            double *cell[4];
+            bool m_ok[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m = mw + (kq >> 1) + 2 * r;
+                const long idx = (long)m * (2 * lmax + 1 - m) / 2 + l;
+                m_ok[r] = m < lp1;
+                // (lbase is a multiple of 4: the cell of the lane's channel in tile 0)
+                cell[r] = alm + ((size_t)idx * Gout + ((cur_lbase + (ri & ~3)) >> 2)) * 8 + 4 * (kq & 1) + (ri & 3);
+            }
+            const int ncol_lane = cur_lend4 - cur_lbase - (ri & ~3);   // the lane's cell of tile t is inside the chunk if 16 t < this
+#pragma unroll
+            for (int t = 0; t < NCT; t++) {
+                const bool col_ok = 16 * t < ncol_lane;                // (the chunk's end rounded up to a cell: the whole cell or none)
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+                    if (col_ok && m_ok[r]) cell[r][32 * t] = acc[t][r] * sc;
+            }
+        }
+        DSTAMP(5);                           // epilogue (scale, a_lm stores issued)
+        if (!have_next) break;
+    }
+#if DRAW_STAMPS
+    if (lane == 0) {
+        for (int k = 0; k < 7; k++) atomicAdd(&g_draw_stamps[k], d_acc[k]);
+        atomicAdd(&g_draw_stamps[7], 1ull);
+    }
+#endif
+}
+
 // l_lo .. l_hi: the multipoles of this launch (0 .. lmax: all); FROMG: gsrc[0] is element g_off of the stream-order
 // buffer; `stream`: where the launch goes (the context's stream, or the draw stream of the l-range pipeline)
 // chan: the launch's channels {nu0, nu1, cw, nnu} (see the kernel); rows: T holds the row block of the local channels
 struct draw_chan {
     int nu0, nu1, cw, nnu;
 };
-// (l, m block) of every slot of the range 0 .. lmax in the order the kernel takes them: l from lmax down, the l / 128 + 1
-// blocks of an l in order; entry = l << 8 | block.  Built once per lmax, kept in the context.
-static int draw_slot_table(corahip_ctx *ctx, int lmax, const unsigned **tab) {
-    if (ctx->draw_slot_tab && ctx->draw_slot_lmax == lmax) {
-        *tab = ctx->draw_slot_tab;
+// (l, m block) of every slot of the range 0 .. lmax in the order the kernel takes them: l from lmax down, the l / mb + 1
+// blocks of an l in order; entry = l << 8 | block.  Built once per lmax and block size (128 m, or 64 m for the wide
+// shape), kept in the context.
+static int draw_slot_table(corahip_ctx *ctx, int lmax, int mb, const unsigned **tab) {
+    const int which = mb == DRAW_MB ? 0 : 1;
+    if (ctx->draw_slot_tab[which] && ctx->draw_slot_lmax[which] == lmax) {
+        *tab = ctx->draw_slot_tab[which];
         return 0;
     }
     std::vector<unsigned> h;
-    h.reserve((size_t)draw_slots(0, lmax));
+    h.reserve((size_t)draw_slots(0, lmax, mb));
     for (int l = lmax; l >= 0; l--)
-        for (int mb = 0; mb <= l / DRAW_MB; mb++) h.push_back(((unsigned)l << 8) | (unsigned)mb);
-    (void)ctx->draw_slot_tab.reset();
-    ctx->draw_slot_lmax = -1;
+        for (int b = 0; b <= l / mb; b++) h.push_back(((unsigned)l << 8) | (unsigned)b);
+    (void)ctx->draw_slot_tab[which].reset();
+    ctx->draw_slot_lmax[which] = -1;
     dev_buf<unsigned> d;
     HIP_TRY(d.alloc(h.size()));
     HIP_TRY(hipMemcpy(d, h.data(), sizeof(unsigned) * h.size(), hipMemcpyHostToDevice));   // (synchronous: visible to every stream)
-    ctx->draw_slot_tab = std::move(d);
-    ctx->draw_slot_lmax = lmax;
-    *tab = ctx->draw_slot_tab;
+    ctx->draw_slot_tab[which] = std::move(d);
+    ctx->draw_slot_lmax[which] = lmax;
+    *tab = ctx->draw_slot_tab[which];
     return 0;
 }
 
-template <int NCT, bool FROMG = false, int NB = DRAW_NBUF>
+// NCT = DRAW_WNCT: the wide shape (Philox mode only)
+template <int NCT, bool FROMG = false>
 static int launch_draw_rng(corahip_ctx *ctx, hipStream_t stream, const double *T, size_t t_ldl, int rows, const int32_t *info,
                            uint64_t seed, const double *gsrc, size_t g_off, int l_lo, int l_hi, int lmax, int F,
                            draw_chan ch, int Gout, double *alm) {
-    constexpr int NC = 16 * NCT;
+    constexpr bool WIDE = NCT == DRAW_WNCT;
+    static_assert(!(WIDE && FROMG), "the wide shape generates its normals");
+    constexpr int NC = 16 * NCT, MB = WIDE ? DRAW_WMB : DRAW_MB, NB = WIDE ? 2 : DRAW_NBUF;
     const size_t shm = sizeof(double) * NB * NC * DRAW_KC;
-    HIP_TRY(hipFuncSetAttribute((const void *)draw_rng_kernel<NCT, FROMG, NB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)shm));
+    const void *kernel;
+    if constexpr (WIDE) kernel = (const void *)draw_wide_kernel;
+    else kernel = (const void *)draw_rng_kernel<NCT, FROMG, NB>;
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     // scratch slot 3: 4096 bytes of zeros (DMA source of padded rows) + the work queue counter behind them
     char *zq = nullptr;
     int rc = corahip_ctx_scratch(ctx, 3, 8192, (void **)&zq);
@@ -541,19 +806,24 @@ static int launch_draw_rng(corahip_ctx *ctx, hipStream_t stream, const double *T
     HIP_TRY(hipMemsetAsync(zq, 0, 8192, stream));
     const int n0 = std::min(ch.cw, ch.nnu), n1 = ch.nnu - n0;
     const int ncg0 = (((n0 + 3) & ~3) + NC - 1) / NC, ncg = ncg0 + (((n1 + 3) & ~3) + NC - 1) / NC;
-    const long nslots = draw_slots(l_lo, l_hi);
+    const long nslots = draw_slots(l_lo, l_hi, MB);
     const long nitems = nslots * ncg;
-    ARG_CHECK(nitems < (1L << 30) && lmax < (1 << 24) && lmax / DRAW_MB < 256);
+    ARG_CHECK(nitems < (1L << 30) && lmax < (1 << 24) && lmax / MB < 256);
     const unsigned *slot_tab = nullptr;
-    if ((rc = draw_slot_table(ctx, lmax, &slot_tab))) return rc;
-    slot_tab += l_hi < lmax ? draw_slots(l_hi + 1, lmax) : 0;      // the launch's run of the table starts at its l_hi
-    // persistent: one workgroup per CU for the 128-channel shape (106 KB of LDS), two for the narrower ones
+    if ((rc = draw_slot_table(ctx, lmax, MB, &slot_tab))) return rc;
+    slot_tab += l_hi < lmax ? draw_slots(l_hi + 1, lmax, MB) : 0;      // the launch's run of the table starts at its l_hi
+    // persistent: one workgroup per CU for the 128- and 256-channel shapes (106 / 139 KB of LDS), two for the narrower ones
     const int per_cu = (shm + 8300 > 80 * 1024) ? 1 : 2;
     dim3 grid((unsigned)std::min<long>(nitems, (long)ctx->num_cu * per_cu));
-    draw_rng_kernel<NCT, FROMG, NB><<<grid, 64 * DRAW_WAVES, shm, stream>>>(T, t_ldl, rows, info, (const double *)zq, seed, gsrc,
-                                                                        g_off, l_lo, l_hi, lmax, F, ch.nu0, ch.nu1, ch.cw,
-                                                                        ch.nnu, Gout, (int)nslots, ncg0, ncg, alm,
-                                                                        (unsigned *)(zq + 4096), slot_tab);
+    if constexpr (WIDE)
+        draw_wide_kernel<<<grid, 64 * DRAW_WAVES, shm, stream>>>(T, t_ldl, rows, info, (const double *)zq, seed, lmax, F, ch.nu0,
+                                                                ch.nu1, ch.cw, ch.nnu, Gout, (int)nslots, ncg0, ncg, alm,
+                                                                (unsigned *)(zq + 4096), slot_tab);
+    else
+        draw_rng_kernel<NCT, FROMG, NB><<<grid, 64 * DRAW_WAVES, shm, stream>>>(T, t_ldl, rows, info, (const double *)zq, seed, gsrc,
+                                                                            g_off, l_lo, l_hi, lmax, F, ch.nu0, ch.nu1, ch.cw,
+                                                                            ch.nnu, Gout, (int)nslots, ncg0, ncg, alm,
+                                                                            (unsigned *)(zq + 4096), slot_tab);
     LAUNCH_CHECK();
 #if DRAW_STAMPS
     {
@@ -683,6 +953,9 @@ static int draw_philox(corahip_ctx *ctx, const double *T, int rows, const int32_
     const int Gout = (ch.nnu + 3) / 4;
     const size_t t_ldl = rows ? (size_t)ch.nnu * F : (size_t)F * F;
     const int ncol = chan_ncol(ch);
+#if DRAW_WIDE
+    if (ncol > 128) return launch_draw_rng<DRAW_WNCT>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
+#endif
     if (ncol <= 16) return launch_draw_rng<1>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
     if (ncol <= 32) return launch_draw_rng<2>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
     if (ncol <= 64) return launch_draw_rng<4>(ctx, ctx->stream, T, t_ldl, rows, info, seed, nullptr, 0, 0, lmax, lmax, F, ch, Gout, alm_dev);
