@@ -149,6 +149,9 @@ SIGNATURES = {
     "corahip_fftlog_phase": (c_int, [c_void_p, c_double, c_double, ctypes.c_int64, PTR]),
     "corahip_jl_romb": (c_int, [c_void_p, PTR, c_int, ctypes.POINTER(c_int), PTR, c_int, c_double, PTR, c_int, PTR]),
     "corahip_xi_rsd": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, PTR, PTR, ctypes.c_long, PTR, ctypes.c_long, PTR]),
+    "corahip_powerlaw_los": (c_int, [c_void_p, PTR, PTR, PTR, c_double, c_double, c_double, c_double, c_int, ctypes.c_long, c_int,
+                                     PTR]),
+    "corahip_field_moments": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, PTR]),
     "corahip_logconv": (c_int, [c_void_p, PTR, PTR, ctypes.c_int64, c_int, c_int]),
     "corahip_logconv_split": (c_int, [ctypes.c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
@@ -2033,6 +2036,65 @@ class Context:
         lnrd = self.to_device(lnr)
         _check(self.lib.corahip_galaxy_combine(self.h, self._f64(fg), self._f64(fgs), self._f64(haslam), self._f64(sc),
                                                self._f64(am), 1.0 / mv, self._f64(lnrd), nchan, skip, npix, self._f64(out)))
+        return out
+
+    # -- LOFAR synchrotron (csrc/lofar.hip) --------------------------------------------------------------------------------
+    def _depth_field(self, f, name):
+        """A contiguous float64 device field [..., nz] with at least two axes: (ncol, nz), ncol the product of the others."""
+        torch = _torch()
+        if (not isinstance(f, torch.Tensor) or f.dim() < 2 or f.dtype != torch.float64 or f.device != self.device
+                or not f.is_contiguous() or f.numel() < 1):
+            raise ValueError("%s must be a contiguous, non-empty float64 [..., nz] tensor on %s (got %r)"
+                             % (name, self.device, tuple(getattr(f, "shape", ()))))
+        nz = int(f.shape[-1])
+        return int(f.numel()) // nz, nz
+
+    @staticmethod
+    def powerlaw_range_check(xmax, b0, sb, beta_absmax):
+        """The guard of ``powerlaw_los`` (that of ``galaxy_combine``): ValueError unless ``xmax (|b0| + |sb| beta_absmax) <
+        512``, the range of the kernel's exp.  Host arithmetic only."""
+        if not float(xmax) * (abs(float(b0)) + abs(float(sb)) * float(beta_absmax)) < 512.0:      # (NaN fails too)
+            raise ValueError("powerlaw_los: |x (b0 + sb beta)| must stay below 512")
+
+    def field_moments(self, f):
+        """``(f.sum(axis=-1).std(), f.std(), abs(f).max())`` of a device field [..., nz] as host floats (numpy's ``ddof = 0``):
+        two passes each, fixed summation order, identical bits from call to call.  Waits for the result."""
+        ncol, nz = self._depth_field(f, "f")
+        out = self.empty((3,))
+        _check(self.lib.corahip_field_moments(self.h, self._f64(f), ncol, nz, self._f64(out)))
+        v = out.cpu().numpy()
+        return float(v[0]), float(v[1]), float(v[2])
+
+    def powerlaw_los(self, A, beta, x, a0=0.0, sa=1.0, b0=0.0, sb=1.0, out=None, beta_absmax=None):
+        """``out[i, p] = sum_z (a0 + sa A[p, z]) exp(x[i] (b0 + sb beta[p, z]))`` in one launch: [nfreq, ncol], ncol the
+        product of all axes of the fields but the last.
+
+        A, beta : device fields [..., nz] of one shape (``beta is A`` is allowed); x : [nfreq], host array or device
+        tensor, ``log(nu / nu_0)``; beta_absmax : ``max |beta|`` if the caller has it (``field_moments``), else it is
+        measured here.  ``max|x| (|b0| + |sb| max|beta|) < 512`` (the range of the kernel's exp): ValueError before the
+        launch otherwise.  The depth sum runs in the order of z whatever ``x`` holds: a subset of the channels gives the
+        bits those channels have in the full call."""
+        torch = _torch()
+        ncol, nz = self._depth_field(A, "A")
+        if beta is not A and (self._depth_field(beta, "beta") != (ncol, nz) or beta.shape != A.shape):
+            raise ValueError("beta has shape %r, expected %r" % (tuple(beta.shape), tuple(A.shape)))
+        if not isinstance(x, torch.Tensor):
+            x = self.to_device(np.asarray(x, dtype=np.float64).reshape(-1))
+        if x.dim() != 1 or x.numel() < 1 or x.dtype != torch.float64 or x.device != self.device or not x.is_contiguous():
+            raise ValueError("x must be a non-empty float64 vector")
+        nfreq = int(x.numel())
+        a0, sa, b0, sb = float(a0), float(sa), float(b0), float(sb)
+        if not all(np.isfinite(v) for v in (a0, sa, b0, sb)):
+            raise ValueError("powerlaw_los: a0, sa, b0, sb must be finite (got %r)" % ((a0, sa, b0, sb),))
+        bmax = float(self.field_moments(beta)[2] if beta_absmax is None else beta_absmax)
+        self.powerlaw_range_check(float(x.abs().max()), b0, sb, bmax)
+        out = self._out_like(out, (nfreq, ncol), "powerlaw_los")
+        obytes = out.numel() * 8
+        for t, name in ((A, "A"), (beta, "beta"), (x, "x")):
+            if self._overlap(out, obytes, t, t.numel() * 8):
+                raise ValueError("powerlaw_los: out overlaps %s" % name)
+        _check(self.lib.corahip_powerlaw_los(self.h, self._f64(A), self._f64(beta), self._f64(x), a0, sa, b0, sb, nfreq, ncol,
+                                             nz, self._f64(out)))
         return out
 
     # -- mkconstrained (csrc/constrained.hip) ------------------------------------------------------------------------------

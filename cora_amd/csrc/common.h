@@ -64,7 +64,7 @@ struct corahip_ctx {
     //        4 Legendre matrix of legendre_project, 5 its zero-padded operand, 6 block tables of normals_pcg64 /
     //        segment tables of normals_mt19937_legacy, 7 the two-slot ring of the l-range pipeline (drawstream.hip),
     //        8 barrier words of the cooperative Cholesky, 9 position lists of the MT19937 jump polynomials,
-    //        10 block partials of complex_variance (faraday.hip), 11 per-pixel source offsets of pointsource_paint,
+    //        10 block partials of complex_variance (faraday.hip) and of field_moments with its column sums (lofar.hip), 11 per-pixel source offsets of pointsource_paint,
     //        12 spline records + interval lookup table of xi_multi_average (corrfunc.hip)
     //  written whole by every call that reads them: 1, 3, 4, 5, 6, 7, 8, 10, 11, 12; caches behind a host flag: 0
     //  (tt_valid), 2 (pairs_key / pairs_ptr), 9 (mt_plist_ready)

@@ -1,1 +1,2 @@
-"""Counterpart of cora.foreground: gaussianfg, galaxy (parameter classes), pointsource (unresolved background)."""
+"""Counterpart of cora.foreground: gaussianfg, galaxy (parameter classes), pointsource (unresolved background), poisson,
+lofar (diffuse synchrotron from a spectral index per voxel)."""

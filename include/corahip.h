@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd, and (LOFAR synchrotron) powerlaw_los, field_moments */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -802,6 +802,24 @@ int corahip_eig_top_batched(corahip_ctx *ctx, const double *C, int nl, int F, in
 int corahip_constrained_weights(corahip_ctx *ctx, const double *V, int nl, int F, int k, const int32_t *f_ind, double *W,
                                 int32_t *info);
 int corahip_alm_mix_l(corahip_ctx *ctx, const double *alm_in, int lmax, int k, const double *W, int F, double *alm_out);
+
+/* ---- LOFAR diffuse synchrotron (cora/foreground/lofar.py:63-71; csrc/lofar.hip) ------------------------------------------
+ * All FP64, no atomics, one writer per element, every summation order a function of the shape alone: the same bits from
+ * call to call.
+ * powerlaw_los: A, beta [ncol, nz] (nz contiguous: the memory of an [x_num, y_num, nz] field), x [nfreq] = ln(nu_i / nu_0):
+ *              out[i, p] = sum_z (a0 + sa A[p, z]) exp(x[i] (b0 + sb beta[p, z])),   out [nfreq, ncol].
+ *            The affine maps are applied on the way in (one fma each); the raw fields are not written.  Per term
+ *            t = x b, e = exp(t), acc = fma(a, e, acc), z ascending from 0: the order depends on nz alone, so a channel
+ *            computed alone has the bits of the same channel computed among many.  exp is glibc's (csrc/glibc_exp.h): below
+ *            1 ulp, and |x (b0 + sb beta)| < 512 is the caller's to ensure.  With E = 1 that ulp bound,
+ *              |out - exact| <= (nz + 2 max|x b| + 2 E + 4) 2^-53 sum_z |a_z| exp(x_i b_z).
+ *            beta == A is allowed; out must not overlap an input.  nfreq, ncol, nz >= 1 (EINVAL otherwise, before any launch).
+ * field_moments: f [ncol, nz] -> out3 (device): out3[0] the population standard deviation (numpy's ddof = 0) of the column sums
+ *            s_p = sum_z f[p, z], out3[1] that of all elements, out3[2] = max |f|.  Two passes each, the mean and then the
+ *            squared deviations, over block partials and one ordered final pass (scratch slot 10).                          */
+int corahip_powerlaw_los(corahip_ctx *ctx, const double *A, const double *beta, const double *x, double a0, double sa,
+                         double b0, double sb, int nfreq, long ncol, int nz, double *out);
+int corahip_field_moments(corahip_ctx *ctx, const double *f, long ncol, int nz, double *out3);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
