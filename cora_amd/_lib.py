@@ -152,6 +152,10 @@ SIGNATURES = {
     "corahip_powerlaw_los": (c_int, [c_void_p, PTR, PTR, PTR, c_double, c_double, c_double, c_double, c_int, ctypes.c_long, c_int,
                                      PTR]),
     "corahip_field_moments": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, PTR]),
+    "corahip_sphbessel_radial": (c_int, [c_void_p, PTR, c_int, PTR, PTR, PTR, c_int, c_int, c_int, ctypes.c_long, PTR]),
+    "corahip_cl_gram": (c_int, [c_void_p, PTR, PTR, c_int, c_int, c_int, ctypes.c_long, PTR, c_int]),
+    "corahip_clarray_fullsky_workspace_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "corahip_clarray_fullsky": (c_int, [c_void_p, PTR, PTR, c_int, PTR, PTR, PTR, c_int, c_int, c_int, c_int, PTR, PTR]),
     "corahip_logconv": (c_int, [c_void_p, PTR, PTR, ctypes.c_int64, c_int, c_int]),
     "corahip_logconv_split": (c_int, [ctypes.c_int64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "corahip_sht_plan_rings": (c_int, [c_void_p, PTR, PTR, PTR, PTR]),
@@ -2095,6 +2099,116 @@ class Context:
                 raise ValueError("powerlaw_los: out overlaps %s" % name)
         _check(self.lib.corahip_powerlaw_los(self.h, self._f64(A), self._f64(beta), self._f64(x), a0, sa, b0, sb, nfreq, ncol,
                                              nz, self._f64(out)))
+        return out
+
+    # -- exact curved-sky C_l (csrc/fullsky.hip) ---------------------------------------------------------------------------
+    FULLSKY_MAX_NSUB = 17
+
+    def _fullsky_args(self, k, chi, cb, cf, lmax, name):
+        """(k [nk], chi, cb, cf [F, nsub]) as contiguous float64 device tensors, from host arrays or device tensors."""
+        torch = _torch()
+
+        def dev(a, nm):
+            if not isinstance(a, torch.Tensor):
+                a = self.to_device(np.asarray(a, dtype=np.float64))
+            if a.dtype != torch.float64 or a.device != self.device:
+                raise ValueError("%s: %s must be float64 on %s" % (name, nm, self.device))
+            return a.contiguous()
+
+        k, chi, cb, cf = dev(k, "k"), dev(chi, "chi"), dev(cb, "cb"), dev(cf, "cf")
+        if chi.dim() == 1:
+            chi, cb, cf = chi[:, None], cb[:, None] if cb.dim() == 1 else cb, cf[:, None] if cf.dim() == 1 else cf
+        if k.dim() != 1 or k.numel() < 1 or chi.dim() != 2 or cb.shape != chi.shape or cf.shape != chi.shape:
+            raise ValueError("%s: k must be [nk], chi, cb, cf of one shape [F, nsub] (got %r, %r, %r, %r)"
+                             % (name, tuple(k.shape), tuple(chi.shape), tuple(cb.shape), tuple(cf.shape)))
+        F, nsub = int(chi.shape[0]), int(chi.shape[1])
+        if F < 1 or F > 65535 or nsub < 1 or nsub > self.FULLSKY_MAX_NSUB:
+            raise ValueError("%s: 1 <= F <= 65535 and 1 <= nsub <= %d (got F = %d, nsub = %d)"
+                             % (name, self.FULLSKY_MAX_NSUB, F, nsub))
+        if int(lmax) != lmax or lmax < 0:
+            raise ValueError("%s: lmax must be a non-negative integer (got %r)" % (name, lmax))
+        return k, chi.contiguous(), cb.contiguous(), cf.contiguous(), F, nsub, int(lmax)
+
+    def sphbessel_radial(self, k, chi, cb, cf, lmax, ld_k=None):
+        """The radial table ``A[l, i, n] = sum_a cb[i, a] j_l(k_n chi[i, a]) - cf[i, a] j_l''(k_n chi[i, a])`` for
+        ``l = 0 .. lmax`` as a ``[lmax + 1, F, nk]`` device tensor (``corahip_sphbessel_radial``).
+
+        k : [nk] wavenumbers (>= 0, finite); chi, cb, cf : [F, nsub] (or [F]), the sub-samples of each channel with their
+        weights; host arrays or device tensors.  With ``ld_k > nk`` the result is the view ``[..., :nk]`` of a
+        ``[lmax + 1, F, ld_k]`` tensor whose other columns are zero.  j_l comes from the upward recurrence below the turning
+        point and a normalised downward one above it; the values are finite for every finite ``k chi >= 0`` and the same
+        from call to call."""
+        k, chi, cb, cf, F, nsub, lmax = self._fullsky_args(k, chi, cb, cf, lmax, "sphbessel_radial")
+        nk = int(k.numel())
+        ld = nk if ld_k is None else int(ld_k)
+        if ld < nk:
+            raise ValueError("sphbessel_radial: ld_k must be >= nk")
+        A = self.empty((lmax + 1, F, ld))
+        _check(self.lib.corahip_sphbessel_radial(self.h, self._f64(k), nk, self._f64(chi), self._f64(cb), self._f64(cf), F,
+                                                 nsub, lmax, ld, self._f64(A)))
+        return A if ld == nk else A[:, :, :nk]
+
+    def cl_gram(self, A, g, out=None, accumulate=False):
+        """``C[l, i, j] = sum_n g_n A[l, i, n] A[l, j, n]`` (added to ``out`` with ``accumulate``) as ``[nl, F, F]``: one
+        FP64 MFMA Gram product per l (``corahip_cl_gram``).
+
+        A : float64 device tensor [nl, F, nk], k contiguous; a view ``[..., :nk]`` of a wider tensor is taken as it is.
+        g : [nk], either sign.  The result equals its transpose bit for bit; the sum of an element runs over n in ascending
+        order whatever F is, so the rows of a subset of the channels give the bits of the full result's sub-block."""
+        torch = _torch()
+        if not isinstance(A, torch.Tensor) or A.dim() != 3 or A.dtype != torch.float64 or A.device != self.device or A.numel() < 1:
+            raise ValueError("cl_gram: A must be a non-empty float64 [nl, F, nk] tensor on %s" % (self.device,))
+        nl, F, nk = (int(v) for v in A.shape)
+        ld = int(A.stride(1)) if F > 1 else (int(A.stride(0)) if nl > 1 else nk)
+        if (nk > 1 and A.stride(2) != 1) or ld < nk or (nl > 1 and A.stride(0) != F * ld):
+            A = A.contiguous()
+            ld = nk
+        if not isinstance(g, torch.Tensor):
+            g = self.to_device(np.asarray(g, dtype=np.float64))
+        if g.dtype != torch.float64 or g.device != self.device or tuple(g.shape) != (nk,):
+            raise ValueError("cl_gram: g must be float64 [%d]" % nk)
+        g = g.contiguous()
+        if accumulate and out is None:
+            raise ValueError("cl_gram: accumulate needs out")
+        out = self._out_like(out, (nl, F, F), "cl_gram")
+        if self._overlap(out, out.numel() * 8, A, ((nl * F - 1) * ld + nk) * 8):
+            raise ValueError("cl_gram: out overlaps A")
+        _check(self.lib.corahip_cl_gram(self.h, c_void_p(A.data_ptr()), self._f64(g), nl - 1, F, nk, ld, self._f64(out),
+                                        1 if accumulate else 0))
+        return out
+
+    def clarray_fullsky_chunk(self, lmax, F, nk, max_bytes=None):
+        """The number of wavenumbers per pass of :meth:`clarray_fullsky` under a workspace budget of ``max_bytes`` (default:
+        a quarter of the device memory, at most 16 GiB): a multiple of 16, at least 16, no more than nk rounded up."""
+        torch = _torch()
+        if max_bytes is None:
+            max_bytes = min(torch.cuda.get_device_properties(self.device).total_memory // 4, 16 << 30)
+        per = 8 * (int(lmax) + 1) * int(F)
+        chunk = max(int(max_bytes) // per // 16 * 16, 16)
+        return min(chunk, (int(nk) + 15) // 16 * 16)
+
+    def clarray_fullsky(self, k, g, chi, cb, cf, lmax, max_bytes=None, nk_chunk=None):
+        """``C[l, i, j] = sum_n g_n A_l[i, n] A_l[j, n]`` with the radial table of :meth:`sphbessel_radial`, as a
+        ``[lmax + 1, F, F]`` device tensor (``corahip_clarray_fullsky``).  The k axis runs in ascending chunks whose table
+        fits ``max_bytes`` (:meth:`clarray_fullsky_chunk`; ``nk_chunk`` sets the length itself): table, then Gram product,
+        accumulating after the first.  Symmetric bit for bit, the same bits from call to call."""
+        torch = _torch()
+        k, chi, cb, cf, F, nsub, lmax = self._fullsky_args(k, chi, cb, cf, lmax, "clarray_fullsky")
+        nk = int(k.numel())
+        if not isinstance(g, torch.Tensor):
+            g = self.to_device(np.asarray(g, dtype=np.float64))
+        if g.dtype != torch.float64 or g.device != self.device or tuple(g.shape) != (nk,):
+            raise ValueError("clarray_fullsky: g must be float64 [%d]" % nk)
+        g = g.contiguous()
+        chunk = self.clarray_fullsky_chunk(lmax, F, nk, max_bytes) if nk_chunk is None else int(nk_chunk)
+        if chunk < 1:
+            raise ValueError("clarray_fullsky: nk_chunk must be positive")
+        b = c_size_t()
+        _check(self.lib.corahip_clarray_fullsky_workspace_bytes(lmax, F, chunk, ctypes.byref(b)))
+        work = torch.empty(int(b.value) // 8, dtype=torch.float64, device=self.device)
+        out = self.empty((lmax + 1, F, F))
+        _check(self.lib.corahip_clarray_fullsky(self.h, self._f64(k), self._f64(g), nk, self._f64(chi), self._f64(cb),
+                                                self._f64(cf), F, nsub, lmax, chunk, self._p(work), self._f64(out)))
         return out
 
     # -- mkconstrained (csrc/constrained.hip) ------------------------------------------------------------------------------

@@ -4,6 +4,7 @@ Same call surface as the reference (``clarray``, ``mkfullsky``); the work is don
 HIP kernels behind ``libcorahip.so``:
 
   clarray   -> K1  fused table-gather + Romberg channel average (21cm table model),
+                   radial table + Gram product per l (the exact curved-sky 21cm model),
                    outer-product kernel (separable foregrounds), or a device Romberg
                    reduction of host-evaluated samples (any other callable)
   mkfullsky -> K2  batched jittered Cholesky / eigen root per l
@@ -73,6 +74,11 @@ def clarray_device(aps, lmax, zarray, zromb=3, zwidth=None):
     if plan is not None and plan["kind"] == "separable":
         al, bcov = plan["prepare"](larr.copy(), za)
         return ctx.clarray_separable(ctx.to_device(al), ctx.to_device(bcov), zlen, zint, w)
+
+    if plan is not None and plan["kind"] == "fullsky":
+        # the exact curved-sky model: the channel average is taken inside the table of radial functions
+        p = plan["prepare"](za, zint, romberg_weights(zromb))
+        return ctx.clarray_fullsky(p["k"], p["g"], p["chi"], p["cb"], p["cf"], lmax)
 
     # generic callable: evaluate on the host in l-chunks, reduce on the device
     import torch

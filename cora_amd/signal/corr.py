@@ -17,7 +17,11 @@ csrc/rsdcorr.hip (``corahip_xi_rsd``: the six multipole splines and the Legendre
 points) on tables that ``gen_cache`` makes on the device (``corrfunc.ps_to_multipoles``: ``corahip_jl_romb`` and FFTLog) or
 ``_load_cache`` reads from a file.  ``powerspectrum`` / ``powerspectrum_1D`` call Python spectra and stay host numpy.
 
-``angular_powerspectrum_full`` of the reference's corr.py is dead code there and outside this package's scope.
+The exact curved-sky C_l(z, z') (``angular_powerspectrum_full``, corr.py:777-868: dead code in the reference, which
+imports a module that does not exist) runs through csrc/fullsky.hip: on one uniform wavenumber grid the integral is a
+Gram product over k of a table of radial functions, ``C_l[i, j] = sum_n g_n A_l[i, n] A_l[j, n]`` with ``A_l[i, n] =
+cb_i j_l(k_n chi_i) - cf_i j_l''(k_n chi_i)``; the channel average of ``skysim.clarray`` is taken inside the table.  The
+reference's piecewise adaptive integrator is not reproduced.
 """
 import math
 from os.path import exists
@@ -517,12 +521,107 @@ class RedshiftCorrelation(object):
         return dict(kind="table21cm", prepare=prepare)
 
     def _clarray_plan(self, aps):
-        """Protocol used by ``skysim.clarray`` to recognise the table model: only the un-overridden flat-sky
-        method qualifies (``angular_powerspectrum`` is an alias of it); any other bound method - a subclass
-        override, ``angular_powerspectrum_full``, ... - goes down the generic host-callable path."""
-        if getattr(aps, "__func__", None) is not RedshiftCorrelation.angular_powerspectrum_fft:
+        """Protocol used by ``skysim.clarray`` to recognise the models that run on the device: the un-overridden flat-sky
+        method (``angular_powerspectrum`` is an alias of it) is the table model, the un-overridden
+        ``angular_powerspectrum_full`` the exact curved-sky one; any other bound method - a subclass override, ... - goes
+        down the generic host-callable path."""
+        fn = getattr(aps, "__func__", None)
+        if fn is RedshiftCorrelation.angular_powerspectrum_full:
+            return self._fullsky_plan(lambda z: z)
+        if fn is not RedshiftCorrelation.angular_powerspectrum_fft:
             return None
         return self._table_plan(lambda z: z)
+
+    # ---- exact curved-sky C_l (corr.py:777-868) ------------------------------------------------
+    fullsky_oversample = 4
+    fullsky_kmax = None            # the upper limit of the k integral; None: the default of _fullsky_grid
+
+    def _fullsky_check(self):
+        if not self._vv_only:
+            raise Exception("Only works for vv_only at the moment.")
+        if self.ps_2d:
+            raise ValueError("angular_powerspectrum_full takes an isotropic ps_vv(k), not ps_2d")
+        if self._freq_window != 0:
+            raise ValueError("angular_powerspectrum_full: _freq_window must be 0 (the exact channel average of "
+                             "skysim.clarray replaces that window)")
+
+    def _fullsky_grid(self, chimax, kmax=None, oversample=None):
+        """The wavenumber grid of the exact C_l and its weights ``g_n = (2 / pi) w_n k_n^2 P(k_n)`` (host arrays).
+
+        Uniform from 0 to ``kmax`` with the largest step that is not above ``pi / (oversample chimax)`` - ``oversample``
+        samples per period of the fastest component ``cos(k (x1 + x2))``, default ``fullsky_oversample`` = 4 - and the
+        trapezoid weights ``w``: the integrand vanishes at both ends, so the rule converges fast.  ``kmax`` defaults to the
+        attribute ``fullsky_kmax`` and, where that is None, to ``6 _kstar`` for the library's own spline spectrum (``exp(-18)`` at the cut) and to ``kperpmax`` otherwise.
+        ``ps_vv`` is evaluated once, on the grid without k = 0 (where g = 0)."""
+        if kmax is None:
+            kmax = self.fullsky_kmax
+        if kmax is None:
+            sp = self._ps_spline_plan()
+            kmax = 6.0 * sp[1] if sp is not None else self.kperpmax
+        kmax = float(kmax)
+        oversample = self.fullsky_oversample if oversample is None else oversample
+        if not (kmax > 0 and np.isfinite(kmax)) or not (oversample > 0 and np.isfinite(oversample)):
+            raise ValueError("kmax and oversample must be positive (got %r, %r)" % (kmax, oversample))
+        if not (chimax > 0 and np.isfinite(chimax)):
+            raise ValueError("the largest comoving distance must be positive (got %r)" % (chimax,))
+        n = max(int(math.ceil(kmax * oversample * chimax / math.pi)), 1)
+        k = np.linspace(0.0, kmax, n + 1)
+        w = np.full(n + 1, kmax / n)
+        w[0] = w[-1] = 0.5 * kmax / n
+        g = np.zeros(n + 1)
+        g[1:] = (2.0 / math.pi) * w[1:] * k[1:] ** 2 * np.asarray(self.ps_vv(k[1:]), dtype=np.float64)
+        return k, g
+
+    def _fullsky_plan(self, za_to_z, kmax=None, oversample=None):
+        """The plan ``skysim.clarray`` runs the exact model by: ``prepare(za, zint, w)`` -> the arguments of
+        ``Context.clarray_fullsky`` for the ``F zint`` sub-samples ``za`` with Romberg weights ``w`` [zint]."""
+        self._fullsky_check()
+
+        def prepare(za, zint, w):
+            chi, pfd, f, b = self._z_quantities(za_to_z(np.asarray(za, dtype=np.float64)))
+            k, g = self._fullsky_grid(float(np.max(chi)), kmax, oversample)
+            wa = np.asarray(w, dtype=np.float64)[np.newaxis, :]
+            shape = (-1, zint)
+            return dict(k=k, g=g, chi=chi.reshape(shape), cb=wa * (pfd * b).reshape(shape), cf=wa * (pfd * f).reshape(shape))
+
+        return dict(kind="fullsky", prepare=prepare)
+
+    def angular_powerspectrum_full(self, la, za1, za2, kmax=None, oversample=None):
+        r"""The angular power spectrum C_l(z1, z2) on the curved sky, calculated explicitly (corr.py:777-868), at broadcast
+        points; a scalar in gives a float out.
+
+        .. math:: C_l(z_1, z_2) = \frac{2}{\pi} D_1 D_2 p_1 p_2 \int_0^{k_{max}} k^2 P(k)
+                  [b_1 j_l(k x_1) - f_1 j_l''(k x_1)] [b_2 j_l(k x_2) - f_2 j_l''(k x_2)] dk
+
+        for a model with ``ps_vv`` only (an Exception with the reference's message otherwise); ``ps_2d`` and a non-zero
+        ``_freq_window`` raise ValueError, and so does an ``l`` that is negative or not an integer.  The integral is the
+        trapezoid rule on the grid of :meth:`_fullsky_grid` for the largest distance among the redshifts (``kmax``,
+        ``oversample``: see there); the reference's piecewise adaptive scheme is not reproduced.  The per-redshift work is
+        done on the unique redshifts; the table of radial functions is built once for them, all C_l[i, j] up to the
+        largest l come from one Gram product per l on the device, and the requested (l, i, j) are gathered."""
+        self._fullsky_check()
+        la = np.asarray(la, dtype=np.float64)
+        za1, za2 = np.asarray(za1, dtype=np.float64), np.asarray(za2, dtype=np.float64)
+        if la.size and (not np.all(np.isfinite(la)) or np.any(la < 0) or np.any(la != np.round(la))):
+            raise ValueError("angular_powerspectrum_full: l must be a non-negative integer")
+        shape = np.broadcast(la, za1, za2).shape
+        if la.size == 0 or za1.size == 0 or za2.size == 0:
+            return np.zeros(shape)
+        zu, inv = np.unique(np.concatenate([za1.ravel(), za2.ravel()]), return_inverse=True)
+        chi, pfd, f, b = self._z_quantities(zu)
+        k, g = self._fullsky_grid(float(np.max(chi)), kmax, oversample)
+        i1 = inv[: za1.size].reshape(za1.shape)
+        i2 = inv[za1.size :].reshape(za2.shape)
+        import torch
+
+        ctx = _lib.get_context()
+        C = ctx.clarray_fullsky(k, g, chi, pfd * b, pfd * f, int(la.max()))
+
+        def index(a):
+            return torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, shape)).astype(np.int64).ravel()).to(ctx.device)
+
+        res = C[index(la), index(i1), index(i2)].cpu().numpy().reshape(shape)
+        return res if res.ndim else float(res)
 
     # ---- the aps callable ------------------------------------------------------------------
     def angular_powerspectrum_fft(self, la, za1, za2):

@@ -85,10 +85,23 @@ class Corr21cm(corr.RedshiftCorrelation, maps.Sky3d):
             z1, z2 = nu1, nu2
         return corr.RedshiftCorrelation.angular_powerspectrum_fft(self, l, z1, z2)
 
+    def angular_powerspectrum_full(self, l, nu1, nu2, redshift=False, kmax=None, oversample=None):
+        """C_l(nu1, nu2) on the curved sky by explicit integration; ``nu`` in MHz unless ``redshift`` is set
+        (corr21cm.py:211-236).  ``kmax``, ``oversample``: :meth:`RedshiftCorrelation._fullsky_grid`."""
+        if not redshift:
+            z1 = constants.nu21 / np.asarray(nu1, dtype=np.float64) - 1.0
+            z2 = constants.nu21 / np.asarray(nu2, dtype=np.float64) - 1.0
+        else:
+            z1, z2 = nu1, nu2
+        return corr.RedshiftCorrelation.angular_powerspectrum_full(self, l, z1, z2, kmax=kmax, oversample=oversample)
+
     def _clarray_plan(self, aps):
         # skysim.clarray samples in frequency (MHz) when driven through Sky3d
-        if getattr(aps, "__func__", None) is Corr21cm.angular_powerspectrum:
+        fn = getattr(aps, "__func__", None)
+        if fn is Corr21cm.angular_powerspectrum:
             return self._table_plan(lambda nu: constants.nu21 / nu - 1.0)
+        if fn is Corr21cm.angular_powerspectrum_full:
+            return self._fullsky_plan(lambda nu: constants.nu21 / nu - 1.0)
         return None
 
     def mean_nu(self, freq):

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd, and (LOFAR synchrotron) powerlaw_los, field_moments */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd, and (LOFAR synchrotron) powerlaw_los, field_moments, and (exact curved-sky C_l) sphbessel_radial, cl_gram, clarray_fullsky_workspace_bytes, clarray_fullsky */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -820,6 +820,31 @@ int corahip_alm_mix_l(corahip_ctx *ctx, const double *alm_in, int lmax, int k, c
 int corahip_powerlaw_los(corahip_ctx *ctx, const double *A, const double *beta, const double *x, double a0, double sa,
                          double b0, double sb, int nfreq, long ncol, int nz, double *out);
 int corahip_field_moments(corahip_ctx *ctx, const double *f, long ncol, int nz, double *out3);
+
+/* ---- exact curved-sky C_l(z, z') (angular_powerspectrum_full of cora/signal/corr.py:777-868; csrc/fullsky.hip) -------------
+ * C_l[i, j] = sum_n g_n A_l[i, n] A_l[j, n],  A_l[i, n] = sum_a cb[i, a] j_l(k_n chi[i, a]) - cf[i, a] j_l''(k_n chi[i, a]),
+ * g_n = (2 / pi) w_n k_n^2 P(k_n) on one wavenumber grid k [nk]; chi, cb, cf are [F, nsub] (the sub-samples of a channel with
+ * their quadrature weights folded into cb and cf).  All arrays on the device, FP64, no atomics, one writer per element, every
+ * summation order fixed: the same bits from call to call.
+ * sphbessel_radial: A [lmax + 1, F, ld_k] (k contiguous, ld_k >= nk; columns nk .. ld_k - 1 are written as zeros).
+ *            j_l by the upward recurrence while l <= x = k chi and by a downward (Miller) recurrence started at
+ *            lmax + 1 + ceil(sqrt(160 (lmax + 1))) + 30 above it, normalised at the turning point; j_l'' = (l (l - 1) / x^2 - 1)
+ *            j_l + (2 / x) j_{l+1}.  x = 0: j_0 = 1, j_0'' = -1/3, j_2'' = 2/15, zeros otherwise.  Finite for every finite x >= 0;
+ *            the error of j_l and of j_l'' stays within a few 1e-13 of the envelope 1 / max(x, 1) up to lmax = 3071
+ *            (tests/_fullsky_oracle.py).  1 <= nsub <= 17, F <= 65535 (EINVAL otherwise, before any launch).
+ * cl_gram:   C [lmax + 1, F, F] = (accumulate ? C : 0) + sum_{n < nk} g_n A[l, i, n] A[l, j, n] on FP64 MFMA; g of either
+ *            sign.  Elements i <= j are computed and written to both places: C equals its transpose bit for bit.  An
+ *            element's sum runs over n = 0, 1, ... in steps of 4 whatever F is: rows of a subset of the channels give the
+ *            bits of the full call's sub-block.  With accumulate only the upper triangle of C is read.
+ * clarray_fullsky: the k axis in chunks of nk_chunk, ascending: the table of a chunk into workspace
+ *            (clarray_fullsky_workspace_bytes(lmax, F, nk_chunk)), then cl_gram, accumulating after the first chunk.     */
+int corahip_sphbessel_radial(corahip_ctx *ctx, const double *k, int nk, const double *chi, const double *cb, const double *cf,
+                             int F, int nsub, int lmax, long ld_k, double *A);
+int corahip_cl_gram(corahip_ctx *ctx, const double *A, const double *g, int lmax, int F, int nk, long ld_k, double *C,
+                    int accumulate);
+int corahip_clarray_fullsky_workspace_bytes(int lmax, int F, int nk_chunk, size_t *bytes);
+int corahip_clarray_fullsky(corahip_ctx *ctx, const double *k, const double *g, int nk, const double *chi, const double *cb,
+                            const double *cf, int F, int nsub, int lmax, int nk_chunk, void *workspace, double *C);
 
 /* ring geometry of the plan (host arrays of length 4 nside - 1), for tests */
 int corahip_sht_plan_rings(const corahip_sht_plan *plan, int64_t *host_start, int32_t *host_nphi,
