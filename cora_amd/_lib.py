@@ -123,6 +123,7 @@ SIGNATURES = {
     "corahip_bias_field": (c_int, [c_void_p, PTR, PTR, PTR, PTR, c_int, ctypes.c_long, PTR]),
     "corahip_lognormal": (c_int, [c_void_p, PTR, PTR, PTR, c_double, c_int, ctypes.c_long, ctypes.c_long, PTR]),
     "corahip_alm_cross_spectra": (c_int, [c_void_p, PTR, c_int, PTR, c_int, c_int, PTR]),
+    "corahip_alm_gather_channels": (c_int, [c_void_p, PTR, c_int, PTR, c_int, c_int, PTR, c_int, c_int]),
     "corahip_healpix_interp_weights": (c_int, [c_void_p, c_int, PTR, PTR, ctypes.c_long, PTR, PTR]),
     "corahip_healpix_interp_val": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, PTR, PTR, ctypes.c_long, PTR]),
     "corahip_healpix_rotate_maps": (c_int, [c_void_p, PTR, ctypes.c_long, c_int, ctypes.POINTER(c_double), PTR]),
@@ -793,6 +794,55 @@ class Context:
                                                   ny, int(lmax), self._f64(out)))
         return out
 
+    def alm_gather_channels(self, src, nsrc, idx, dst, ndst, dst_first=0):
+        """Channel ``dst_first + j`` of ``dst`` = channel ``idx[j]`` of ``src`` for every j, both a_lm buffers in the
+        device layout ``[nalm, G, 2, 4]`` of the same lmax (``corahip_alm_gather_channels``): a streaming copy, bit for
+        bit, that writes nothing of ``dst`` outside those channels - the other channels of a shared group and the
+        padding keep what they held.  Returns ``dst``.
+
+        ``src`` has ``ceil(nsrc / 4)`` groups and ``dst`` ``ceil(ndst / 4)``: a buffer padded to 8 channels (what
+        ``map2alm_spin2`` returns) is passed with ``nsrc = 4 * src.shape[1]``.  ``idx``: a host sequence or a device
+        tensor of int32 (host integer arrays of another width are converted), checked here on the host - one entry at
+        least, every entry in ``[0, nsrc)``, ``dst_first + len(idx) <= ndst`` - ``ValueError`` otherwise; repeats are
+        fine.  ``dst`` must not overlap ``src``."""
+        torch = _torch()
+        nsrc, ndst, dst_first = int(nsrc), int(ndst), int(dst_first)
+        for t, name in ((src, "src"), (dst, "dst")):
+            if (not isinstance(t, torch.Tensor) or t.dim() != 4 or tuple(t.shape[2:]) != (2, 4) or t.dtype != torch.float64
+                    or t.device != self.device or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous float64 [nalm, G, 2, 4] tensor on %s" % (name, self.device))
+        nalm = int(src.shape[0])
+        lmax = int(round((np.sqrt(8.0 * nalm + 1.0) - 3.0) / 2.0))
+        if nalm < 1 or (lmax + 1) * (lmax + 2) // 2 != nalm or int(dst.shape[0]) != nalm:
+            raise ValueError("src and dst must hold the (lmax + 1)(lmax + 2) / 2 coefficients of one lmax (got %d and %d rows)"
+                             % (nalm, int(dst.shape[0])))
+        if nsrc < 1 or int(src.shape[1]) != (nsrc + 3) // 4:
+            raise ValueError("src has %d channel groups, nsrc = %d needs %d" % (int(src.shape[1]), nsrc, (nsrc + 3) // 4))
+        if ndst < 1 or int(dst.shape[1]) != (ndst + 3) // 4:
+            raise ValueError("dst has %d channel groups, ndst = %d needs %d" % (int(dst.shape[1]), ndst, (ndst + 3) // 4))
+        if isinstance(idx, torch.Tensor):
+            if idx.dtype != torch.int32:
+                raise ValueError("idx must be int32 (got %s)" % idx.dtype)
+            host = idx.detach().cpu().numpy()
+        else:
+            host = np.asarray(idx)
+            if host.dtype.kind not in "iu":
+                raise ValueError("idx must hold integers (got dtype %s)" % host.dtype)
+        if host.ndim != 1 or host.size < 1:
+            raise ValueError("idx must be one-dimensional with at least one entry (got shape %r)" % (host.shape,))
+        n = int(host.size)
+        if int(host.min()) < 0 or int(host.max()) >= nsrc:
+            raise ValueError("idx must lie in [0, %d) (got %d .. %d)" % (nsrc, int(host.min()), int(host.max())))
+        if dst_first < 0 or dst_first + n > ndst:
+            raise ValueError("channels %d .. %d do not fit the %d channels of dst" % (dst_first, dst_first + n - 1, ndst))
+        if self._overlap(dst, dst.numel() * 8, src, src.numel() * 8):
+            raise ValueError("alm_gather_channels: dst overlaps src")
+        if not (isinstance(idx, torch.Tensor) and idx.device == self.device and idx.is_contiguous()):
+            idx = self.to_device(host, dtype=np.int32)
+        _check(self.lib.corahip_alm_gather_channels(self.h, self._f64(src), nsrc, self._p(idx), n, lmax, self._f64(dst), ndst,
+                                                    dst_first))
+        return dst
+
     # -- K4/K5 ------------------------------------------------------------------------
     # truncation exponent of the Legendre sums used by plans made without an explicit one (0 = the library's
     # default, 2^-70); `Context.sht_cut_exp = -900` before the first transform keeps every representable term
@@ -1210,11 +1260,16 @@ class Context:
         first = np.clip(np.arange(n) - 2, 0, n - 4)
         return coef, first
 
-    def slice_diff2(self, f, x, g=None, h=None, s=None, t=None, out=None):
+    def slice_diff2(self, f, x, g=None, h=None, s=None, t=None, out=None, coef=None):
         """``lssutil.diff2(f, x, axis=0)`` of a device field f [n, ncol], n >= 4, equal to the reference bit for bit
         (the reference's operation order, no contraction).  With ``g``, ``h`` [n, ncol] and per-row factors ``s``,
         ``t``: ``out = (h + s[:, None] * g) + d2 * t[:, None]`` in one pass.  ``f=None`` (``x`` unused): ``out = h +
-        s[:, None] * g``.  ``out`` must not overlap ``f``."""
+        s[:, None] * g``.  ``out`` must not overlap ``f``; it may be ``g`` or ``h`` (an element is read before it is
+        written, by the same thread).
+
+        ``coef``: a ready-made host table [n, 4] in place of ``diff2_coefficients(x)`` (``x`` is then unused): any
+        stencil over the same four rows ``first[i] .. first[i] + 3``, evaluated as ``((c0 w0 + c1 w1) + c2 w2) + c3 w3``
+        (``lssutil.laplacian_device`` merges the radial terms of the Laplacian into one)."""
         if (g is None) != (h is None):
             raise ValueError("slice_diff2: g and h come together")
         ref = f if f is not None else g
@@ -1223,9 +1278,14 @@ class Context:
         n, ncol = self._field2d(ref, "f" if f is not None else "g")
         cdev = None
         if f is not None:
-            coef, _ = self.diff2_coefficients(x)
-            if coef.shape[0] != n:
-                raise ValueError("x has %d entries, f %d rows" % (coef.shape[0], n))
+            if coef is None:
+                coef, _ = self.diff2_coefficients(x)
+                if coef.shape[0] != n:
+                    raise ValueError("x has %d entries, f %d rows" % (coef.shape[0], n))
+            else:
+                coef = np.asarray(coef, dtype=np.float64)
+                if coef.shape != (n, 4) or n < 4:
+                    raise ValueError("coef has shape %r, expected %r with at least 4 rows" % (coef.shape, (n, 4)))
             cdev = self.to_device(coef)
         for a, name in ((g, "g"), (h, "h")):
             if a is not None and self._field2d(a, name) != (n, ncol):

@@ -522,32 +522,46 @@ def clarray_from_maps(maps, lmax=None, niter=None, use_weights=None):
     ``hputil.map2alm_device(maps, nside, lmax, use_weights, niter)`` (defaults as there), by one FP64 MFMA Gram product
     per l on the device (``Context.alm_cross_spectra``).  The result is symmetric in (i, j) bit for bit.
 
+    A polarised stack ``[numz, npol, npix]`` with planes (T, Q, U) or (T, Q, U, V) - what ``getpolsky`` returns - gives
+    the spectra of the fields (T, E, B[, V]) of all channels at once, ``[lmax + 1, P numz, P numz]`` with ``P = npol``
+    (``hputil.cross_spectra_pol_device``).  The index rule is field-major, channel ``p numz + i`` is field p of map i
+    (``hputil.sky_channel``): ``C.reshape(L, P, numz, P, numz)[l, p, i, q, j]`` is :math:`C_l^{pq}(\\nu_i, \\nu_j)`,
+    so ``[l, 1, :, 1, :]`` is EE, ``[l, 2, :, 2, :]`` BB, ``[l, 0, :, 1, :]`` TE.  E and B in HEALPix's convention;
+    any other ``npol`` raises ``Exception("Wrong number of polarisation components.")``.
+
     On maps made by :func:`mkfullsky` the expectation is not ``C_l`` but ``C_l (2l + 1/2) / (2l + 1)``:
     ``mkfullsky`` (like the reference) draws a complex ``a_l0`` of which the synthesis keeps the real part, half the
-    variance.  This function does not correct for it.
+    variance.  This function does not correct for it, in the polarised case either (every field of ``mkfullsky``
+    is a scalar map).
 
     Parameters
     ----------
-    maps : np.ndarray or device tensor (numz, npix)
+    maps : np.ndarray or device tensor (numz, npix) or (numz, npol, npix); any other rank is a ValueError
     lmax : integer, optional
         Default ``3 nside - 1``.
 
     Returns
     -------
-    cl : (lmax+1, numz, numz), a numpy array for host maps and a device tensor for device maps
+    cl : (lmax+1, numz, numz) or (lmax+1, npol numz, npol numz), a numpy array for host maps and a device tensor for
+        device maps
     """
     import torch
 
     from ..util import hputil
 
-    if isinstance(maps, torch.Tensor):
-        return hputil.cross_spectra_device(maps, lmax=lmax, use_weights=use_weights, niter=niter)
+    host = not isinstance(maps, torch.Tensor)
+    if host:
+        maps = np.asarray(maps, dtype=np.float64)
+    rank = maps.ndim
+    if rank not in (2, 3):
+        raise ValueError("maps must be [numz, npix] or [numz, npol, npix]")
+    if rank == 3:
+        hputil._check_sky(maps)
+    spectra = hputil.cross_spectra_device if rank == 2 else hputil.cross_spectra_pol_device
+    if not host:
+        return spectra(maps, lmax=lmax, use_weights=use_weights, niter=niter)
     ctx = _lib.get_context()
-    maps = np.ascontiguousarray(maps, dtype=np.float64)
-    if maps.ndim != 2:
-        raise ValueError("maps must be [numz, npix]")
-    cl = hputil.cross_spectra_device(torch.from_numpy(maps).to(ctx.device), lmax=lmax, use_weights=use_weights,
-                                     niter=niter)
+    cl = spectra(torch.from_numpy(np.ascontiguousarray(maps)).to(ctx.device), lmax=lmax, use_weights=use_weights, niter=niter)
     return cl.cpu().numpy()
 
 

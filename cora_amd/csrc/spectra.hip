@@ -25,6 +25,9 @@
 //                          Work per item grows as l + 1: the grid runs over l in descending order.
 //                          Padding channels (4 G > n) are staged like the others; they only ever reach rows / columns
 //                          >= n of the MFMA result, which are not stored.  Groups beyond G are staged as zeros.
+//   alm_gather_channels_kernel   the streaming copy that puts chosen channels of one a_lm buffer into a channel range of
+//                          another (T, E, B, V of a polarised sky into one field-major operand of the Gram kernel);
+//                          described at the kernel.
 // All element offsets are 64-bit (nalm * 8 G exceeds 2^31 at 256 channels, lmax 2048).
 #include "common.h"
 #include "mfma_tile.h"
@@ -143,6 +146,69 @@ cross_spectra_kernel(const double *__restrict__ A, int nx, int Ga, const double 
         }
 }
 
+// ---- channel gather in the a_lm layout: dst channel dst_first + j = src channel idx[j] ------------------------------------
+// Both buffers are [nalm][G][2][4]; channel c of an (l, m) row of 8 G doubles sits at 8 (c / 4) + 4 (Re, Im) + c % 4.  The
+// unit of work is a destination pair: 16 bytes = the same component of the channels (4 g + 2 h, 4 g + 2 h + 1).  A thread
+// owns one pair position of the row (group g, component, half h) for the whole call: it reads its (up to) two indices
+// once, and then walks the rows a, a + stride, ... with GC_U rows of loads in flight before the stores.  Lanes run along
+// the row (consecutive pairs = consecutive 16 bytes), and where the touched part of a row is shorter than the workgroup
+// the remaining threads take the following rows, so a wave writes contiguous runs of the touched groups of consecutive
+// rows.  A pair with both channels inside [dst_first, dst_first + n) takes one 16-byte store (and one 16-byte load when
+// its two sources are an aligned neighbouring pair); at the ragged ends the one channel inside takes an 8-byte store;
+// nothing else of dst is written: one writer per element, no atomics, no workspace.  An index outside [0, nsrc) writes
+// nothing for its channel (the Python binding refuses it before the launch).  All element offsets are 64-bit.
+constexpr int GC_NT = 256;
+constexpr int GC_U = 4;                 // rows in flight per thread
+
+__global__ void __launch_bounds__(GC_NT)
+alm_gather_channels_kernel(const double *__restrict__ src, int nsrc, int Gs, const int32_t *__restrict__ idx, int n, long nalm,
+                           double *__restrict__ dst, int Gd, int dst_first, int g0, int np, int W, int R) {
+    const int tid = threadIdx.x;
+    const int q = (int)blockIdx.x * W + tid % W, r = tid / W;       // pair position in the touched groups, row of the block
+    if (r >= R || q >= np) return;
+    const int g = g0 + (q >> 2), c = (q >> 1) & 1, h = q & 1;
+    const int j0 = 4 * g + 2 * h - dst_first, j1 = j0 + 1;
+    int s0 = -1, s1 = -1;
+    if (j0 >= 0 && j0 < n) s0 = idx[j0];
+    if (j1 >= 0 && j1 < n) s1 = idx[j1];
+    const bool w0 = (unsigned)s0 < (unsigned)nsrc, w1 = (unsigned)s1 < (unsigned)nsrc;
+    if (!w0 && !w1) return;
+    const size_t so0 = w0 ? (size_t)(8 * (s0 >> 2) + 4 * c + (s0 & 3)) : 0, so1 = w1 ? (size_t)(8 * (s1 >> 2) + 4 * c + (s1 & 3)) : 0;
+    const bool both = w0 && w1, wide = both && s1 == s0 + 1 && (s0 & 1) == 0;
+    const size_t srow = (size_t)Gs * 8, drow = (size_t)Gd * 8, doff = (size_t)(8 * g + 4 * c + 2 * h);
+    const long astep = (long)gridDim.y * R;
+    for (long a = (long)blockIdx.y * R + r; a < nalm; a += GC_U * astep) {
+        double2 v[GC_U];
+#pragma unroll
+        for (int u = 0; u < GC_U; u++) {
+            const long au = a + u * astep;
+            v[u] = make_double2(0.0, 0.0);
+            if (au < nalm) {
+                const double *sp = src + (size_t)au * srow;
+                if (wide)
+                    v[u] = *reinterpret_cast<const double2 *>(sp + so0);
+                else {
+                    if (w0) v[u].x = sp[so0];
+                    if (w1) v[u].y = sp[so1];
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < GC_U; u++) {
+            const long au = a + u * astep;
+            if (au < nalm) {
+                double *dp = dst + (size_t)au * drow + doff;
+                if (both)
+                    *reinterpret_cast<double2 *>(dp) = v[u];
+                else if (w0)
+                    dp[0] = v[u].x;
+                else
+                    dp[1] = v[u].y;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -163,6 +229,29 @@ int corahip_alm_cross_spectra(corahip_ctx *ctx, const double *alm_a, int nx, con
     StageTimer t(ctx, "alm_cross_spectra");
     hipLaunchKernelGGL(cross_spectra_kernel, dim3((unsigned)(ntiles * (lmax + 1))), dim3(CS_NT), 0, ctx->stream, alm_a, nx, Ga,
                        sym ? alm_a : alm_b, ny, Gb, lmax, sym ? 1 : 0, (int)nty, (int)ntiles, out);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+int corahip_alm_gather_channels(corahip_ctx *ctx, const double *src, int nsrc, const int32_t *idx, int n, int lmax,
+                                double *dst, int ndst, int dst_first) {
+    ARG_CHECK(ctx && src && idx && dst && nsrc >= 1 && ndst >= 1 && n >= 1 && lmax >= 0);
+    ARG_CHECK(dst_first >= 0 && dst_first <= ndst - n);
+    ARG_CHECK(is_aligned(src, 16) && is_aligned(dst, 16) && is_aligned(idx, 4));
+    const int Gs = (nsrc + 3) / 4, Gd = (ndst + 3) / 4;
+    const long nalm = nalm_of(lmax);
+    ARG_CHECK(!overlaps(dst, (size_t)nalm * Gd * 64, src, (size_t)nalm * Gs * 64));
+    const int g0 = dst_first / 4, g1 = (dst_first + n - 1) / 4;
+    const int np = 4 * (g1 - g0 + 1);                               // 16-byte pairs of a row in the touched groups
+    const int W = np < GC_NT ? np : GC_NT, R = GC_NT / W;           // pairs and rows a workgroup covers
+    const unsigned gx = (unsigned)((np + W - 1) / W);
+    long gy = (nalm + (long)R * GC_U - 1) / ((long)R * GC_U);       // enough row blocks for GC_U rows per thread ...
+    const long cap = (long)ctx->num_cu * 16 / gx;                   // ... at most 16 workgroups per CU in all
+    if (gy > cap) gy = cap;
+    if (gy < 1) gy = 1;
+    StageTimer t(ctx, "alm_gather_channels");
+    hipLaunchKernelGGL(alm_gather_channels_kernel, dim3(gx, (unsigned)gy), dim3(GC_NT), 0, ctx->stream, src, nsrc, Gs, idx, n,
+                       nalm, dst, Gd, dst_first, g0, np, W, R);
     LAUNCH_CHECK();
     return 0;
 }

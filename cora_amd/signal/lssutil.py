@@ -4,7 +4,8 @@
 csrc/lsschain.hip.  The angular derivatives come from the derivative
 synthesis (csrc/sht_der1.hip), the radial one from ``radial_gradient_kernel``; everything stays on the device in
 the ``_device`` forms.  The estimators ``pk_flat`` (:293-376), ``corrfunc`` (:379-443), ``ang_correlation`` (:446-464) and
-``transfer`` (:467-488) are read off the all-pairs spectra of the slices (csrc/spectra.hip)."""
+``transfer`` (:467-488) are read off the all-pairs spectra of the slices (csrc/spectra.hip).  ``laplacian`` (:188-222) is
+composed from the iterated analysis, ``alm_scale_l``, the synthesis and one merged radial stencil."""
 import numpy as np
 
 from .. import _lib
@@ -157,6 +158,127 @@ def gradient(maps, x, grad0=True, lmax=None, niter=3):
     ctx = _lib.get_context()
     dev = ctx.to_device(maps)
     return ctx.to_host(gradient_device(dev, np.asarray(x, dtype=np.float64), grad0=grad0, lmax=lmax, niter=niter))
+
+
+# ------------------------------------------------------------------------------------
+# the Laplacian in spherical coordinates (cora/signal/lssutil.py:188-222)
+# ------------------------------------------------------------------------------------
+def laplacian_coefficients(x):
+    """Host table [n, 4] of the radial part of :func:`laplacian` for coordinates ``x`` [n], n >= 4:
+    ``diff2(f, x)_i + (2 / x_i) np.gradient(f, x)_i = sum_k coef[i, k] f[first[i] + k]`` over the four rows
+    ``first[i] = min(max(i - 2, 0), n - 4)`` that ``corahip_slice_diff2`` reads.  ``Context.diff2_coefficients(x)`` plus
+    ``2 / x_i`` times ``Context.gradient_coefficients(x)``, whose rows i - 1, i, i + 1 (the one-sided pair at the ends)
+    always lie among those four: each entry is ``d_k + (2 / x_i) g_k`` with one product and one sum."""
+    x = np.asarray(x, dtype=np.float64)
+    coef, first = _lib.Context.diff2_coefficients(x)
+    grad = _lib.Context.gradient_coefficients(x)
+    n = x.size
+    coef = coef.copy()
+    for i in range(n):
+        for k in range(3):
+            row = i - 1 + k
+            if 0 <= row < n:
+                coef[i, row - first[i]] += (2.0 / x[i]) * grad[i, k]
+    return coef
+
+
+def laplacian_bytes(nside, lmax, chunk=SLICE_CHUNK):
+    """Upper bound of the temporary device memory of :func:`laplacian_device` beyond its input and its output, for slice
+    chunks of ``chunk``, from the library's own workspace sizes: the iterated analysis of a chunk (its synthesis and
+    its residual, the coefficients, their update and the padded buffer of a pass: two maps and three coefficient sets
+    per slice), the ``[chunk, lmax + 1]`` factors, the shared transform workspace (the larger of the analysis and the
+    synthesis of a chunk), plus 1 MiB of small tables."""
+    ctx = _lib.get_context()
+    nside, lmax, chunk = int(nside), int(lmax), max(4, int(chunk) // 4 * 4)
+    plan = ctx.sht_plan(nside, lmax)
+    npix = 12 * nside * nside
+    nalm = (lmax + 1) * (lmax + 2) // 2
+    alm = nalm * ((chunk + 7) // 8 * 2) * 64
+    ws = max(ctx.map2alm_workspace_bytes(plan, chunk), ctx.alm2map_workspace_bytes(plan, chunk))
+    return 2 * chunk * npix * 8 + 3 * alm + chunk * (lmax + 1) * 8 + ws + (1 << 20)
+
+
+def laplacian_device(maps, x, out=None, lmax=None, niter=3, chunk=SLICE_CHUNK):
+    """:func:`laplacian` on device tensors: maps [nmaps, npix] (float64, contiguous), ``x`` [nmaps] (host or device) ->
+    [nmaps, npix] (``out``: the tensor to write; it must not overlap ``maps``).
+
+    Angular part, per chunk of ``chunk`` slices: ``hputil.map2alm_device(use_weights=False, niter)``, the factors
+    ``fl[i, l] = -l (l + 1) / x_i^2`` applied by ``Context.alm_scale_l``, and ``Context.alm2map`` straight into ``out``.
+    Radial part: both terms are stencils over the same four rows, merged on the host into one table
+    (:func:`laplacian_coefficients`) and added to ``out`` in place by one ``Context.slice_diff2`` pass.  Temporaries
+    stay below :func:`laplacian_bytes`.  Needs at least 4 slices (``diff2``'s one-sided ends)."""
+    import torch
+
+    xh = _host_x(x)
+    nmaps, nside = check_maps(maps, xh)
+    if nmaps < 4:
+        raise ValueError("diff2 needs at least 4 samples along the axis (got %d)" % nmaps)
+    lmax = 3 * nside - 1 if lmax is None else int(lmax)
+    npix = 12 * nside * nside
+    ctx = _lib.get_context()
+    if out is None:
+        out = ctx.empty((nmaps, npix))
+    assert_shape(out, (nmaps, npix), "out")
+    for t, name in ((maps, "maps"), (out, "out")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 device tensor" % name)
+    if ctx._overlap(out, nmaps * npix * 8, maps, nmaps * npix * 8):
+        raise ValueError("laplacian: out overlaps maps")
+    coef = laplacian_coefficients(xh)
+    ll = np.arange(lmax + 1, dtype=np.float64)
+    fl = -(ll * (ll + 1.0))[None, :] / (xh * xh)[:, None]
+    chunk = max(4, int(chunk) // 4 * 4)
+    for c0 in range(0, nmaps, chunk):
+        n = min(chunk, nmaps - c0)
+        alm = hputil.map2alm_device(maps[c0:c0 + n], nside, lmax, use_weights=False, niter=niter)
+        ctx.alm_scale_l(alm, lmax, fl[c0:c0 + n], out=alm)
+        ctx.alm2map(alm, nside, lmax, n, out=out[c0:c0 + n])
+        del alm
+    # out = (out + 0 * out) + stencil(maps) * 1: the kernel's epilogue with h = g = out
+    ctx.slice_diff2(maps, xh, g=out, h=out, s=0.0, t=1.0, out=out, coef=coef)
+    return out
+
+
+def laplacian(maps, x, lmax=None, niter=3):
+    """Take the Laplacian of a set of maps in spherical coordinates (cora/signal/lssutil.py:188-222).
+
+    ``out_i = S[-l (l + 1) a_i] / x_i^2 + diff2(maps, x)_i + 2 np.gradient(maps, x, axis=0)_i / x_i`` with
+    ``a_i = map2alm(maps_i)`` - three refinements and no weights, healpy's defaults, which is what the reference
+    runs - and ``S`` the synthesis at the maps' nside.
+
+    The two radial terms are evaluated as ONE four-point stencil with merged coefficients
+    (:func:`laplacian_coefficients`) and added to the angular part, so the same terms are rounded in a different order
+    than in the reference's three separate additions: the results agree to a few ulp of the sum of the terms'
+    magnitudes, not bit for bit.  ``1 / x_i^2`` multiplies the coefficients before the synthesis, not the map after
+    it.  The ends follow the reference: ``diff2`` is one-sided (4-point) on rows 0, 1 and
+    N - 1, ``np.gradient`` first order on rows 0 and N - 1.
+
+    For up to ``SLICE_CHUNK`` maps this function runs the same kernels on the same batch shapes as
+    :func:`laplacian_device` and returns the host copy of its result.
+
+    Parameters
+    ----------
+    maps : np.ndarray[nmaps, npix]
+        HEALPix maps (RING) at the radial positions ``x``; at least 4.
+    x : np.ndarray[nmaps]
+        Radial coordinate of each map.
+    lmax : int, optional
+        Band limit of the analysis, default ``3 nside - 1`` (healpy's).
+    niter : int, optional
+        Refinements of the analysis (healpy's ``iter``), default 3.
+
+    Returns
+    -------
+    lap : np.ndarray[nmaps, npix]
+    """
+    maps = np.asarray(maps)
+    x = np.asarray(x)
+    nmaps, _ = check_maps(maps, x)
+    if nmaps < 4:
+        raise ValueError("diff2 needs at least 4 samples along the axis (got %d)" % nmaps)
+    ctx = _lib.get_context()
+    dev = ctx.to_device(maps)
+    return ctx.to_host(laplacian_device(dev, np.asarray(x, dtype=np.float64), lmax=lmax, niter=niter))
 
 
 # ------------------------------------------------------------------------------------

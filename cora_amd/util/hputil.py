@@ -557,13 +557,15 @@ def anafast(map1, map2=None, lmax=None, iter=3, use_weights=False, pol=False):
     ``lmax = 3 nside - 1``): one map -> ``[lmax + 1]``; maps ``[n, npix]`` -> ``[n (n + 1) / 2, lmax + 1]`` in the
     order of :func:`spectra_pair_order`; with ``map2`` (same shape) the cross spectra only, entry (i, j) from map i of
     ``map1`` and map j of ``map2``.  All pairs come from one call of the Gram kernel (:func:`cross_spectra_device`).
-    ``pol=True`` on more than one map (healpy: T, Q, U) is not implemented."""
+    ``pol=True`` on more than one map (healpy: T, Q, U) is not implemented here: the polarised spectra of a (T, Q, U)
+    triple are :func:`anafast_pol`."""
     import torch
 
     map1 = np.asarray(map1, dtype=np.float64)
     single = map1.ndim == 1
     if pol and not single:
-        raise NotImplementedError("anafast: polarised (spin-2) spectra are not implemented; pass pol=False")
+        raise NotImplementedError("anafast: polarised (spin-2) spectra of [T, Q, U] are hputil.anafast_pol; "
+                                  "anafast takes pol=False")
     m1 = np.ascontiguousarray(map1.reshape(1, -1) if single else map1)
     if m1.ndim != 2:
         raise ValueError("anafast takes one map or maps [n, npix]")
@@ -580,6 +582,163 @@ def anafast(map1, map2=None, lmax=None, iter=3, use_weights=False, pol=False):
     if single:
         return cl[:, 0, 0].copy()
     i, j = spectra_pair_order(m1.shape[0])
+    return np.ascontiguousarray(cl[:, i, j].T)
+
+
+# ------------------------------------------------------------------------------------
+# polarised skies: maps [F, npol, npix] of (T, Q, U[, V]) -> a_lm of (T, E, B[, V]) in one field-major buffer and the
+# spectra C_l^{pq}(nu, nu') of all of them from one Gram product (csrc/spectra.hip)
+# ------------------------------------------------------------------------------------
+SKY_CHUNK = 16      # frequency channels that go through the analysis together in map2alm_sky_device
+
+
+def sky_channel(p, f, nfreq):
+    """The field-major rule of :func:`map2alm_sky_device`: field ``p`` (0 = T, 1 = E, 2 = B, 3 = V) of frequency channel
+    ``f`` of ``nfreq`` is channel ``p * nfreq + f`` (scalars or arrays)."""
+    return np.asarray(p) * int(nfreq) + np.asarray(f)
+
+
+def _check_sky(maps, name="maps"):
+    """(F, npol, nside) of a polarised stack [F, npol, npix], npol 3 or 4 - decided on the shape alone."""
+    shape = tuple(maps.shape)
+    if len(shape) != 3:
+        raise ValueError("%s must be [nfreq, npol, npix] (got shape %r)" % (name, shape))
+    if shape[1] not in (3, 4):
+        raise Exception("Wrong number of polarisation components.")
+    if shape[0] < 1:
+        raise ValueError("%s holds no frequency channel" % name)
+    return int(shape[0]), int(shape[1]), _npix2nside(shape[2])
+
+
+def map2alm_sky_bytes(nside, lmax, npol, chunk=SKY_CHUNK):
+    """Upper bound of the temporary device memory of :func:`map2alm_sky_device` beyond its input and its output, for
+    chunks of ``chunk`` frequency channels, from the library's own workspace sizes.  With ``M`` the bytes of one map,
+    ``A(n) = nalm * 2 ceil(n / 8) * 64`` those of the coefficients of n channels padded to 8, ``c = chunk``,
+    ``s = (npol - 2) c`` scalar maps and ``p = 8 ceil(2 c / 8)``, the larger of
+
+    * the scalar planes: their contiguous copy, the synthesis and the residual of a refinement (``3 s M``), the
+      coefficients, their update and the padded buffer of a pass (``3 A(s)``);
+    * the (Q, U) planes: their copy ``2 c M``, the synthesis of the padded (E, B) set ``p M``, the residual ``2 c M``
+      and its six ring-scaled maps ``6 c M``, three (E, B) sets ``3 A(2 c)`` and the six-fold set of a pass twice
+      (``2 A(6 c)``: as :meth:`Context.map2alm` returns it and padded to 8),
+
+    plus the shared transform workspace (the largest of the analysis of ``s`` and ``6 c`` channels and the synthesis of
+    ``s`` and ``p``) and 1 MiB of small tables."""
+    ctx = _lib.get_context()
+    nside, lmax, npol, c = int(nside), int(lmax), int(npol), max(1, int(chunk))
+    if npol not in (3, 4):
+        raise Exception("Wrong number of polarisation components.")
+    plan = ctx.sht_plan(nside, lmax)
+    m = 12 * nside * nside * 8
+    nalm = (lmax + 1) * (lmax + 2) // 2
+
+    def a8(n):
+        return nalm * ((n + 7) // 8 * 2) * 64
+
+    s, p = (npol - 2) * c, (2 * c + 7) // 8 * 8
+    scal = 3 * s * m + 3 * a8(s)
+    pol = (10 * c + p) * m + 3 * a8(2 * c) + 2 * a8(6 * c)
+    ws = max(ctx.map2alm_workspace_bytes(plan, s), ctx.alm2map_workspace_bytes(plan, s),
+             ctx.map2alm_workspace_bytes(plan, 6 * c), ctx.alm2map_workspace_bytes(plan, p))
+    return max(scal, pol) + ws + (1 << 20)
+
+
+def map2alm_sky_device(maps, lmax=None, use_weights=None, niter=None, chunk=SKY_CHUNK):
+    """Analysis of a polarised sky: device maps ``[F, npol, npix]`` with planes (T, Q, U) or (T, Q, U, V) - what
+    ``getpolsky`` returns and :func:`sphtrans_sky` takes - -> one ``alm_dev [nalm, ceil(P F / 4), 2, 4]`` of ``P F``
+    channels, **field-major**: channel ``p F + f`` (:func:`sky_channel`) holds field p of frequency channel f, fields
+    in the order (T, E, B[, V]), ``P = npol``.  Any other ``npol`` raises ``Exception("Wrong number of polarisation
+    components.")`` as :func:`sphtrans_sky` does.  ``lmax`` defaults to ``3 nside - 1``, ``use_weights`` and ``niter``
+    to the module's ``_weight`` / ``_iter`` as in :func:`map2alm_device`.
+
+    E and B follow the convention documented at ``corahip_alm2map_spin2`` (HEALPix's: ``Q +- iU = - sum (a^E +- i a^B)
+    (+-2)Y_lm``); their ``l < 2`` coefficients are zero.  Padding channels of the last group are zero.
+
+    The channels go through in chunks of ``chunk`` frequencies: T (and V) of a chunk through :func:`map2alm_device`,
+    its (Q_f, U_f) pairs - adjacent rows ``npol f + 1``, ``npol f + 2`` of the flattened stack - through
+    :func:`map2alm_pol_device`, and each set of coefficients is put into the output by
+    ``Context.alm_gather_channels``, which also takes E and B apart (the spin-2 analysis returns them interleaved).
+    Temporaries stay below :func:`map2alm_sky_bytes`.
+
+    The default chunk of 16: at nside 1024 (lmax 3071, nalm 4 720 128, M = 100.7 MB) the (Q, U) side of the bound is
+    ``(160 + 32) M + 3 A(32) + 2 A(96)`` = 19.3 + 7.2 + 14.5 = 41.1 GB plus the workspace of a 96-channel analysis -
+    beside 77.3 GB of input and 58.0 GB of output for 256 channels x 3 planes on a 288 GB device - where the analysis
+    of all pairs at once takes six ring-scaled maps per pair alone, 155 GB."""
+    import torch
+
+    F, npol, nside = _check_sky(maps)
+    if not isinstance(maps, torch.Tensor) or maps.dtype != torch.float64:
+        raise ValueError("maps must be a float64 device tensor")
+    ctx = _lib.get_context()
+    if maps.device != ctx.device:
+        raise ValueError("maps must be on %s (got %s)" % (ctx.device, maps.device))
+    lmax = 3 * nside - 1 if lmax is None else int(lmax)
+    chunk = max(1, int(chunk))
+    npix = int(maps.shape[2])
+    nout = npol * F
+    out = ctx._alm_out(lmax, nout)
+    if nout % 4:
+        out[:, -1].zero_()                                  # the padding channels share this group; the gather keeps them
+    for f0 in range(0, F, chunk):
+        c = min(chunk, F - f0)
+        ar = np.arange(c, dtype=np.int32)
+        planes = [0] + ([3] if npol == 4 else [])
+        scal = torch.cat([maps[f0:f0 + c, p] for p in planes]) if len(planes) > 1 else maps[f0:f0 + c, 0].contiguous()
+        alm = map2alm_device(scal, nside, lmax, use_weights=use_weights, niter=niter)
+        del scal
+        for k, p in enumerate(planes):
+            ctx.alm_gather_channels(alm, 4 * alm.shape[1], k * c + ar, out, nout, dst_first=p * F + f0)
+        del alm
+        qu = maps[f0:f0 + c, 1:3].contiguous().view(2 * c, npix)
+        alm = map2alm_pol_device(qu, nside, lmax, use_weights=use_weights, niter=niter)
+        del qu
+        for k in (0, 1):                                    # E_f, B_f = channels 2 f, 2 f + 1 of the spin-2 result
+            ctx.alm_gather_channels(alm, 4 * alm.shape[1], 2 * ar + k, out, nout, dst_first=(1 + k) * F + f0)
+        del alm
+    return out
+
+
+def cross_spectra_pol_device(maps, maps2=None, lmax=None, use_weights=None, niter=None):
+    """Device maps ``[F, npol, npix]`` (and ``maps2 [F2, npol2, npix]``) of (T, Q, U[, V]) -> device
+    ``[lmax + 1, P F, P2 F2]``: ``C.reshape(L, P, F, P2, F2)[l, p, i, q, j]`` is ``C_l^{pq}(nu_i, nu_j)`` with p, q over
+    (T, E, B[, V]) - TT, EE, BB, TE, EB, TB and their frequency cross terms at once.  :func:`map2alm_sky_device`
+    (``use_weights``, ``niter`` as there) and one ``Context.alm_cross_spectra`` call on the field-major buffers; with
+    ``maps2=None`` the result equals its transpose bit for bit.  Default ``lmax = 3 nside - 1``."""
+    F, npol, nside = _check_sky(maps)
+    if maps2 is not None:
+        F2, npol2, nside2 = _check_sky(maps2, "maps2")
+        if nside2 != nside:
+            raise ValueError("maps2 must have the nside of maps")
+    ctx = _lib.get_context()
+    lmax = 3 * nside - 1 if lmax is None else int(lmax)
+    alm = map2alm_sky_device(maps, lmax, use_weights=use_weights, niter=niter)
+    if maps2 is None:
+        return ctx.alm_cross_spectra(alm, npol * F, lmax)
+    alm2 = map2alm_sky_device(maps2, lmax, use_weights=use_weights, niter=niter)
+    return ctx.alm_cross_spectra(alm, npol * F, lmax, alm_b=alm2, ny=npol2 * F2)
+
+
+def anafast_pol(map1, map2=None, lmax=None, iter=3, use_weights=False):
+    """``healpy.anafast(map1, map2, pol=True)`` for one polarised map ``[3, npix]`` (T, Q, U), with healpy's defaults
+    (``iter=3``, ``use_weights=False``, ``lmax = 3 nside - 1``): ``[6, lmax + 1]`` in healpy's order TT, EE, BB, TE, EB,
+    TB - :func:`spectra_pair_order` of 3 over (T, E, B).  With ``map2`` (same shape) entry (X, Y) takes X from ``map1``
+    and Y from ``map2``.  Any other shape raises ``ValueError``.  (:func:`cross_spectra_pol_device` underneath.)"""
+    import torch
+
+    m1 = np.asarray(map1, dtype=np.float64)
+    if m1.ndim != 2 or m1.shape[0] != 3:
+        raise ValueError("anafast_pol takes one polarised map [3, npix] of (T, Q, U) (got shape %r)" % (m1.shape,))
+    _npix2nside(m1.shape[1])
+    m2 = None
+    if map2 is not None:
+        m2 = np.asarray(map2, dtype=np.float64)
+        if m2.shape != m1.shape:
+            raise ValueError("anafast_pol: map2 must have the shape of map1")
+    ctx = _lib.get_context()
+    d1 = torch.from_numpy(np.ascontiguousarray(m1[None])).to(ctx.device)
+    d2 = None if m2 is None else torch.from_numpy(np.ascontiguousarray(m2[None])).to(ctx.device)
+    cl = cross_spectra_pol_device(d1, d2, lmax=lmax, use_weights=use_weights, niter=iter).cpu().numpy()
+    i, j = spectra_pair_order(3)
     return np.ascontiguousarray(cl[:, i, j].T)
 
 

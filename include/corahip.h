@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd, and (LOFAR synchrotron) powerlaw_los, field_moments, and (exact curved-sky C_l) sphbessel_radial, cl_gram, clarray_fullsky_workspace_bytes, clarray_fullsky */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd, and (LOFAR synchrotron) powerlaw_los, field_moments, and (exact curved-sky C_l) sphbessel_radial, cl_gram, clarray_fullsky_workspace_bytes, clarray_fullsky, and (polarised spectra) alm_gather_channels */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -656,6 +656,22 @@ int corahip_lognormal(corahip_ctx *ctx, const double *f, const double *hv, const
  * out must overlap neither operand.  nx, ny >= 1, lmax >= 0. */
 int corahip_alm_cross_spectra(corahip_ctx *ctx, const double *alm_a, int nx, const double *alm_b, int ny, int lmax,
                               double *out);
+
+/* Channel gather in the same layout: channel dst_first + j of dst = channel idx[j] of src, j < n, for every (l, m) and
+ * both components, bit for bit.  What puts T, E, B (and V) of a polarised sky - E and B interleaved in one buffer, T in
+ * another - into one field-major operand of alm_cross_spectra without full-size temporaries.
+ *   src, dst      device [nalm][G][2][4], 16-byte aligned, G = ceil(nsrc / 4) resp. ceil(ndst / 4) channel groups.  A
+ *                 buffer padded to 8 channels (a raw map2alm buffer, what Context.map2alm_spin2 returns) is passed with
+ *                 nsrc = 4 G, its padded channel count; its padding channels can then be indexed like any other.
+ *   idx           device int32 [n], every entry in [0, nsrc); repeats are allowed.  The library cannot check device data:
+ *                 an entry outside the range writes nothing for its channel (Context.alm_gather_channels refuses it on
+ *                 the host).
+ * Only channels [dst_first, dst_first + n) of dst are written: the other channels of the first and last group touched
+ * and the padding channels keep what they held.  One writer per element, no atomics, no workspace: identical bits from
+ * call to call.  16-byte stores for the pairs that lie inside the range, 8-byte stores at its ragged ends.  dst must not
+ * overlap src.  n, nsrc, ndst >= 1, 0 <= dst_first <= ndst - n, lmax >= 0 (EINVAL otherwise). */
+int corahip_alm_gather_channels(corahip_ctx *ctx, const double *src, int nsrc, const int32_t *idx, int n, int lmax,
+                                double *dst, int ndst, int dst_first);
 
 /* ---- HEALPix RING bilinear interpolation (csrc/hpinterp.hip): healpy.get_interp_weights / get_interp_val ------------
  * The published HEALPix scheme (get_interpol), restated: the two iso-latitude rings around theta (ring colatitudes are
