@@ -89,6 +89,8 @@ SIGNATURES = {
     "corahip_alm2map_spin2": (c_int, [c_void_p, c_void_p, PTR, c_int, PTR, c_void_p, c_size_t]),
     "corahip_spin2_ring_scale": (c_int, [c_void_p, c_void_p, PTR, c_int, PTR]),
     "corahip_spin2_combine": (c_int, [c_void_p, c_void_p, PTR, c_int, c_int, PTR, c_int]),
+    "corahip_map2alm_spin2_workspace_bytes": (c_int, [c_void_p, c_int, ctypes.POINTER(c_size_t)]),
+    "corahip_map2alm_spin2": (c_int, [c_void_p, c_void_p, PTR, c_int, PTR, PTR, c_void_p, c_size_t]),
     "corahip_xi_table_max_knots": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "corahip_xi_table_average": (c_int, [c_void_p, PTR, PTR, PTR, c_int, c_int, c_double, c_double, PTR, c_int, PTR, PTR,
                                          c_int, c_int, PTR]),
@@ -991,6 +993,44 @@ class Context:
             out = self.empty((nalm, gout, 2, 4))
         assert tuple(out.shape) == (nalm, gout, 2, 4), out.shape
         _check(self.lib.corahip_spin2_combine(self.h, plan, self._f64(a6), a6.shape[1], nf, self._f64(out), gout))
+        return out
+
+    # -- spin-2 analysis (one Legendre pass, csrc/sht_polana_native.hip) ----------------------
+    def map2alm_spin2_workspace_bytes(self, plan, nfields):
+        b = c_size_t()
+        _check(self.lib.corahip_map2alm_spin2_workspace_bytes(plan, nfields, ctypes.byref(b)))
+        return int(b.value)
+
+    def map2alm_spin2_native(self, maps_qu, nside, lmax, ring_w=None, chunk=None, out=None):
+        """The quadrature pass of ``map2alm_spin2`` as one Legendre pass (K5^T on the 2 nf channels + the adjoint of the
+        spin-2 synthesis kernel): same arguments, same layout of the result, no scaled copies of the maps.
+
+        Fields go through in chunks of `chunk` (a multiple of 4, so that every chunk fills whole 8-channel groups;
+        default: as many as a 96 GB workspace holds)."""
+        plan = self.sht_plan(nside, lmax)
+        n2, npix = maps_qu.shape
+        assert n2 % 2 == 0 and npix == 12 * nside * nside
+        nf = n2 // 2
+        nalm = (lmax + 1) * (lmax + 2) // 2
+        gout = (2 * nf + 7) // 8 * 2
+        if chunk is None:
+            per4 = self.map2alm_spin2_workspace_bytes(plan, 4)
+            chunk = max(4, min((int(96e9 // per4)) * 4, (nf + 3) // 4 * 4))
+        assert chunk >= 4 and chunk % 4 == 0
+        if out is None:
+            out = self.empty((nalm, gout, 2, 4))
+        assert tuple(out.shape) == (nalm, gout, 2, 4), out.shape
+        w = self._f64(ring_w) if ring_w is not None else None
+        for f0 in range(0, nf, chunk):
+            n = min(chunk, nf - f0)
+            gn = (2 * n + 7) // 8 * 2
+            need = self.map2alm_spin2_workspace_bytes(plan, n)
+            ws = self.workspace(need)
+            part = out if (f0 == 0 and n == nf) else self.empty((nalm, gn, 2, 4))
+            _check(self.lib.corahip_map2alm_spin2(self.h, plan, self._f64(maps_qu[2 * f0:2 * (f0 + n)]), n, w,
+                                                  self._f64(part), self._p(ws), need))
+            if part is not out:
+                out[:, f0 // 2:f0 // 2 + gn].copy_(part)
         return out
 
     # -- derivative synthesis (composition around the scalar synthesis, csrc/sht_der1.hip) --------------

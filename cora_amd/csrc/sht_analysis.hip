@@ -322,6 +322,7 @@ int sht_legendre_adj(corahip_ctx *ctx, const corahip_sht_plan *p, int ncols, con
     if (ntile > 16) return CORAHIP_EINVAL;      // (more than 16 ring tiles: nside > 16384)
     const int ntile128 = (p->npair + LMIN_RINGS - 1) / LMIN_RINGS;
     dim3 grid((unsigned)((p->L + 63) / 64), (unsigned)p->L);
+    StageTimer tr(ctx, "alm_reduce");           // (inside legendre_adj: the reduction's share of it)
     alm_reduce_rows_kernel<<<grid, 256, 0, ctx->stream>>>(part, p->nalm, ntile, ncols, p->lmax, ntile128, p->d_lmin, p->d_zeros, alm_dev);
     LAUNCH_CHECK();
     return 0;

@@ -128,3 +128,34 @@ extern "C" int corahip_alm2map_spin2(corahip_ctx *ctx, corahip_sht_plan *p, cons
     if (rc) return rc;
     return sht_ringfft(ctx, p, inter, nnu_pad8, nnu, maps);
 }
+
+// spin-2 analysis in one Legendre pass: G_m cells of the 2 nfields channels + (S_W, S_X) slabs per ring tile
+extern "C" int corahip_map2alm_spin2_workspace_bytes(const corahip_sht_plan *p, int nfields, size_t *bytes) {
+    ARG_CHECK(p != nullptr && bytes != nullptr && nfields >= 1);
+    const size_t G = nnu_pad_of(2 * nfields) / 4;
+    const int ntile = (p->npair + 64 * ADJ_WAVES - 1) / (64 * ADJ_WAVES);
+    *bytes = (size_t)p->nring * G * p->L * 8 * sizeof(double)            // G_m cells (the `inter` layout)
+             + (size_t)2 * ntile * p->nalm * G * 8 * sizeof(double);     // per-ring-tile partial S_W and S_X
+    return 0;
+}
+// maps_qu [2 nfields][npix] RING, (Q_f, U_f) interleaved -> alm_eb_dev [nalm][nnu_pad8(2 nfields)/4][2][4], (E_f, B_f)
+// interleaved: ONE weighted quadrature pass, the adjoint of corahip_alm2map_spin2
+extern "C" int corahip_map2alm_spin2(corahip_ctx *ctx, corahip_sht_plan *p, const double *maps_qu, int nfields,
+                                     const double *ring_w, double *alm_eb_dev, void *workspace, size_t workspace_bytes) {
+    ARG_CHECK(ctx != nullptr && p != nullptr && maps_qu != nullptr && alm_eb_dev != nullptr && workspace != nullptr);
+    ARG_CHECK(nfields >= 1 && 2 * nfields <= 65535);
+    size_t need;
+    corahip_map2alm_spin2_workspace_bytes(p, nfields, &need);
+    if (workspace_bytes < need) {
+        corahip_set_error("map2alm_spin2 workspace too small: %zu bytes, need %zu (process fewer fields per call)",
+                          workspace_bytes, need);
+        return CORAHIP_ENOMEM;
+    }
+    const int nnu = 2 * nfields, nnu_pad8 = nnu_pad_of(nnu);
+    const int G = nnu_pad8 / 4;
+    double *inter = (double *)workspace;
+    double *part = inter + (size_t)p->nring * G * p->L * 8;
+    int rc = sht_ringana(ctx, p, maps_qu, nnu, nnu_pad8, ring_w, inter);
+    if (rc) return rc;
+    return sht_legendre_adj_pol(ctx, p, 2 * nnu_pad8, nnu, inter, part, alm_eb_dev);
+}

@@ -3,7 +3,8 @@
 //   sht_legendre.hip  K4: Legendre contraction on FP64 MFMA (scalar and spin-2 forms)
 //   sht_ringfft.hip   K5 and K5^T: per-ring phase / fold / FFT (synthesis) and FFT / split (analysis)
 //   sht_analysis.hip  K4^T: adjoint Legendre contraction + reduction over ring tiles
-//   sht_api.hip       C ABI entry points (alm2map, map2alm, alm2map_spin2, workspace sizes)
+//   sht_polana_native.hip  K4^T for spin 2: (Q, U) ring spectra -> (E, B) in one Legendre pass + its tile reduction
+//   sht_api.hip       C ABI entry points (alm2map, map2alm, alm2map_spin2, map2alm_spin2, workspace sizes)
 //
 // Replaces hputil.sphtrans_inv_sky -> healpy.alm2map (cora/util/hputil.py:369-391,500-531) and, for the
 // "next" rows, healpy.map2alm and the polarised synthesis.  Definition implemented: SURVEY.md Appendix A
@@ -592,3 +593,7 @@ int sht_ringana(corahip_ctx *ctx, const corahip_sht_plan *p, const double *maps,
 // K4^T + reduction over ring tiles: G_m cells -> alm_dev (part: per-ring-tile scratch)
 int sht_legendre_adj(corahip_ctx *ctx, const corahip_sht_plan *p, int ncols, const double *inter, double *part,
                      double *alm_dev);
+// K4^T spin 2 + reduction over ring tiles (sht_polana_native.hip): G_m cells of nchan interleaved (Q, U) channels ->
+// interleaved (E, B) alm_dev (part: two slabs, S_W and S_X, per ring tile; builds the plan's g table on first use)
+int sht_legendre_adj_pol(corahip_ctx *ctx, corahip_sht_plan *p, int ncols, int nchan, const double *inter, double *part,
+                         double *alm_dev);

@@ -9,8 +9,10 @@
 // scaled ring by ring, because r1, r2 depend on the ring only and the sums run over north and south rings separately
 // (the parity signs of lambda_{l-1}, r2 are the ring's own).  So
 //   E_lm = -(sum W Q~ - i sum X U~),   B_lm = -(sum W U~ + i sum X Q~)
-// need six scalar transforms per (Q, U) pair: [Q, r1 Q, r2 Q, U, r1 U, r2 U] - three times the scalar cost per map
-// where a dedicated two-operand kernel (as on the synthesis side) would need two, and no new MFMA kernel.
+// need six scalar transforms per (Q, U) pair: [Q, r1 Q, r2 Q, U, r1 U, r2 U], and no new MFMA kernel.  The dedicated
+// two-operand kernel (sht_polana_native.hip, the adjoint of the synthesis side's) runs two ring transforms per pair
+// instead of six and holds no scaled maps; its Legendre work is four products (W Q~, W U~, X Q~, X U~) against these
+// six contractions - 1.5 by operation count, not 3.
 #include "sht_internal.h"
 
 int sht_ensure_polc(corahip_ctx *ctx, corahip_sht_plan *p);

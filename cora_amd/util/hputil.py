@@ -6,6 +6,8 @@
 ``sphtrans_real`` / ``sphtrans_sky`` / ``sph_ps`` call the adjoint kernels where the reference
 calls ``healpy.map2alm(use_weights=True, iter=2)`` (cora/util/hputil.py:46-47,195-234,460-497,607-619).
 """
+import contextlib
+
 import numpy as np
 
 from .. import _lib
@@ -272,6 +274,8 @@ def sphtrans_inv_sky(alm, nside):
 # ------------------------------------------------------------------------------------
 _weight = True   # cora/util/hputil.py:46
 _iter = 2        # cora/util/hputil.py:47
+_spin2_method = "composed"   # quadrature pass of the (Q, U) analysis: "composed" (six scalar passes, csrc/sht_polana.hip)
+                             # or "native" (one spin-2 Legendre pass, csrc/sht_polana_native.hip)
 _ring_weight_cache = {}
 
 
@@ -322,20 +326,47 @@ def map2alm_device(maps, nside, lmax, use_weights=None, niter=None):
     return alm
 
 
-def map2alm_pol_device(maps_qu, nside, lmax, use_weights=None, niter=None):
+def _resolve_spin2_method(method=None):
+    """``method`` of the (Q, U) analysis: None = the module's ``_spin2_method``; checked before any device work."""
+    method = _spin2_method if method is None else method
+    if method not in ("composed", "native"):
+        raise ValueError("method must be 'composed' or 'native' (got %r)" % (method,))
+    return method
+
+
+@contextlib.contextmanager
+def spin2_method(method):
+    """``with hputil.spin2_method("native"): ...`` - the module's ``_spin2_method`` for the duration of the block: the
+    route of :func:`map2alm_sky_device`, :func:`map2alm_sky_bytes`, :func:`cross_spectra_pol_device`,
+    :func:`anafast_pol` and everything built on them (``skysim.clarray_from_maps`` on polarised stacks), and of
+    :func:`map2alm_pol_device` called without ``method``.  Any value but "composed" / "native" raises ``ValueError``."""
+    global _spin2_method
+    method = _resolve_spin2_method(method)
+    saved, _spin2_method = _spin2_method, method
+    try:
+        yield method
+    finally:
+        _spin2_method = saved
+
+
+def map2alm_pol_device(maps_qu, nside, lmax, use_weights=None, niter=None, method=None):
     """Device maps [2 n, npix], (Q_f, U_f) interleaved -> alm_dev with (E_f, B_f) interleaved: the (Q, U) half of
     healpy.map2alm([T, Q, U], use_weights, iter) - a quadrature pass composed of scalar passes over ring-scaled
-    maps (csrc/sht_polana.hip) plus `niter` refinements alm <- alm + A(map - S alm) with the spin-2 synthesis."""
+    maps (csrc/sht_polana.hip) plus `niter` refinements alm <- alm + A(map - S alm) with the spin-2 synthesis.
+    ``method="native"`` runs every quadrature pass as one spin-2 Legendre pass (``Context.map2alm_spin2_native``) on the
+    maps as they are; None = the module's ``_spin2_method``, any other value raises ``ValueError``."""
+    method = _resolve_spin2_method(method)
     ctx = _lib.get_context()
+    analyse = ctx.map2alm_spin2_native if method == "native" else ctx.map2alm_spin2
     use_weights = _weight if use_weights is None else use_weights
     niter = _iter if niter is None else niter
     w = ctx.to_device(ring_weights(nside)) if use_weights else None
     n2 = maps_qu.shape[0]
-    alm = ctx.map2alm_spin2(maps_qu, int(nside), int(lmax), w)
+    alm = analyse(maps_qu, int(nside), int(lmax), w)
     nnu_pad = 4 * alm.shape[1]
     for _ in range(niter):
         back = ctx.alm2map_spin2(alm, int(nside), int(lmax), nnu_pad)[:n2]
-        alm = alm + ctx.map2alm_spin2(maps_qu - back, int(nside), int(lmax), w)
+        alm = alm + analyse(maps_qu - back, int(nside), int(lmax), w)
         del back
     return alm
 
@@ -623,7 +654,12 @@ def map2alm_sky_bytes(nside, lmax, npol, chunk=SKY_CHUNK):
       (``2 A(6 c)``: as :meth:`Context.map2alm` returns it and padded to 8),
 
     plus the shared transform workspace (the largest of the analysis of ``s`` and ``6 c`` channels and the synthesis of
-    ``s`` and ``p``) and 1 MiB of small tables."""
+    ``s`` and ``p``) and 1 MiB of small tables.
+
+    With the module's ``_spin2_method`` at "native" (:func:`spin2_method`) the (Q, U) side is that of the one-pass analysis: no
+    ring-scaled maps and no six-fold coefficient sets, ``(4 c + p) M + 3 A(2 c)``, and the workspace of the spin-2
+    analysis of ``c`` fields (``Context.map2alm_spin2_workspace_bytes``) in place of that of ``6 c`` scalar channels."""
+    method = _resolve_spin2_method()
     ctx = _lib.get_context()
     nside, lmax, npol, c = int(nside), int(lmax), int(npol), max(1, int(chunk))
     if npol not in (3, 4):
@@ -637,9 +673,14 @@ def map2alm_sky_bytes(nside, lmax, npol, chunk=SKY_CHUNK):
 
     s, p = (npol - 2) * c, (2 * c + 7) // 8 * 8
     scal = 3 * s * m + 3 * a8(s)
-    pol = (10 * c + p) * m + 3 * a8(2 * c) + 2 * a8(6 * c)
+    if method == "native":
+        pol = (4 * c + p) * m + 3 * a8(2 * c)
+        ana = ctx.map2alm_spin2_workspace_bytes(plan, c)
+    else:
+        pol = (10 * c + p) * m + 3 * a8(2 * c) + 2 * a8(6 * c)
+        ana = ctx.map2alm_workspace_bytes(plan, 6 * c)
     ws = max(ctx.map2alm_workspace_bytes(plan, s), ctx.alm2map_workspace_bytes(plan, s),
-             ctx.map2alm_workspace_bytes(plan, 6 * c), ctx.alm2map_workspace_bytes(plan, p))
+             ana, ctx.alm2map_workspace_bytes(plan, p))
     return max(scal, pol) + ws + (1 << 20)
 
 
@@ -663,9 +704,13 @@ def map2alm_sky_device(maps, lmax=None, use_weights=None, niter=None, chunk=SKY_
     The default chunk of 16: at nside 1024 (lmax 3071, nalm 4 720 128, M = 100.7 MB) the (Q, U) side of the bound is
     ``(160 + 32) M + 3 A(32) + 2 A(96)`` = 19.3 + 7.2 + 14.5 = 41.1 GB plus the workspace of a 96-channel analysis -
     beside 77.3 GB of input and 58.0 GB of output for 256 channels x 3 planes on a 288 GB device - where the analysis
-    of all pairs at once takes six ring-scaled maps per pair alone, 155 GB."""
+    of all pairs at once takes six ring-scaled maps per pair alone, 155 GB.
+
+    The (Q, U) pairs take the route of the module's ``_spin2_method`` ("composed" / "native", :func:`spin2_method`),
+    read once at entry and checked before any device work; the bound is :func:`map2alm_sky_bytes` under the same setting."""
     import torch
 
+    method = _resolve_spin2_method()
     F, npol, nside = _check_sky(maps)
     if not isinstance(maps, torch.Tensor) or maps.dtype != torch.float64:
         raise ValueError("maps must be a float64 device tensor")
@@ -690,7 +735,7 @@ def map2alm_sky_device(maps, lmax=None, use_weights=None, niter=None, chunk=SKY_
             ctx.alm_gather_channels(alm, 4 * alm.shape[1], k * c + ar, out, nout, dst_first=p * F + f0)
         del alm
         qu = maps[f0:f0 + c, 1:3].contiguous().view(2 * c, npix)
-        alm = map2alm_pol_device(qu, nside, lmax, use_weights=use_weights, niter=niter)
+        alm = map2alm_pol_device(qu, nside, lmax, use_weights=use_weights, niter=niter, method=method)
         del qu
         for k in (0, 1):                                    # E_f, B_f = channels 2 f, 2 f + 1 of the spin-2 result
             ctx.alm_gather_channels(alm, 4 * alm.shape[1], 2 * ar + k, out, nout, dst_first=(1 + k) * F + f0)
@@ -703,7 +748,9 @@ def cross_spectra_pol_device(maps, maps2=None, lmax=None, use_weights=None, nite
     ``[lmax + 1, P F, P2 F2]``: ``C.reshape(L, P, F, P2, F2)[l, p, i, q, j]`` is ``C_l^{pq}(nu_i, nu_j)`` with p, q over
     (T, E, B[, V]) - TT, EE, BB, TE, EB, TB and their frequency cross terms at once.  :func:`map2alm_sky_device`
     (``use_weights``, ``niter`` as there) and one ``Context.alm_cross_spectra`` call on the field-major buffers; with
-    ``maps2=None`` the result equals its transpose bit for bit.  Default ``lmax = 3 nside - 1``."""
+    ``maps2=None`` the result equals its transpose bit for bit.  Default ``lmax = 3 nside - 1``.  The route of the
+    (Q, U) analysis is the module's ``_spin2_method`` (:func:`spin2_method`)."""
+    _resolve_spin2_method()
     F, npol, nside = _check_sky(maps)
     if maps2 is not None:
         F2, npol2, nside2 = _check_sky(maps2, "maps2")
@@ -725,6 +772,7 @@ def anafast_pol(map1, map2=None, lmax=None, iter=3, use_weights=False):
     and Y from ``map2``.  Any other shape raises ``ValueError``.  (:func:`cross_spectra_pol_device` underneath.)"""
     import torch
 
+    _resolve_spin2_method()
     m1 = np.asarray(map1, dtype=np.float64)
     if m1.ndim != 2 or m1.shape[0] != 3:
         raise ValueError("anafast_pol takes one polarised map [3, npix] of (T, Q, U) (got shape %r)" % (m1.shape,))

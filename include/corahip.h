@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define CORAHIP_ABI_VERSION 1
-#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd, and (LOFAR synchrotron) powerlaw_los, field_moments, and (exact curved-sky C_l) sphbessel_radial, cl_gram, clarray_fullsky_workspace_bytes, clarray_fullsky, and (polarised spectra) alm_gather_channels */
+#define CORAHIP_ABI_MINOR 12     /* additions since version 1: 1 = normals_pcg64, pcg64_advance, draw_alm_rows, mkfullsky, mkfullsky_workspace_bytes, abi_minor, normals_mt19937_legacy; 2 = sht_lambda_entry (test hook); 3 = draw_alm_numpy, draw_alm_numpy_begin / _end, corahip_chanset: draw_alm_philox_rows_set, draw_alm_numpy_begin_set, randomfield_irfftn; 4 = glibc_exp (test hook), draw_alm_numpy_prepare / _run; 5 = healpix_neighbours, za_density_sph; 6 = der1_alm_prep, der1_combine, radial_gradient; 7 = slice_mix, slice_diff2, slice_moments, slice_moments_workspace_bytes, bias_field, lognormal; 8 = alm_cross_spectra; 9 = healpix_interp_weights, healpix_interp_val, healpix_rotate_maps, za_density_grid; 10 = xi_table_max_knots; 11 = complex_variance, faraday_mix, faraday_pack; 12 = pointsource_population, pointsource_paint, polarise_rotate, faraday_rotate, healpix_ud_grade, and (constrained galaxy) healpix_reorder, healpix_block_variance, alm_scale_l, galaxy_combine, and (mkconstrained) eig_top_batched, eig_top_max_f, constrained_weights, alm_mix_l, and (pk2xi) sinc_romb, fftlog_phase, logconv, logconv_split, and (initial LSS) xi_multi_average, cl_blocks, and (shot noise) normal_rows_pcg64, and (K4 lane segments) sht_lambda_segment_entry (test hook), and (poisoned scratch) debug_poison_scratch (test hook), and (redshift-space correlation) jl_romb, xi_rsd, and (LOFAR synchrotron) powerlaw_los, field_moments, and (exact curved-sky C_l) sphbessel_radial, cl_gram, clarray_fullsky_workspace_bytes, clarray_fullsky, and (polarised spectra) alm_gather_channels, and (native spin-2 analysis) map2alm_spin2_workspace_bytes, map2alm_spin2 */
 
 #define CORAHIP_EINVAL (-1)   /* bad argument / shape */
 #define CORAHIP_ENOMEM (-2)   /* workspace too small / allocation refused */
@@ -420,6 +420,15 @@ int corahip_spin2_ring_scale(corahip_ctx *ctx, corahip_sht_plan *plan, const dou
                              double *maps6);
 int corahip_spin2_combine(corahip_ctx *ctx, corahip_sht_plan *plan, const double *alm6_dev, int g6, int nfields,
                           double *alm_eb_dev, int gout);
+/* The same quadrature pass as ONE Legendre pass (csrc/sht_polana_native.hip, the adjoint of corahip_alm2map_spin2's
+ * kernel): the ring transforms run on the 2 nfields interleaved (Q_f, U_f) channels of maps_qu as they are, and
+ * W_lm, X_lm are formed inside the contraction: no scaled copies of the maps, two ring transforms per pair where the
+ * composition runs six.  alm_eb_dev: [nalm][nnu_pad8(2 nfields)/4][2][4], (E_f, B_f) = channels (2f, 2f+1), rows
+ * l < 2 and padding channels zero; ring_w as in corahip_map2alm.  Results are bit-identical from call to call.
+ * Workspace: corahip_map2alm_spin2_workspace_bytes(plan, nfields).                                        */
+int corahip_map2alm_spin2_workspace_bytes(const corahip_sht_plan *plan, int nfields, size_t *bytes);
+int corahip_map2alm_spin2(corahip_ctx *ctx, corahip_sht_plan *plan, const double *maps_qu, int nfields,
+                          const double *ring_w, double *alm_eb_dev, void *workspace, size_t workspace_bytes);
 
 /* ---- K0: the 21cm lookup tables (SURVEY 8 row a4 / section 2a "K0") ------------------------------
  * Replaces the one-off setup of RedshiftCorrelation.angular_powerspectrum_fft (cora/signal/corr.py:909-942)
